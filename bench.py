@@ -48,6 +48,11 @@ launch   : `bench.py --gpus N` without WORLD_SIZE in the environment spawns the 
            RCCL for the barrier and the max-over-ranks); under torch.distributed.run it checks
            --gpus against WORLD_SIZE.  `--dry-launch` exercises exactly that launch / shard /
            barrier / aggregate path with gloo on CPUs and no engine call (tests/test_dist_cpu.py).
+plain run: sets up, warms up (--warmup steps), times --steps steps and prints the line (`roofline` and `cpu_baseline`
+           null); `--dump-outputs DIR` then also writes the last step's product (a seeded sample of the batch elements:
+           residue words as 32-bit halves, their decryptions) as DIR/*.npy.  Everything below runs only with `--full`:
+           the bound-noise run, the decryption check, level 2, the in-situ profile and roofline, the RCCL self-check,
+           engine clock / power, the other legs and cpu_baseline.
 other legs (rank 0, skipped by --no-extras): the reference's other benchmark lines over the resident batch --
            `config.bgv_basic_ops` (benchmarks/bgv_basic.cpp:36-211) in the default line, `config.ckks_basic_ops`
            (benchmarks/ckks_basic.cpp:38-236) in the `--workload ckks65536` line, every result decrypted /
@@ -68,6 +73,7 @@ cpu_baseline: the CPU oracle = a port of the reference algorithm driven through 
            core, both on a bounded sample.
 """
 import argparse
+import contextlib
 import json
 import os
 import subprocess
@@ -267,7 +273,32 @@ def run_fixed(hx, ctx, primes, shape, B, steps, warmup, rng, sync, barrier):
         step()
     sync()
     barrier()
-    return time.perf_counter() - t0
+    return time.perf_counter() - t0, (out0, out1)
+
+
+DUMP_BYTES = 60_000_000       # (under the 64 MB a dump may take, headers included)
+
+
+def dump_outputs(out_dir, parts, primes, decrypt=None):
+    """--dump-outputs: the result of the last timed step as .npy files in `out_dir`.  `parts` are the result's
+    polynomials, uint64 residue rows [rows, batch, phi(m)]; each word is written as its high and low 32-bit halves
+    (part<i>_hi32 / part<i>_lo32, [elements, rows, phi(m)]), both exact in float64.  `decrypt(b)` (when given) is what
+    the caller decrypts element b to (`decrypted`, [elements, phi(m)]).  When the whole batch would exceed 64 MB the
+    elements are a fixed seeded sample of it (`batch_elements`); `result_primes` are the rows' prime indices."""
+    os.makedirs(out_dir, exist_ok=True)
+    nrows, batch, n = parts[0].shape
+    per_element = sum(p.shape[0] for p in parts) * n * 16 + (n * 8 if decrypt else 0)
+    count = max(1, min(batch, DUMP_BYTES // per_element))
+    elements = np.sort(np.random.default_rng(2024).choice(batch, count, replace=False))
+    out = {"batch_elements": elements, "result_primes": np.asarray(primes)}
+    for i, p in enumerate(parts):
+        words = np.ascontiguousarray(p[:, elements].transpose(1, 0, 2))
+        out[f"part{i}_hi32"] = words >> np.uint64(32)
+        out[f"part{i}_lo32"] = words & np.uint64(0xFFFFFFFF)
+    if decrypt:
+        out["decrypted"] = np.stack([decrypt(int(b)) for b in elements])
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.asarray(a).astype(np.float64))
 
 
 def real_inputs(hx, hc, cc, ctx, B, seed):
@@ -1205,6 +1236,13 @@ def main():
                     help="skip the secondary legs (python mirror, batch-1 latency, op list, levels of the other scheme, config 5)")
     ap.add_argument("--no-rccl-check", action="store_true", help="N = 1: skip the RCCL self-check (config.rccl_selfcheck)")
     ap.add_argument("--dry-launch", action="store_true", help="N-rank launch/aggregation path on CPUs (gloo), no engine")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: the bound-noise run, the decryption check of every product, level 2, "
+                         "the in-situ kernel table and roofline, the fixed-level and back-to-back NTT runs, engine clock / power, "
+                         "the RCCL self-check, the secondary legs (unless --no-extras) and cpu_baseline (unless --cpu-sample 0). "
+                         "Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path computed in its last step to DIR/<name>.npy (float64)")
     ap.add_argument("--cpu-worker", type=int, default=0, help=argparse.SUPPRESS)
     args = ap.parse_args()
     if not args.batch:
@@ -1315,28 +1353,27 @@ def main():
             return done[0], {"gather_and_verify_ms": round((time.perf_counter() - tg) * 1e3, 1), "product_bytes_this_rank": int(prod.size),
                              "gather_bytes_this_rank": int(mv)}
         n, l, k, d = sess.phim, sess.L_ctxt, sess.K, sess.D
-        dtb, host_b = run_session(sess, 1, steps4, args.warmup, R, sync, group.barrier, measure=False)
-        dtb = group.max_over_ranks(dtb) / steps4 * args.steps
-        host_b = host_b / steps4 * args.steps
+        if args.full:
+            dtb, host_b = run_session(sess, 1, steps4, args.warmup, R, sync, group.barrier, measure=False)
+            dtb = group.max_over_ranks(dtb) / steps4 * args.steps
+            host_b = host_b / steps4 * args.steps
+        else:
+            # what the bound-noise run absorbs in front of the timed loop (first launches, the arena's growth): two
+            # untimed multiplies, so that a --warmup 0 line does not time them either
+            sess.multiply(1, 2, True)
+            sync()
         from helib_amd import sensors
-        with sensors.Sampler(local_rank) as smp:           # engine clock / package power WHILE the timed loop runs
+        # (--full: engine clock / package power WHILE the timed loop runs)
+        with (sensors.Sampler(local_rank) if args.full else contextlib.nullcontext()) as smp:
             dt, host_s = run_session(sess, 1, args.steps, args.warmup, R, sync, group.barrier, measure=True)
         rate_rank = B * R * args.steps / dt                # this rank's own rate over its own clock
         rate_min, rate_max = group.min_over_ranks(rate_rank), group.max_over_ranks(rate_rank)
         dt = group.max_over_ranks(dt)
-        nver, gather1 = verify_level(1)                    # every batch element of the last product
-        res_primes = sess.result_primes(1)
-        prof1 = in_situ_profile(hx, sess, 1, 8, sync) if rank == 0 else None
-        # level 2: the kept product with itself (operands that carry the special primes of a key switch)
-        run_session(sess, 2, 1, 1, R, sync, group.barrier, measure=True)            # two full warm steps
-        malloc0 = sess.arena_stats()["hipMalloc_calls"]
-        dt2, _ = run_session(sess, 2, steps4, 0, R, sync, group.barrier, measure=True)
-        malloc2 = sess.arena_stats()["hipMalloc_calls"] - malloc0
-        dt2 = group.max_over_ranks(dt2)
-        nver2, gather2 = verify_level(2)
-        prof2 = in_situ_profile(hx, sess, 2, 4, sync, warm=8) if (rank == 0 and extras) else None
-        nver_all = int(group.sum_over_ranks(nver))
-        nver2_all = int(group.sum_over_ranks(nver2))
+        if args.dump_outputs and rank == 0:
+            # the kept level-1 product = the last multiply of the last timed step (every multiply of a step has the same
+            # operands); with --scatter this rank holds no secret key
+            dump_outputs(args.dump_outputs, [sess.ctxt_rows(1, 0, part)[1] for part in (0, 1)], sess.result_primes(1),
+                         None if args.scatter else (lambda b: sess.decrypt(1, b)[0]))
         mults = pairs_all * R * args.steps
         scheme = (f"CKKS m=65536 precision={args.precision} bits={args.bits}" if ckks else f"BGV m=32768 p=65537 bits={args.bits}")
         workload = (f"{scheme} (L={l}x{sess.ctxt_bits}b, K={k}x{sess.special_bits}b, {sess.n_small} small primes, D={d}): "
@@ -1354,214 +1391,235 @@ def main():
             per_mult = algorithmic_bytes_fixed(n, l, k, d)
         else:
             per_mult = algorithmic_bytes_fresh(n, l, k, d)
-        extra = {"host": "C++17: include/helib_amd_ctxt.hpp + helib_amd_keys.hpp in helib_amd/lib/libhelib_amd_host.so "
-                         "(helib_amd/csrc/host_session.cpp); python only times and checks",
-                 "mults_per_step": R, "multiplications_per_step_all_ranks": pairs_all * R,
-                 "timed_region_s": round(dt, 3),
-                 "bound_noise_mult_per_s": round(mults / dtb, 1),
-                 "bound_noise_ms_per_step": round(dtb / args.steps * 1e3, 4),
-                 # host time to enqueue a step: with measured noise it contains the waits for the norm read-backs;
-                 # the bound-noise run has no waits and is the enqueue cost (throttled by the HIP queue once it is full)
-                 "host_ms_per_step_incl_norm_waits": round(host_s / args.steps * 1e3, 4),
-                 "host_enqueue_ms_per_step": round(host_b / args.steps * 1e3, 4),
-                 "setup_s_keys_and_encryptions": round(t_setup, 2),
-                 "one_key_pair": (f"rank 0's key pair for all {world} ranks: {key_bytes} bytes of key material broadcast once "
-                                  f"({'gloo, --one-device' if args.one_device else 'RCCL'}), every rank encrypts its own slice under it"
-                                  if world > 1 else "single rank"),
-                 **smp.summary(),
-                 "process_group_world_size": group.world_size_seen(), "world_size_seen": group.world_size_seen(),
-                 "key_material_bytes_broadcast": key_bytes,
-                 "batch_split": ({"what": "rank 0 encrypts all pairs and keeps the secret key; public key material broadcast; each rank's "
-                                          "slice scattered as wire-format ciphertexts (Ctxt::writeTo, one device tensor per rank and "
-                                          f"operand, {'gloo' if args.one_device else 'RCCL send/recv'}); products gathered the same way; "
-                                          "rank 0 alone decrypts and verifies every product of every rank",
-                                  **split, "level1": gather1, "level2": gather2, "verified_on_rank0": True,
-                                  "ranks_hold_secret_key": "rank 0 only"} if args.scatter else
-                                 "not used: every rank encrypts its own slice (bench.py --scatter moves the ciphertexts instead)"),
-                 "per_rank_mult_per_s_min": round(rate_min, 1), "per_rank_mult_per_s_max": round(rate_max, 1),
-                 "extras": ("all secondary legs, roofline traffic, cpu_baseline and the RCCL self-check: this is the N = 1 line"
-                            if extras else ("skipped at N > 1: the ranks end together, the line carries the headline, the "
-                                            "in-situ kernel table and the roofline only" if world > 1 else "skipped (--no-extras)")),
-                 "result_primes": res_primes,
-                 "inputs": ("key pair, relinearisation matrix and public-key encryptions of random plaintexts made by the C++ "
-                            "host (helib_amd_keys.hpp: SecKey::GenSecKey, Encrypt / CKKSencrypt), as benchmarks/bgv_basic.cpp:144-157"),
-                 "verified": (f"decrypt(last product) == plaintext product mod (X^N+1{'' if ckks else ', p'}) for all {nver_all} batch "
-                              f"elements of all ranks" + (" (decoded: within the error bound the ciphertext reports AND correlated with "
-                                                          "the expected product beyond 8 sigma of an unrelated one; smallest correlation "
-                                                          f"{getattr(src or sess, 'min_ckks_correlation', float('nan')):.4f})" if ckks else "")
-                              + (" -- gathered as wire-format ciphertexts and decrypted by rank 0 alone (the only holder of the secret key)"
-                                 if args.scatter else "")),
-                 "level2": {"what": "product x product: both operands carry the special primes of the previous key switch "
-                                    "(the several-primes mod-switch in front of the tensor product)",
-                            "mult_per_s": round(pairs_all * R * steps4 / dt2, 1),
-                            "ms_per_mult_of_the_batch": round(dt2 / (steps4 * R) * 1e3, 4),
-                            "over_level1": round((dt2 / steps4) / (dt / args.steps), 3),
-                            "hipMalloc_calls_in_timed_window": malloc2,
-                            "verified_elements": nver2_all, "result_primes": sess.result_primes(2)}}
-        if world == 1 and not args.no_rccl_check:
-            # RCCL once before the 8-GPU node does it for us: the N-rank run's own calls in a world of one (<= 2 s)
-            # (with one real wire-format ciphertext through the scatter / gather code and through an RCCL broadcast)
-            extra["rccl_selfcheck"] = hdist.rccl_selfcheck(sess.export_public_keys(), torch.device("cuda", local_rank),
-                                                           ctxt_blob=sess.export_ctxts(0, 0, 0, 1))
-        extra["level2_mult_per_s"] = extra["level2"]["mult_per_s"]
-        extra["level2_over_level1"] = extra["level2"]["over_level1"]
-        if rank == 0:
-            table, us_per_mult = kernel_table(prof1, n, B, l, k, d, 8)
-            extra["kernels_in_situ"] = {"what": "one multiply of the batch, every launch bracketed by HIP events on its stream "
-                                                "(8 multiplies profiled after the timed region, behind 24 un-profiled ones)",
-                                        "kernel_us_per_multiply_of_the_batch": round(us_per_mult, 1),
-                                        "wall_us_per_multiply_of_the_batch": round(dt / (args.steps * R) * 1e6, 1),
-                                        "dropped_launch_records": prof1["dropped"], "kernels": table[:16]}
-            # the fused sequence's own compulsory bytes: what the kernels that ran are entitled to move (their
-            # algorithmic bytes per launch x launches per multiply), per ciphertext multiplication
-            fused = sum(r["algorithmic_bytes_per_launch"] * r["launches_per_multiply"] for r in table
-                        if "algorithmic_bytes_per_launch" in r) / B
-            share = sum(r["share"] for r in table if "algorithmic_bytes_per_launch" in r)
-            extra["fused_algorithmic_MB_per_mult"] = round(fused / 1e6, 2)
-            extra["fused_hbm_roofline_mult_per_s_per_gpu"] = round(HBM_PEAK_GBS * 1e9 / fused, 0)
-            extra["value_over_fused_roofline"] = round((pairs_all / world * R * args.steps / dt) / (HBM_PEAK_GBS * 1e9 / fused), 4)
-            extra["fused_bytes_cover_share_of_kernel_time"] = round(share, 3)
-            if prof2:
-                t2, us2 = kernel_table(prof2, n, B, l, k, d, 4)
-                extra["level2"]["kernels_in_situ"] = [{kk: r[kk] for kk in ("kernel", "workgroups", "launches_per_multiply", "avg_us",
-                                                                            "us_per_multiply", "share")} for r in t2[:14]]
-            b2b = None
-            if not ckks:
-                # the kernel-level pipeline alone (ctxt primes as rows 0.., specials after) + the back-to-back transform
-                cc = hc.ChainContext(32768, 65537, 1, bits=args.bits, c=3)
-                shape = dict(M=cc.m, L=l, K=k, digits=[[i - cc.ctxtPrimes[0] for i in dg] for dg in cc.digits])
-                sub = hx.Context(cc.m, local_rank)
-                fixed_primes = [cc.primes[i] for i in cc.ctxtPrimes + cc.specialPrimes]
-                for q in fixed_primes:
-                    sub.add_prime(q)
-                sub.set_stream(stream)
-                if world == 1:
-                    dtf = run_fixed(hx, sub, fixed_primes, shape, B, args.steps * R, args.warmup, rng, sync, lambda: None)
-                    extra["fixed_level_mult_per_s"] = round(B * R * args.steps / dtf, 1)
-                    extra["fixed_level_ms_per_mult_batch"] = round(dtf / (args.steps * R) * 1e3, 4)
-                    extra["fixed_level_algorithmic_MB_per_mult"] = round(algorithmic_bytes_fixed(n, l, k, d) / 1e6, 2)
-                b2b = ntt_back_to_back(hx, sub, fixed_primes, list(range(l)), list(range(l, l + k)), shape["digits"], B, rng,
-                                       args.ntt_iters)
-                rec = os.path.join(ROOT, "profiles", "r05_pmc_fresh_multiply_traffic.json")
-                if os.path.exists(rec):
-                    with open(rec) as f:
-                        tr = json.load(f)
-                    if tr.get("batch") == B and tr.get("bits") == args.bits:
-                        gb = tr["traffic_GB_per_multiply_of_the_batch"]
-                        extra["hbm_traffic_GB_per_step_recorded"] = round(gb * R, 1)
-                        extra["hbm_traffic_avg_TBps_over_the_step_recorded"] = round(gb * R / (dt / args.steps) / 1e3, 2)
-                        extra["hbm_traffic_source"] = ("recorded, not measured in this run: profiles/r05_pmc_fresh_multiply_traffic.json "
-                                                       "(rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over the same command, round 5's "
-                                                       "kernels -- the multiply path is unchanged since; counted at the L2, so "
-                                                       "Infinity-Cache hits are included)")
-                        extra["traffic_whole_operation"] = {"GB_per_multiply_of_the_batch": gb, "MB_per_mult": round(gb * 1e3 / B, 2),
-                                                            "avg_TBps_over_the_step": extra["hbm_traffic_avg_TBps_over_the_step_recorded"],
-                                                            "source": "recorded (profiles/r05_pmc_fresh_multiply_traffic.json), not measured in this run"}
-            roof = make_roofline(table, n, B, l, k, d, b2b)
-            if extras:
-                sync()
-                ts = []
-                for i in range(14):                      # one ciphertext pair at a time, as benchmarks/bgv_basic.cpp:158-164 times it
-                    sync()
-                    t0 = time.perf_counter()
-                    sess.multiply_single(True)
-                    sync()
-                    if i >= 2:
-                        ts.append((time.perf_counter() - t0) * 1e3)
-                ts.sort()
+        if not args.full:
+            extra = {"mults_per_step": R, "multiplications_per_step_all_ranks": pairs_all * R,
+                     "timed_region_s": round(dt, 3),
+                     "host_ms_per_step_incl_norm_waits": round(host_s / args.steps * 1e3, 4),
+                     "setup_s_keys_and_encryptions": round(t_setup, 2),
+                     "per_rank_mult_per_s_min": round(rate_min, 1), "per_rank_mult_per_s_max": round(rate_max, 1),
+                     "not_run": "bench.py --full: the decryption check, level 2, kernel table, roofline, secondary legs, cpu_baseline"}
+        else:
+            nver, gather1 = verify_level(1)                    # every batch element of the last product
+            res_primes = sess.result_primes(1)
+            prof1 = in_situ_profile(hx, sess, 1, 8, sync) if rank == 0 else None
+            # level 2: the kept product with itself (operands that carry the special primes of a key switch)
+            run_session(sess, 2, 1, 1, R, sync, group.barrier, measure=True)            # two full warm steps
+            malloc0 = sess.arena_stats()["hipMalloc_calls"]
+            dt2, _ = run_session(sess, 2, steps4, 0, R, sync, group.barrier, measure=True)
+            malloc2 = sess.arena_stats()["hipMalloc_calls"] - malloc0
+            dt2 = group.max_over_ranks(dt2)
+            nver2, gather2 = verify_level(2)
+            prof2 = in_situ_profile(hx, sess, 2, 4, sync, warm=8) if (rank == 0 and extras) else None
+            nver_all = int(group.sum_over_ranks(nver))
+            nver2_all = int(group.sum_over_ranks(nver2))
+            extra = {"host": "C++17: include/helib_amd_ctxt.hpp + helib_amd_keys.hpp in helib_amd/lib/libhelib_amd_host.so "
+                             "(helib_amd/csrc/host_session.cpp); python only times and checks",
+                     "mults_per_step": R, "multiplications_per_step_all_ranks": pairs_all * R,
+                     "timed_region_s": round(dt, 3),
+                     "bound_noise_mult_per_s": round(mults / dtb, 1),
+                     "bound_noise_ms_per_step": round(dtb / args.steps * 1e3, 4),
+                     # host time to enqueue a step: with measured noise it contains the waits for the norm read-backs;
+                     # the bound-noise run has no waits and is the enqueue cost (throttled by the HIP queue once it is full)
+                     "host_ms_per_step_incl_norm_waits": round(host_s / args.steps * 1e3, 4),
+                     "host_enqueue_ms_per_step": round(host_b / args.steps * 1e3, 4),
+                     "setup_s_keys_and_encryptions": round(t_setup, 2),
+                     "one_key_pair": (f"rank 0's key pair for all {world} ranks: {key_bytes} bytes of key material broadcast once "
+                                      f"({'gloo, --one-device' if args.one_device else 'RCCL'}), every rank encrypts its own slice under it"
+                                      if world > 1 else "single rank"),
+                     **smp.summary(),
+                     "process_group_world_size": group.world_size_seen(), "world_size_seen": group.world_size_seen(),
+                     "key_material_bytes_broadcast": key_bytes,
+                     "batch_split": ({"what": "rank 0 encrypts all pairs and keeps the secret key; public key material broadcast; each rank's "
+                                              "slice scattered as wire-format ciphertexts (Ctxt::writeTo, one device tensor per rank and "
+                                              f"operand, {'gloo' if args.one_device else 'RCCL send/recv'}); products gathered the same way; "
+                                              "rank 0 alone decrypts and verifies every product of every rank",
+                                      **split, "level1": gather1, "level2": gather2, "verified_on_rank0": True,
+                                      "ranks_hold_secret_key": "rank 0 only"} if args.scatter else
+                                     "not used: every rank encrypts its own slice (bench.py --scatter moves the ciphertexts instead)"),
+                     "per_rank_mult_per_s_min": round(rate_min, 1), "per_rank_mult_per_s_max": round(rate_max, 1),
+                     "extras": ("all secondary legs, roofline traffic, cpu_baseline and the RCCL self-check: this is the N = 1 line"
+                                if extras else ("skipped at N > 1: the ranks end together, the line carries the headline, the "
+                                                "in-situ kernel table and the roofline only" if world > 1 else "skipped (--no-extras)")),
+                     "result_primes": res_primes,
+                     "inputs": ("key pair, relinearisation matrix and public-key encryptions of random plaintexts made by the C++ "
+                                "host (helib_amd_keys.hpp: SecKey::GenSecKey, Encrypt / CKKSencrypt), as benchmarks/bgv_basic.cpp:144-157"),
+                     "verified": (f"decrypt(last product) == plaintext product mod (X^N+1{'' if ckks else ', p'}) for all {nver_all} batch "
+                                  f"elements of all ranks" + (" (decoded: within the error bound the ciphertext reports AND correlated with "
+                                                              "the expected product beyond 8 sigma of an unrelated one; smallest correlation "
+                                                              f"{getattr(src or sess, 'min_ckks_correlation', float('nan')):.4f})" if ckks else "")
+                                  + (" -- gathered as wire-format ciphertexts and decrypted by rank 0 alone (the only holder of the secret key)"
+                                     if args.scatter else "")),
+                     "level2": {"what": "product x product: both operands carry the special primes of the previous key switch "
+                                        "(the several-primes mod-switch in front of the tensor product)",
+                                "mult_per_s": round(pairs_all * R * steps4 / dt2, 1),
+                                "ms_per_mult_of_the_batch": round(dt2 / (steps4 * R) * 1e3, 4),
+                                "over_level1": round((dt2 / steps4) / (dt / args.steps), 3),
+                                "hipMalloc_calls_in_timed_window": malloc2,
+                                "verified_elements": nver2_all, "result_primes": sess.result_primes(2)}}
+            if world == 1 and not args.no_rccl_check:
+                # RCCL once before the 8-GPU node does it for us: the N-rank run's own calls in a world of one (<= 2 s)
+                # (with one real wire-format ciphertext through the scatter / gather code and through an RCCL broadcast)
+                extra["rccl_selfcheck"] = hdist.rccl_selfcheck(sess.export_public_keys(), torch.device("cuda", local_rank),
+                                                               ctxt_blob=sess.export_ctxts(0, 0, 0, 1))
+            extra["level2_mult_per_s"] = extra["level2"]["mult_per_s"]
+            extra["level2_over_level1"] = extra["level2"]["over_level1"]
+            if rank == 0:
+                table, us_per_mult = kernel_table(prof1, n, B, l, k, d, 8)
+                extra["kernels_in_situ"] = {"what": "one multiply of the batch, every launch bracketed by HIP events on its stream "
+                                                    "(8 multiplies profiled after the timed region, behind 24 un-profiled ones)",
+                                            "kernel_us_per_multiply_of_the_batch": round(us_per_mult, 1),
+                                            "wall_us_per_multiply_of_the_batch": round(dt / (args.steps * R) * 1e6, 1),
+                                            "dropped_launch_records": prof1["dropped"], "kernels": table[:16]}
+                # the fused sequence's own compulsory bytes: what the kernels that ran are entitled to move (their
+                # algorithmic bytes per launch x launches per multiply), per ciphertext multiplication
+                fused = sum(r["algorithmic_bytes_per_launch"] * r["launches_per_multiply"] for r in table
+                            if "algorithmic_bytes_per_launch" in r) / B
+                share = sum(r["share"] for r in table if "algorithmic_bytes_per_launch" in r)
+                extra["fused_algorithmic_MB_per_mult"] = round(fused / 1e6, 2)
+                extra["fused_hbm_roofline_mult_per_s_per_gpu"] = round(HBM_PEAK_GBS * 1e9 / fused, 0)
+                extra["value_over_fused_roofline"] = round((pairs_all / world * R * args.steps / dt) / (HBM_PEAK_GBS * 1e9 / fused), 4)
+                extra["fused_bytes_cover_share_of_kernel_time"] = round(share, 3)
+                if prof2:
+                    t2, us2 = kernel_table(prof2, n, B, l, k, d, 4)
+                    extra["level2"]["kernels_in_situ"] = [{kk: r[kk] for kk in ("kernel", "workgroups", "launches_per_multiply", "avg_us",
+                                                                                "us_per_multiply", "share")} for r in t2[:14]]
+                b2b = None
                 if not ckks:
-                    try:     # batched Encrypt / Decrypt in the C++ host (the reference times one ciphertext per call)
-                        extra["batched_encrypt_decrypt"] = sess.encrypt_decrypt_batch(min(B, 64), 3)
-                        if not extra["batched_encrypt_decrypt"]["all_elements_round_trip"]:
-                            raise SystemExit("bench: DecryptBatch(EncryptBatch(m)) != m")
-                    except SystemExit:
-                        raise
-                    except Exception as e:
-                        extra["batched_encrypt_decrypt"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
-                extra["batch1_latency_ms"] = round(ts[len(ts) // 2], 4)
-                extra["batch1_latency_ms_min"] = round(ts[0], 4)
-                try:
-                    c12 = config1_2_leg(hx)
-                    extra.update(c12)
-                    c1, c2 = c12["config1_fft_bench"], c12["config2_doublecrt_add_mul"]["batch64"]
-                    extra.update({"config1_fft_forward_us_one_row": c1["forward_us_one_row"], "config1_fft_forward_GBps": c1["forward_GBps"],
-                                  "config1_fft_inverse_GBps": c1["inverse_GBps"], "config2_add_GBps": c2["add_GBps"],
-                                  "config2_mul_GBps": c2["mul_GBps"]})
-                except Exception as e:
-                    extra["config1_fft_bench"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
-                try:
-                    extra["config5_bluestein"] = config5_leg(hx)
-                    extra["config5_bluestein_forward_ns_per_row"] = extra["config5_bluestein"]["forward"]["ns_per_row"]
-                    extra["config5_bluestein_inverse_ns_per_row"] = extra["config5_bluestein"]["inverse"]["ns_per_row"]
-                except Exception as e:
-                    extra["config5_bluestein"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
-                # the other workloads through the same C++ host, two levels each: the other scheme at its BASELINE shape,
-                # and the reference's OWN benchmark parameters (benchmarks/bgv_basic.cpp:247 bits=6400,
-                # benchmarks/ckks_basic.cpp:263 precision=1 bits=440)
-                legs = {"bgv32768_bits950": (("bgv", 32768, 65537, 1, 950), 128, 8),
-                        "ckks65536_bits1400": (("ckks", 65536, -1, args.precision, 1400), 64, 8),
-                        "ckks65536_bits440_reference_params": (("ckks", 65536, -1, 1, 440), 64, 8),
-                        "bgv32768_bits6400_reference_params": (("bgv", 32768, 65537, 1, 6400), 16, 4),
-                        # the reference's general-m benchmark ring (benchmarks/bgv_basic.cpp:236 big_params): m = 32003 prime,
-                        # p = 2, bits = 5800 -- every transform a Bluestein convolution
-                        "bgv32003_bits5800_reference_params": (("bgv", 32003, 2, 1, 5800), 8, 2),
-                        # BASELINE configs[4]'s ring end to end (tests/GTestBootstrapping.cpp:113: m = 21845 = 5 * 17 * 257, p = 2):
-                        # every transform of the multiply is the Good-Thomas x Rader kernel (round 6; Bluestein under HX_NO_PFA)
-                        "bgv21845_bits950_config5_ring": (("bgv", 21845, 2, 1, 950), 32, 4)}
-                mine = "ckks65536_bits%d" % args.bits if ckks else "bgv32768_bits%d" % args.bits
-                for name, (sp, bb, rr) in legs.items():
-                    if name.startswith(mine):
-                        continue
+                    # the kernel-level pipeline alone (ctxt primes as rows 0.., specials after) + the back-to-back transform
+                    cc = hc.ChainContext(32768, 65537, 1, bits=args.bits, c=3)
+                    shape = dict(M=cc.m, L=l, K=k, digits=[[i - cc.ctxtPrimes[0] for i in dg] for dg in cc.digits])
+                    sub = hx.Context(cc.m, local_rank)
+                    fixed_primes = [cc.primes[i] for i in cc.ctxtPrimes + cc.specialPrimes]
+                    for q in fixed_primes:
+                        sub.add_prime(q)
+                    sub.set_stream(stream)
+                    if world == 1:
+                        dtf, _ = run_fixed(hx, sub, fixed_primes, shape, B, args.steps * R, args.warmup, rng, sync, lambda: None)
+                        extra["fixed_level_mult_per_s"] = round(B * R * args.steps / dtf, 1)
+                        extra["fixed_level_ms_per_mult_batch"] = round(dtf / (args.steps * R) * 1e3, 4)
+                        extra["fixed_level_algorithmic_MB_per_mult"] = round(algorithmic_bytes_fixed(n, l, k, d) / 1e6, 2)
+                    b2b = ntt_back_to_back(hx, sub, fixed_primes, list(range(l)), list(range(l, l + k)), shape["digits"], B, rng,
+                                           args.ntt_iters)
+                    rec = os.path.join(ROOT, "profiles", "r05_pmc_fresh_multiply_traffic.json")
+                    if os.path.exists(rec):
+                        with open(rec) as f:
+                            tr = json.load(f)
+                        if tr.get("batch") == B and tr.get("bits") == args.bits:
+                            gb = tr["traffic_GB_per_multiply_of_the_batch"]
+                            extra["hbm_traffic_GB_per_step_recorded"] = round(gb * R, 1)
+                            extra["hbm_traffic_avg_TBps_over_the_step_recorded"] = round(gb * R / (dt / args.steps) / 1e3, 2)
+                            extra["hbm_traffic_source"] = ("recorded, not measured in this run: profiles/r05_pmc_fresh_multiply_traffic.json "
+                                                           "(rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over the same command, round 5's "
+                                                           "kernels -- the multiply path is unchanged since; counted at the L2, so "
+                                                           "Infinity-Cache hits are included)")
+                            extra["traffic_whole_operation"] = {"GB_per_multiply_of_the_batch": gb, "MB_per_mult": round(gb * 1e3 / B, 2),
+                                                                "avg_TBps_over_the_step": extra["hbm_traffic_avg_TBps_over_the_step_recorded"],
+                                                                "source": "recorded (profiles/r05_pmc_fresh_multiply_traffic.json), not measured in this run"}
+                roof = make_roofline(table, n, B, l, k, d, b2b)
+                if extras:
+                    sync()
+                    ts = []
+                    for i in range(14):                      # one ciphertext pair at a time, as benchmarks/bgv_basic.cpp:158-164 times it
+                        sync()
+                        t0 = time.perf_counter()
+                        sess.multiply_single(True)
+                        sync()
+                        if i >= 2:
+                            ts.append((time.perf_counter() - t0) * 1e3)
+                    ts.sort()
+                    if not ckks:
+                        try:     # batched Encrypt / Decrypt in the C++ host (the reference times one ciphertext per call)
+                            extra["batched_encrypt_decrypt"] = sess.encrypt_decrypt_batch(min(B, 64), 3)
+                            if not extra["batched_encrypt_decrypt"]["all_elements_round_trip"]:
+                                raise SystemExit("bench: DecryptBatch(EncryptBatch(m)) != m")
+                        except SystemExit:
+                            raise
+                        except Exception as e:
+                            extra["batched_encrypt_decrypt"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
+                    extra["batch1_latency_ms"] = round(ts[len(ts) // 2], 4)
+                    extra["batch1_latency_ms_min"] = round(ts[0], 4)
                     try:
-                        small = name.startswith("bgv32003")     # (1 warm + 2 timed steps: a multiply takes milliseconds here)
-                        leg, so = levels_leg(hh, sp, bb, rr, local_rank, stream, sync, hx=hx,
-                                             **(dict(warm_steps=1, steps=2) if small else {}))
-                        so.close()
-                        del so
-                        extra["levels_" + name] = leg
-                        for kk in ("level1_mult_per_s", "level2_mult_per_s", "level2_over_level1", "hipMalloc_calls_in_timed_windows"):
-                            extra[f"{name}_{kk}"] = leg[kk]          # (flat copies: nested objects do not survive every reader)
+                        c12 = config1_2_leg(hx)
+                        extra.update(c12)
+                        c1, c2 = c12["config1_fft_bench"], c12["config2_doublecrt_add_mul"]["batch64"]
+                        extra.update({"config1_fft_forward_us_one_row": c1["forward_us_one_row"], "config1_fft_forward_GBps": c1["forward_GBps"],
+                                      "config1_fft_inverse_GBps": c1["inverse_GBps"], "config2_add_GBps": c2["add_GBps"],
+                                      "config2_mul_GBps": c2["mul_GBps"]})
                     except Exception as e:
-                        extra["levels_" + name] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
-                if ckks:
+                        extra["config1_fft_bench"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
                     try:
-                        extra["ckks_basic_ops"] = ckks_basic_ops(hx, hc, local_rank, stream, sync, args.bits, precision=args.precision)
-                    except SystemExit:
-                        raise
+                        extra["config5_bluestein"] = config5_leg(hx)
+                        extra["config5_bluestein_forward_ns_per_row"] = extra["config5_bluestein"]["forward"]["ns_per_row"]
+                        extra["config5_bluestein_inverse_ns_per_row"] = extra["config5_bluestein"]["inverse"]["ns_per_row"]
                     except Exception as e:
-                        extra["ckks_basic_ops"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
-                if not ckks:
-                    # the python mirror of the same host logic (helib_amd/ctxt.py + keys.py): secondary figure, the
-                    # reference's other benchmark lines, and the HIP-graph replay of one multiply
-                    try:
-                        cc = hc.ChainContext(32768, 65537, 1, bits=args.bits, c=3)
-                        pctx = hx.Context(cc.m, local_rank)
-                        for q in cc.primes:
-                            pctx.add_prime(q)
-                        pctx.set_stream(stream)
-                        prepared = real_inputs(hx, hc, cc, pctx, B, 7 + rank)
-                        dtp, _, _, nvp, enq = run_fresh(hx, hc, cc, pctx, B, steps4, 1, rng, sync, lambda: None, measure=True,
-                                                        prepared=prepared, mults_per_step=R)
-                        extra["python_mirror_mult_per_s"] = round(B * R * steps4 / dtp, 1)
-                        extra["python_mirror_host_enqueue_ms_per_mult_from_idle"] = round(enq * 1e3, 4)
-                        fa, fb, _, sk, msgs = prepared
-                        extra["bgv_basic_ops"] = bgv_basic_ops(hx, hc, cc, fa, fb, sk, msgs, sync)
-                        _, _, gms = batch1_latency(hx, hc, fa, fb, sync)
-                        extra["batch1_latency_hip_graph_ms"] = [round(v, 4) for v in gms] if isinstance(gms, tuple) else gms
-                    except SystemExit:
-                        raise
-                    except Exception as e:
-                        extra["python_mirror"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
-            if args.cpu_sample > 0 and world == 1 and not ckks:
-                cc = hc.ChainContext(32768, 65537, 1, bits=args.bits, c=3)
-                cpu = cpu_baseline_fresh(cc, max(1, args.cpu_sample // 2))
-                cpu["all_cores"] = cpu_baseline_all_cores(args.bits, max(1, args.cpu_sample // 4))
-                shape = dict(M=cc.m, L=l, K=k, digits=[[i - cc.ctxtPrimes[0] for i in dg] for dg in cc.digits])
-                cpu["fixed_level_value"] = cpu_baseline_fixed(shape, [cc.primes[i] for i in cc.ctxtPrimes + cc.specialPrimes],
-                                                              args.cpu_sample)["value"]
-            elif args.cpu_sample > 0 and world == 1:
-                shape = SHAPES["ckks65536"]
-                cpu = cpu_baseline_fixed(shape, gen_primes(shape), max(2, args.cpu_sample // 6))
+                        extra["config5_bluestein"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
+                    # the other workloads through the same C++ host, two levels each: the other scheme at its BASELINE shape,
+                    # and the reference's OWN benchmark parameters (benchmarks/bgv_basic.cpp:247 bits=6400,
+                    # benchmarks/ckks_basic.cpp:263 precision=1 bits=440)
+                    legs = {"bgv32768_bits950": (("bgv", 32768, 65537, 1, 950), 128, 8),
+                            "ckks65536_bits1400": (("ckks", 65536, -1, args.precision, 1400), 64, 8),
+                            "ckks65536_bits440_reference_params": (("ckks", 65536, -1, 1, 440), 64, 8),
+                            "bgv32768_bits6400_reference_params": (("bgv", 32768, 65537, 1, 6400), 16, 4),
+                            # the reference's general-m benchmark ring (benchmarks/bgv_basic.cpp:236 big_params): m = 32003 prime,
+                            # p = 2, bits = 5800 -- every transform a Bluestein convolution
+                            "bgv32003_bits5800_reference_params": (("bgv", 32003, 2, 1, 5800), 8, 2),
+                            # BASELINE configs[4]'s ring end to end (tests/GTestBootstrapping.cpp:113: m = 21845 = 5 * 17 * 257, p = 2):
+                            # every transform of the multiply is the Good-Thomas x Rader kernel (round 6; Bluestein under HX_NO_PFA)
+                            "bgv21845_bits950_config5_ring": (("bgv", 21845, 2, 1, 950), 32, 4)}
+                    mine = "ckks65536_bits%d" % args.bits if ckks else "bgv32768_bits%d" % args.bits
+                    for name, (sp, bb, rr) in legs.items():
+                        if name.startswith(mine):
+                            continue
+                        try:
+                            small = name.startswith("bgv32003")     # (1 warm + 2 timed steps: a multiply takes milliseconds here)
+                            leg, so = levels_leg(hh, sp, bb, rr, local_rank, stream, sync, hx=hx,
+                                                 **(dict(warm_steps=1, steps=2) if small else {}))
+                            so.close()
+                            del so
+                            extra["levels_" + name] = leg
+                            for kk in ("level1_mult_per_s", "level2_mult_per_s", "level2_over_level1", "hipMalloc_calls_in_timed_windows"):
+                                extra[f"{name}_{kk}"] = leg[kk]          # (flat copies: nested objects do not survive every reader)
+                        except Exception as e:
+                            extra["levels_" + name] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
+                    if ckks:
+                        try:
+                            extra["ckks_basic_ops"] = ckks_basic_ops(hx, hc, local_rank, stream, sync, args.bits, precision=args.precision)
+                        except SystemExit:
+                            raise
+                        except Exception as e:
+                            extra["ckks_basic_ops"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
+                    if not ckks:
+                        # the python mirror of the same host logic (helib_amd/ctxt.py + keys.py): secondary figure, the
+                        # reference's other benchmark lines, and the HIP-graph replay of one multiply
+                        try:
+                            cc = hc.ChainContext(32768, 65537, 1, bits=args.bits, c=3)
+                            pctx = hx.Context(cc.m, local_rank)
+                            for q in cc.primes:
+                                pctx.add_prime(q)
+                            pctx.set_stream(stream)
+                            prepared = real_inputs(hx, hc, cc, pctx, B, 7 + rank)
+                            dtp, _, _, nvp, enq = run_fresh(hx, hc, cc, pctx, B, steps4, 1, rng, sync, lambda: None, measure=True,
+                                                            prepared=prepared, mults_per_step=R)
+                            extra["python_mirror_mult_per_s"] = round(B * R * steps4 / dtp, 1)
+                            extra["python_mirror_host_enqueue_ms_per_mult_from_idle"] = round(enq * 1e3, 4)
+                            fa, fb, _, sk, msgs = prepared
+                            extra["bgv_basic_ops"] = bgv_basic_ops(hx, hc, cc, fa, fb, sk, msgs, sync)
+                            _, _, gms = batch1_latency(hx, hc, fa, fb, sync)
+                            extra["batch1_latency_hip_graph_ms"] = [round(v, 4) for v in gms] if isinstance(gms, tuple) else gms
+                        except SystemExit:
+                            raise
+                        except Exception as e:
+                            extra["python_mirror"] = f"unavailable: {type(e).__name__}: {str(e)[:160]}"
+                if args.cpu_sample > 0 and world == 1 and not ckks:
+                    cc = hc.ChainContext(32768, 65537, 1, bits=args.bits, c=3)
+                    cpu = cpu_baseline_fresh(cc, max(1, args.cpu_sample // 2))
+                    cpu["all_cores"] = cpu_baseline_all_cores(args.bits, max(1, args.cpu_sample // 4))
+                    shape = dict(M=cc.m, L=l, K=k, digits=[[i - cc.ctxtPrimes[0] for i in dg] for dg in cc.digits])
+                    cpu["fixed_level_value"] = cpu_baseline_fixed(shape, [cc.primes[i] for i in cc.ctxtPrimes + cc.specialPrimes],
+                                                                  args.cpu_sample)["value"]
+                elif args.cpu_sample > 0 and world == 1:
+                    shape = SHAPES["ckks65536"]
+                    cpu = cpu_baseline_fixed(shape, gen_primes(shape), max(2, args.cpu_sample // 6))
         sess.close()
     else:
         shape = SHAPES[args.workload]
@@ -1572,13 +1630,15 @@ def main():
         ctx.set_stream(stream)
         n = ctx.phim
         l, k, d = shape["L"], shape["K"], len(shape["digits"])
-        dt = run_fixed(hx, ctx, primes, shape, B, args.steps * R, args.warmup, rng, sync, group.barrier)
+        dt, outs = run_fixed(hx, ctx, primes, shape, B, args.steps * R, args.warmup, rng, sync, group.barrier)
         dt = group.max_over_ranks(dt)
+        if args.dump_outputs and rank == 0:
+            dump_outputs(args.dump_outputs, [o.download() for o in outs], outs[0].getIndexSet())
         workload = shape["name"] + f"; synthetic uniform rows; step = {R} multiplications of the {B}-pair batch"
         per_mult = algorithmic_bytes_fixed(n, l, k, d)
         extra = {"mults_per_step": R, "multiplications_per_step_all_ranks": pairs_all * R,
                  "timed_region_s": round(dt, 3)}
-        if rank == 0:
+        if rank == 0 and args.full:
             b2b = ntt_back_to_back(hx, ctx, primes, list(range(l)), list(range(l, l + k)), shape["digits"], B, rng, args.ntt_iters)
             by = b2b["bytes_per_launch"]
             ach = by / (b2b["forward_avg_launch_ms"] * 1e-3) / 1e9
@@ -1592,16 +1652,18 @@ def main():
         cfg = {"workload": workload, "batch_per_gpu": B, "pairs_all_ranks": pairs_all,
                "parallelism": (f"replica x{world}, batch-sharded under one key pair (broadcast once), no data-path collective"
                                + (" -- all ranks on ONE device (--one-device): functional run, not a scaling point" if args.one_device else "")),
-               "algorithmic_MB_per_mult": round(per_mult / 1e6, 2),
-               # (NOT a roofline of this engine: the bytes the REFERENCE's unfused sequence would move, at 8 TB/s -- the fused
-               # kernels move fewer, so `value` may exceed it; the engine's own bound is roofline.fused_hbm_roofline_...)
-               "unfused_reference_equivalent_hbm_bound_mult_per_s_per_gpu": round(HBM_PEAK_GBS * 1e9 / per_mult, 0),
-               "roofline_note": ("algorithmic_MB_per_mult counts the reference-equivalent unfused sequence with "
-                                 "per-multiply key rows (SURVEY 8d): a description of the reference's traffic, not a bound on "
-                                 "this engine.  roofline.fused_algorithmic_MB_per_mult is the compulsory traffic of the kernels "
-                                 "that actually ran (sum of their algorithmic bytes), roofline.value_over_fused_roofline the "
-                                 "whole-operation fraction of the 8 TB/s roofline, roofline.whole_operation_traffic the bytes the "
-                                 "counters saw; the per-kernel fractions are under `roofline` and `config.kernels_in_situ`")}
+               "algorithmic_MB_per_mult": round(per_mult / 1e6, 2)}
+        if args.full:
+            cfg.update({
+                # (NOT a roofline of this engine: the bytes the REFERENCE's unfused sequence would move, at 8 TB/s -- the fused
+                # kernels move fewer, so `value` may exceed it; the engine's own bound is roofline.fused_hbm_roofline_...)
+                "unfused_reference_equivalent_hbm_bound_mult_per_s_per_gpu": round(HBM_PEAK_GBS * 1e9 / per_mult, 0),
+                "roofline_note": ("algorithmic_MB_per_mult counts the reference-equivalent unfused sequence with "
+                                  "per-multiply key rows (SURVEY 8d): a description of the reference's traffic, not a bound on "
+                                  "this engine.  roofline.fused_algorithmic_MB_per_mult is the compulsory traffic of the kernels "
+                                  "that actually ran (sum of their algorithmic bytes), roofline.value_over_fused_roofline the "
+                                  "whole-operation fraction of the 8 TB/s roofline, roofline.whole_operation_traffic the bytes the "
+                                  "counters saw; the per-kernel fractions are under `roofline` and `config.kernels_in_situ`")})
         cfg.update(extra)
         if isinstance(roof, dict):
             # the whole operation next to its dominant kernel, at the top level of the line

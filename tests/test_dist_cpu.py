@@ -155,3 +155,30 @@ def test_launcher_watchdog_stops_the_other_ranks_when_one_dies():
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dry-launch", "--steps", "2"],
                          env=env, capture_output=True, text=True, timeout=240)
     assert out.returncode != 0 and "rank 0 failed first" in out.stderr
+
+
+def test_bench_dump_outputs_is_exact_bounded_and_seeded(tmp_path):
+    """bench.py --dump-outputs: a 64-bit residue word survives as its two 32-bit halves in float64, the files stay under
+    64 MB at the default line's shape (2 parts x 16 rows x 128 elements x N = 16384), and the sampled batch elements are
+    the same from run to run."""
+    import numpy as np
+    import bench
+    rng = np.random.default_rng(5)
+    q = (1 << 60) - 93
+    parts = [rng.integers(0, q, size=(16, 128, 16384), dtype=np.uint64) for _ in range(2)]
+    runs = []
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), parts, list(range(16)), lambda b: np.full(16384, float(b)))
+        files = sorted(os.listdir(d))
+        assert files == ["batch_elements.npy", "decrypted.npy", "part0_hi32.npy", "part0_lo32.npy", "part1_hi32.npy",
+                         "part1_lo32.npy", "result_primes.npy"]
+        assert sum(os.path.getsize(d / f) for f in files) <= 64e6
+        runs.append({f: np.load(d / f) for f in files})
+    a, b = runs
+    assert all(x.dtype == np.float64 and np.array_equal(x, b[f]) for f, x in a.items())
+    el = a["batch_elements.npy"].astype(np.int64)
+    assert len(el) > 1 and len(set(el.tolist())) == len(el)
+    for i in (0, 1):
+        w = (a[f"part{i}_hi32.npy"].astype(np.uint64) << np.uint64(32)) | a[f"part{i}_lo32.npy"].astype(np.uint64)
+        assert np.array_equal(w, parts[i][:, el].transpose(1, 0, 2))
+    assert np.array_equal(a["decrypted.npy"][:, 0], el.astype(np.float64))

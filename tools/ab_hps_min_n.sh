@@ -2,8 +2,8 @@ export TMPDIR=/tmp
 out=gpurun_out/r06_hpsmin; mkdir -p $out
 for round in 1 2; do
 for v in 9 8 5; do
-  HX_HPS_MIN_N=$v timeout 300 python bench.py --workload ckks65536 --steps 8 --warmup 3 --no-extras --cpu-sample 0 > $out/ckks_h${v}_$round.json 2> $out/ckks_h${v}_$round.err
-  HX_HPS_MIN_N=$v timeout 300 python bench.py --steps 8 --warmup 3 --no-extras --cpu-sample 0 > $out/bgv_h${v}_$round.json 2> $out/bgv_h${v}_$round.err
+  HX_HPS_MIN_N=$v timeout 300 python bench.py --workload ckks65536 --steps 8 --warmup 3 --full --no-extras --cpu-sample 0 > $out/ckks_h${v}_$round.json 2> $out/ckks_h${v}_$round.err
+  HX_HPS_MIN_N=$v timeout 300 python bench.py --steps 8 --warmup 3 --full --no-extras --cpu-sample 0 > $out/bgv_h${v}_$round.json 2> $out/bgv_h${v}_$round.err
 done; done
 python - <<'PY'
 import json,glob

@@ -10,7 +10,7 @@ run() { # name workload variant
   v=$3; envs=""
   [ "$v" != default ] && envs="HX_LIB=$R/helib_amd/lib/variants/$v/libhelib_amd.so HX_HOST_LIB=$R/helib_amd/lib/variants/$v/libhelib_amd_host.so"
   f=$out/ab_$1.json
-  env $envs timeout 300 python bench.py --steps 8 --warmup 3 --no-extras --cpu-sample 0 ${2:+--workload $2} > $f 2> ${f%.json}.err
+  env $envs timeout 300 python bench.py --steps 8 --warmup 3 --full --no-extras --cpu-sample 0 ${2:+--workload $2} > $f 2> ${f%.json}.err
   python - $f $1 <<'PY'
 import json,sys
 try:

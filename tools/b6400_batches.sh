@@ -1,7 +1,8 @@
-mkdir -p gpurun_out/r5_6400
+out=${OUT_DIR:-results}/r5_6400
+mkdir -p $out
 for b in 16 48 96; do
-  timeout 600 python bench.py --bits 6400 --batch $b --steps 4 --warmup 1 --mults-per-step 4 --no-extras --cpu-sample 0 --no-rccl-check > gpurun_out/r5_6400/b$b.json 2> gpurun_out/r5_6400/b$b.err
-  python - gpurun_out/r5_6400/b$b.json $b <<'PY'
+  timeout 600 python bench.py --bits 6400 --batch $b --steps 4 --warmup 1 --mults-per-step 4 --full --no-extras --cpu-sample 0 --no-rccl-check > $out/b$b.json 2> $out/b$b.err
+  python - $out/b$b.json $b <<'PY'
 import json,sys
 try:
     d=json.loads(open(sys.argv[1]).readline()); c=d['config']

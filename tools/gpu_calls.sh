@@ -7,7 +7,7 @@
 #   tests_fast       the suite without its oracle-heavy cases (the bits = 6400 and m = 32003 chains, whose CPU side takes
 #                    minutes: a -k expression that happens to include them cost 8 GPU-minutes once); ~1.5 min
 #   smoke            __graft_entry__.smoke()
-#   bench            the driver's command, full line  -> bench_full.json
+#   bench            the driver's command with --full -> bench_full.json
 #   bench_ckks       config 4 (--workload ckks65536)   -> bench_ckks.json
 #   bench_fixed      the fixed-level multiply          -> bench_fixed.json
 #   trace            rocprofv3 --kernel-trace over the driver's command -> bench_kernel_trace.txt + bench_traced.json
@@ -29,7 +29,7 @@ name=$1; shift
 out=gpurun_out/$name
 mkdir -p $out
 R=${GRAFT_REPO_ROOT:-$PWD}
-QUICK="--no-extras --cpu-sample 0"
+QUICK="--full --no-extras --cpu-sample 0"
 
 line() {  # one-line digest of a bench JSON
   python - "$1" "$2" <<'PY'
@@ -76,14 +76,14 @@ for st in "$@"; do
     smoke)
       timeout 300 python __graft_entry__.py --smoke > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -1 $out/smoke.log ;;
     bench)
-      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $out/bench_full.json 2> $out/bench_full.err; echo "bench rc=$?"
+      timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $out/bench_full.json 2> $out/bench_full.err; echo "bench rc=$?"
       line $out/bench_full.json bgv; tail -3 $out/bench_full.err ;;
     bench_ckks)
-      timeout 600 python bench.py --workload ckks65536 --steps 8 --warmup 3 > $out/bench_ckks.json 2> $out/bench_ckks.err; echo "bench ckks rc=$?"
+      timeout 600 python bench.py --workload ckks65536 --steps 8 --warmup 3 --full > $out/bench_ckks.json 2> $out/bench_ckks.err; echo "bench ckks rc=$?"
       line $out/bench_ckks.json ckks; tail -3 $out/bench_ckks.err ;;
     ranks2)
       # the N-rank path with the real engine on this 1-GPU box: two ranks on GPU 0, one key pair broadcast from rank 0
-      timeout 600 python bench.py --gpus 2 --one-device --batch 16 --steps 3 --warmup 1 --mults-per-step 8 --no-extras --cpu-sample 0 \
+      timeout 600 python bench.py --gpus 2 --one-device --batch 16 --steps 3 --warmup 1 --mults-per-step 8 $QUICK \
          > $out/bench_ranks2.json 2> $out/bench_ranks2.err; echo "ranks2 rc=$?"
       python - $out/bench_ranks2.json <<'PY'
 import json, sys
@@ -97,9 +97,9 @@ PY
     scatter)
       # the batch split as a service on this 1-GPU box: (a) one rank, source + worker session on the device;
       # (b) two ranks on GPU 0 over gloo: slices scattered, products gathered, rank 0 alone verifies
-      timeout 600 python bench.py --scatter --steps 4 --warmup 1 --mults-per-step 8 --no-extras --cpu-sample 0 \
+      timeout 600 python bench.py --scatter --steps 4 --warmup 1 --mults-per-step 8 $QUICK \
          > $out/bench_scatter1.json 2> $out/bench_scatter1.err; echo "scatter1 rc=$?"
-      timeout 900 python bench.py --gpus 2 --one-device --scatter --workload ckks65536 --batch 16 --steps 3 --warmup 1 --mults-per-step 8 --no-extras --cpu-sample 0 \
+      timeout 900 python bench.py --gpus 2 --one-device --scatter --workload ckks65536 --batch 16 --steps 3 --warmup 1 --mults-per-step 8 $QUICK \
          > $out/bench_scatter2.json 2> $out/bench_scatter2.err; echo "scatter2 rc=$?"
       python - $out/bench_scatter1.json $out/bench_scatter2.json <<'PY'
 import json, sys
@@ -113,7 +113,7 @@ PY
       tail -n 3 $out/bench_scatter1.err; tail -n 3 $out/bench_scatter2.err ;;
     bench6400)
       # the reference's own BGV parameter (benchmarks/bgv_basic.cpp:247): bits=6400 -> L=107, K=36, D=3
-      timeout 900 python bench.py --bits 6400 --batch 16 --steps 4 --warmup 1 --mults-per-step 4 --no-extras --cpu-sample 0 \
+      timeout 900 python bench.py --bits 6400 --batch 16 --steps 4 --warmup 1 --mults-per-step 4 $QUICK \
          > $out/bench_6400.json 2> $out/bench_6400.err; echo "bench6400 rc=$?"
       line $out/bench_6400.json bits6400; tail -3 $out/bench_6400.err ;;
     trace_ckks)

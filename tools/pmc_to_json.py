@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """tools/rocpd_pmc.py's summary of the three PMC passes (FETCH_SIZE, WRITE_SIZE, SQ_INSTS_VALU over
-`bench.py --steps 2 --warmup 1 --mults-per-step 4 --no-extras --cpu-sample 0`) -> the two JSON records bench.py and DESIGN.md
+`bench.py --steps 2 --warmup 1 --mults-per-step 4 --full --no-extras --cpu-sample 0`) -> the two JSON records bench.py and DESIGN.md
 cite: the HBM traffic of ONE fresh multiply of the batch (sum over its launches) and, per roofline kernel, traffic against
 algorithmic bytes.   usage: tools/pmc_to_json.py pmc_summary.txt ROUND > out.json"""
 import json
@@ -64,5 +64,5 @@ json.dump({"workload": f"BGV m=32768 bits=950 fresh multiplyBy, batch 128, measu
                    "(gfx950: FETCH_SIZE counts 128-byte requests as 64 bytes, /opt/skills/guides/MI355X_MICROARCH.md); "
                    "FETCH_SIZE is counted at the L2: a read served by the Infinity Cache counts, HBM does not see it",
            "source": f"rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE / SQ_INSTS_VALU, three separate passes over `bench.py --gpus 1 --steps 2 "
-                     f"--warmup 1 --mults-per-step 4 --no-extras --cpu-sample 0` (tools/gpu_calls.sh OUT pmc), summarised by tools/rocpd_pmc.py "
+                     f"--warmup 1 --mults-per-step 4 --full --no-extras --cpu-sample 0` (tools/gpu_calls.sh OUT pmc), summarised by tools/rocpd_pmc.py "
                      f"into profiles/r{int(rnd):02d}_pmc_bench_command.txt, this file by tools/pmc_to_json.py"}, sys.stdout, indent=1)
