@@ -58,6 +58,7 @@ SYMBOLS = [
     "hx_ctx_graph_begin", "hx_ctx_graph_end", "hx_graph_launch", "hx_graph_destroy",
     "hx_profile_begin", "hx_profile_end", "hx_ctx_arena_stats", "hx_ctx_reserve",
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
+    "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
 ]
 
 
@@ -145,6 +146,9 @@ def lib():
             "hx_mul_relin_norms": [vp, vp, vp, vp, vp, vp, vp, ip, vp, vp, vp],
             "hx_tensor_bring_to_set": [vp] * 8 + [ip, vp, ip, u64],
             "hx_tensor_bring_to_set_norms": [vp] * 8 + [ip, vp, ip, u64, vp],
+            "hx_ckks_encode": [vp, vp, ip, ip, C.c_double, vp, vp],
+            "hx_ckks_embed": [vp, vp, ip, vp],
+            "hx_ckks_decode": [vp, C.c_double, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -620,6 +624,37 @@ def embeddingLargestCoeff(context, f):
     f = np.ascontiguousarray(f, dtype=np.float64).reshape(-1, context.phim)
     out = np.zeros(f.shape[0], dtype=np.float64)
     _chk(lib().hx_embedding_norm(context.h, _p(f), f.shape[0], _p(out)))
+    return out
+
+
+def ckksEncode(context, slots, scaling, idx, coeffs=False):
+    """CKKS_embedInSlots (src/norms.cpp:574-615) of slots[B, nslots] (complex, nslots <= m/4) scaled by `scaling`,
+    rounded, on the device: a DoubleCRT over the prime indices `idx` in evaluation form (hx_ckks_encode).
+    coeffs=True also returns the int64 coefficients [B, phi(m)] (the zzX)."""
+    v = np.ascontiguousarray(np.atleast_2d(np.asarray(slots, dtype=np.complex128)))
+    B, ns = v.shape
+    out = DoubleCRT(context, list(idx), B, zero=False)
+    cf = np.zeros((B, context.phim), dtype=np.int64) if coeffs else None
+    _chk(lib().hx_ckks_encode(context.h, _p(v), B, ns, float(scaling), out.h, _p(cf) if coeffs else None))
+    return (out, cf) if coeffs else out
+
+
+def ckksEmbed(context, f):
+    """CKKS_canonicalEmbedding (src/norms.cpp:495-519) of real polynomials f[B, phi(m)] on the device ->
+    complex slots [B, m/4] (hx_ckks_embed)."""
+    f = np.ascontiguousarray(np.atleast_2d(np.asarray(f, dtype=np.float64)))
+    assert f.shape[1] == context.phim, f.shape
+    out = np.zeros((f.shape[0], context.phim // 2), dtype=np.complex128)
+    _chk(lib().hx_ckks_embed(context.h, _p(f), f.shape[0], _p(out)))
+    return out
+
+
+def ckksDecode(poly, ln_rat_factor):
+    """rawDecrypt's decode (src/EaCx.cpp:62-86): poly = sum_parts part*s^r in evaluation form ->
+    canonicalEmbedding(centred CRT value / ratFactor) as complex slots [B, m/4] (hx_ckks_decode)."""
+    ctx = poly.context
+    out = np.zeros((poly.batch, ctx.phim // 2), dtype=np.complex128)
+    _chk(lib().hx_ckks_decode(poly.h, float(ln_rat_factor), _p(out)))
     return out
 
 

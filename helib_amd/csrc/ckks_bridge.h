@@ -1,0 +1,27 @@
+// ckks_bridge.h -- what ckks_slots.hip needs of engine.hip's objects (hx_ctx / hx_poly stay private to
+// engine.hip; everything else the slot unit does goes through the C ABI, include/helib_amd.h)
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <mutex>
+
+#include "../../include/helib_amd.h"
+
+namespace hxi {
+struct CtxView {
+  std::recursive_mutex* mu;   // the context's lock (CTX_ENTER)
+  hipStream_t stream;
+  uint64_t m;
+  uint32_t phim;
+  bool capturing;             // a graph capture is open
+  void** state;               // the slot unit's per-context state ...
+  void (**state_free)(void*); // ... and how the context releases it
+};
+// sets the device and fills v; the caller then takes *v->mu
+int ctx_enter(hx_ctx* c, CtxView* v);
+int fail_msg(int code, const char* msg);   // sets hx_last_error, returns code
+hx_ctx* poly_ctx(const hx_poly* p);
+int poly_rows_write(hx_poly* p, uint64_t** d);
+const uint64_t* poly_rows_read(const hx_poly* p);
+}  // namespace hxi

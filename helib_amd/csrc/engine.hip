@@ -271,6 +271,9 @@ struct hx_ctx {
   int graphs_alive = 0;
   hipStream_t own_stream = nullptr;   // created by the first capture of a context that ran on the default stream
   std::vector<void*> graph_retired;
+  // CKKS slot encoding (ckks_slots.hip): its tables and buffers, released with the context
+  void* ckks = nullptr;
+  void (*ckks_free)(void*) = nullptr;
 };
 
 struct hx_poly {
@@ -576,6 +579,8 @@ static void ctx_free(hx_ctx* c)
 {
   hipSetDevice(c->device);
   hipDeviceSynchronize();
+  if (c->ckks_free)   // the CKKS slot unit's tables and buffers (ckks_slots.hip)
+    c->ckks_free(c->ckks);
   if (c->d_tw)
     hipFree(c->d_tw);
   for (auto& kv : c->plans) {
@@ -5108,3 +5113,36 @@ extern "C" int hx_intel_EltwiseMultModScalar(long* r, const long* a, long s, lon
   uint64_t sv = (uint64_t)s;
   return shim_unary(r, a, n, q, [sv](ShimEntry* e) { return hx_mul_scalar(e->a, &sv); });
 }
+
+// ------------------------------------------------------------------
+// bridge for the CKKS slot unit (ckks_slots.hip, ckks_bridge.h): the context's
+// stream, lock and state slot, and the rows of a poly -- the unit does everything else through the ABI
+// ------------------------------------------------------------------
+#include "ckks_bridge.h"
+namespace hxi {
+int fail_msg(int code, const char* msg) { return fail(code, "%s", msg); }
+int ctx_enter(hx_ctx* c, CtxView* v)
+{
+  if (!c)
+    return fail(HX_ERR_INVALID, "null context");
+  CHK(use(c));
+  v->mu = &c->mu;
+  v->stream = c->stream;
+  v->m = c->m;
+  v->phim = c->phim;
+  v->capturing = c->capturing;
+  v->state = &c->ckks;
+  v->state_free = &c->ckks_free;
+  return HX_OK;
+}
+hx_ctx* poly_ctx(const hx_poly* p) { return p ? p->ctx : nullptr; }
+// p's rows are all about to be overwritten: a shared slab is left to its other holders
+int poly_rows_write(hx_poly* p, uint64_t** d)
+{
+  const uint64_t* old;
+  CHK(poly_fresh(p, &old));
+  *d = p->d;
+  return HX_OK;
+}
+const uint64_t* poly_rows_read(const hx_poly* p) { return p->d; }
+}  // namespace hxi

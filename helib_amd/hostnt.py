@@ -238,6 +238,24 @@ class ZmStar:
             n *= d
         return n
 
+    def ith_rep(self, i):
+        """PAlgebra::ith_rep (src/PAlgebra.cpp:520-570): the i-th representative of Z_m^*/<p>, exponent vectors over
+        gens in lexicographic order (the last generator's exponent runs fastest) -- CKKS's slot order."""
+        if not 0 <= i < self.getNSlots():
+            raise ValueError("ZmStar.ith_rep: index out of range")
+        t, rest = 1 % self.m, i
+        for g, d in zip(reversed(self.gens), reversed(self.ords)):
+            t = t * pow(g, rest % d, self.m) % self.m
+            rest //= d
+        return t
+
+    def reps(self):
+        """[ith_rep(i) for every i], built once"""
+        T = getattr(self, "_T", None)
+        if T is None:
+            T = self._T = [self.ith_rep(i) for i in range(self.getNSlots())]
+        return T
+
     def genToPow(self, i, j):
         """g_i^j mod m; i == -1: the Frobenius p^j; negative j through the inverse"""
         if i == len(self.gens):

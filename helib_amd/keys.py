@@ -233,14 +233,72 @@ class PubKey:
                 e_bound *= self.getSKeyBound()
             error_bound += e_bound
         ef = int(math.ceil(error_bound * prec / (scaling * ptxtSize)))
-        coeffs = np.zeros(cc.phim, dtype=object)
-        for i, v in enumerate(ptxt):
-            coeffs[i] = int(v) * ef if ef > 1 else int(v)
+        if hasattr(ptxt, "getIndexSet"):    # already encoded (a DoubleCRT over the ctxt primes): ef * ptxt
+            enc = ptxt.copy()
+            if ef > 1:
+                enc.mulConstant(ef)
+        else:
+            coeffs = np.zeros(cc.phim, dtype=object)
+            for i, v in enumerate(ptxt):
+                coeffs[i] = int(v) * ef if ef > 1 else int(v)
+            enc = be.fromCoeffs(idx, coeffs)
         if ef > 1:
             scaling *= ef
-        parts[0] += be.fromCoeffs(idx, coeffs)
+        parts[0] += enc
         ct = self._newCtxt(parts[0], parts[1], error_bound, 1)
         # EncryptedArrayCx::roundedSize: the next power of two, so as not to leak the size
+        ct.ptxtMag = 1.0 if ptxtSize <= 1 else float(1 << (int(math.ceil(ptxtSize)) - 1).bit_length())
+        ct.lnRatFactor = math.log(scaling)
+        return ct
+
+    def CKKSencryptBatch(self, enc, ptxtSize=1.0, scaling=0.0):
+        """CKKSencrypt of every element of the batched DoubleCRT `enc` (already encoded over the ctxt primes, one
+        scaling for all) into one batched Ctxt.  The samples (r, e0, e1 per element) are drawn in the order B
+        consecutive CKKSencrypt calls would draw them; the batch takes ONE ef, from the largest element error bound,
+        so that its elements share one ratFactor -- element b then equals CKKSencrypt(enc[b]) whenever its own ef
+        is that one (always at B = 1)."""
+        cc, be = self.cc, self.be
+        if not cc.ckks:
+            raise RuntimeError("CKKSencrypt on a BGV context")
+        if ptxtSize <= 0:
+            ptxtSize = 1.0
+        prec = 1 << cc.r
+        if scaling <= 0:
+            scaling = float(prec) / ptxtSize
+        idx = list(cc.ctxtPrimes)
+        B = enc.batch
+        stdev = cc.stdev if cc.pow2 else cc.stdev * math.sqrt(cc.m)
+        rr, ee, bounds = [], [[], []], []
+        for _ in range(B):
+            r, r_bound = self.sampler.sampleSmallBounded()
+            rr.append(be._rows(idx, r))
+            error_bound = r_bound * self.pubEncrKeyNoise
+            for i in range(2):
+                e, e_bound = self.sampler.sampleGaussianBounded(stdev)
+                ee[i].append(be._rows(idx, e))
+                if i == 1:
+                    e_bound *= self.getSKeyBound()
+                error_bound += e_bound
+            bounds.append(error_bound)
+        error_bound = max(bounds)
+
+        def batched(rows):
+            return be.hx.DoubleCRT(be.gctx, idx, B, np.stack(rows, axis=1)).FFT()
+
+        R = batched(rr)
+        parts = []
+        for i in range(2):
+            c = R.copy()
+            c *= self.pubEncrKey[i]         # r * pk_i, the key broadcast over the batch
+            c += batched(ee[i])
+            parts.append(c)
+        ef = int(math.ceil(error_bound * prec / (scaling * ptxtSize)))
+        e0 = enc.copy()
+        if ef > 1:
+            e0.mulConstant(ef)
+            scaling *= ef
+        parts[0] += e0
+        ct = self._newCtxt(parts[0], parts[1], error_bound, 1)
         ct.ptxtMag = 1.0 if ptxtSize <= 1 else float(1 << (int(math.ceil(ptxtSize)) - 1).bit_length())
         ct.lnRatFactor = math.log(scaling)
         return ct

@@ -303,6 +303,29 @@ int hx_relinearize_norms(const hx_poly* t0, const hx_poly* t1, const hx_poly* t2
                          const int* dig_idx, const int* dig_off, int ndig, const int* sp_idx,
                          int nsp, hx_poly* out0, hx_poly* out1, double* norms);
 
+/* ---------------- CKKS slots: EncryptedArrayCx (src/EaCx.cpp) ----------------
+ * m a power of two with 16 <= m <= 2^17 (N = phi(m) = m/2 <= 2^16); a larger m is HX_ERR_UNSUPPORTED, an m that is
+ * not a power of two HX_ERR_INVALID ("CKKS scheme only supports m as a power of two.", src/PAlgebra.cpp:463-467).
+ * Slot vectors are complex doubles (interleaved re, im) in PAlgebra's slot order: slot s is the value at
+ * zeta^-T[m/4-1-s], zeta = exp(2 pi i/m), T[i] = 3^i mod m (ith_rep of Z_m^* / <-1>, src/PAlgebra.cpp:520-570).
+ * Double precision on the device; all three calls synchronise the context's stream. */
+/* CKKS_embedInSlots (src/norms.cpp:574-615) of `batch` vectors of nslots <= m/4 slots each ([batch][nslots]; missing
+ * slots are 0), scaled by `scaling`, rounded as std::round; `out` (batch elements, its own prime set) receives the
+ * coefficients' residues in evaluation form (the DoubleCRT of the zzX, replacing a host encode + upload + FFT);
+ * coeffs_out (optional, host, [batch][phi(m)]) the zzX itself.  A coefficient outside the range of a long:
+ * HX_ERR_INVALID "overflow in encoding" (out then holds no meaningful value). */
+int hx_ckks_encode(hx_ctx* ctx, const double* slots, int batch, int nslots, double scaling, hx_poly* out,
+                   int64_t* coeffs_out);
+/* CKKS_canonicalEmbedding (src/norms.cpp:495-519) of `batch` real polynomials of phi(m) coefficients (host
+ * [batch][phi(m)]) -> slots_out[batch][m/4] (host, complex). */
+int hx_ckks_embed(hx_ctx* ctx, const double* coeffs, int batch, double* slots_out);
+/* The decode of EncryptedArrayCx::rawDecrypt (src/EaCx.cpp:62-86 -> CKKS_decode): p = sum_parts part * s^r in
+ * evaluation form, as SecKey::Decrypt's inner product leaves it (at most 64 primes; p is unchanged) ->
+ * slots_out[batch][m/4] = canonicalEmbedding(centred CRT value / ratFactor), ratFactor = exp(ln_rat_factor).  The
+ * division is DecryptCKKS's (include/helib_amd_keys.hpp): Garner digits weighted by P_k / ratFactor, on the device;
+ * one download. */
+int hx_ckks_decode(const hx_poly* p, double ln_rat_factor, double* slots_out);
+
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
  * host pointers, synchronous, in-place allowed.  FFTFwd / FFTRev1 are what

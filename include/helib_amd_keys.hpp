@@ -93,6 +93,19 @@ public:
     }
     return power(base, j);
   }
+  // PAlgebra::ith_rep (src/PAlgebra.cpp:520-570): the i-th representative of Z_m^* / <p>, the exponent vectors over
+  // gens taken in lexicographic order (the last generator's exponent runs fastest); CKKS's slot order
+  long ith_rep(long i) const
+  {
+    if (i < 0 || i >= getNSlots())
+      throw InvalidArgument("ZmStar::ith_rep: index out of range");
+    long t = 1 % m, rest = i;
+    for (size_t k = gens.size(); k-- > 0;) {
+      t = mul(t, power(gens[k], rest % ords[k]));
+      rest /= ords[k];
+    }
+    return t;
+  }
 
 private:
   long mod(long a) const { return ((a % m) + m) % m; }
@@ -505,6 +518,43 @@ public:
     d.FFT();
     return d;
   }
+  void ckksChecks() const
+  {
+    if (!cc->ckks)
+      throw LogicError("CKKSencrypt on a BGV context");
+    if (!pubEncrKey0)
+      throw LogicError("no public encryption key");
+  }
+  // the tail both CKKS encryptions share: ef, ef*ptxt added to the part of 1, the bookkeeping
+  Ctxt ckksFinish(DoubleCRT (&&parts)[2], const DoubleCRT& ptxt, double error_bound, double ptxtSize, double scaling)
+  {
+    if (ptxtSize <= 0)
+      ptxtSize = 1.0;
+    const double prec = std::ldexp(1.0, (int)cc->r);
+    if (scaling <= 0)
+      scaling = prec / ptxtSize;
+    long ef = (long)std::ceil(error_bound * prec / (scaling * ptxtSize));
+    DoubleCRT pt = ptxt;
+    if (ef > 1) {
+      pt *= ef;
+      scaling *= (double)ef;
+    }
+    parts[0] += pt;
+    Ctxt ct = Ctxt::fresh(*cc, *dev, keys, std::move(parts[0]), std::move(parts[1]));
+    ct.ptxtSpace = 1;
+    ct.lnNoise = std::log(error_bound);
+    ct.lnRatFactor = std::log(scaling);
+    ct.ptxtMag = 1.0;
+    if (ptxtSize > 1) {  // EncryptedArrayCx::roundedSize
+      long v = (long)std::ceil(ptxtSize) - 1, bits = 0;
+      while (v) {
+        bits++;
+        v >>= 1;
+      }
+      ct.ptxtMag = std::ldexp(1.0, (int)bits);
+    }
+    return ct;
+  }
   // DoubleCRT::randomize: uniform residues (the evaluation rows of a uniform polynomial are uniform)
   // on the device (hx_randomize: the reference's rejection sampling over a ChaCha20 stream of the
   // sampler's key); `host` receives the rows when the caller needs them (key-switching `a` columns)
@@ -892,15 +942,14 @@ public:
   // (scaling * ptxtSize)); ratFactor = scaling * ef, ptxtMag = ptxtSize rounded up to a power of two
   Ctxt CKKSencrypt(const std::vector<long>& ptxt, double ptxtSize = 1.0, double scaling = 0.0)
   {
-    if (!cc->ckks)
-      throw LogicError("CKKSencrypt on a BGV context");
-    if (!pubEncrKey0)
-      throw LogicError("no public encryption key");
-    if (ptxtSize <= 0)
-      ptxtSize = 1.0;
-    const double prec = std::ldexp(1.0, (int)cc->r);
-    if (scaling <= 0)
-      scaling = prec / ptxtSize;
+    ckksChecks();
+    return CKKSencrypt(fromCoeffs(cc->ctxtPrimes, ptxt), ptxtSize, scaling);   // (no sample is drawn by fromCoeffs)
+  }
+  // The same for a plaintext already encoded over the ctxt primes (EncryptedArrayCx::encode into a DoubleCRT,
+  // include/helib_amd_ckks.hpp)
+  Ctxt CKKSencrypt(const DoubleCRT& ptxt, double ptxtSize = 1.0, double scaling = 0.0)
+  {
+    ckksChecks();
     const IndexSet& idx = cc->ctxtPrimes;
     DoubleCRT parts[2] = {*pubEncrKey0, *pubEncrKey1};
     double r_bound = 0;
@@ -914,27 +963,45 @@ public:
         e_bound *= skBound;
       error_bound += e_bound;
     }
-    long ef = (long)std::ceil(error_bound * prec / (scaling * ptxtSize));
-    DoubleCRT pt = fromCoeffs(idx, ptxt);
-    if (ef > 1) {
-      pt *= ef;
-      scaling *= (double)ef;
-    }
-    parts[0] += pt;
-    Ctxt ct = Ctxt::fresh(*cc, *dev, keys, std::move(parts[0]), std::move(parts[1]));
-    ct.ptxtSpace = 1;
-    ct.lnNoise = std::log(error_bound);
-    ct.lnRatFactor = std::log(scaling);
-    ct.ptxtMag = 1.0;
-    if (ptxtSize > 1) {  // EncryptedArrayCx::roundedSize
-      long v = (long)std::ceil(ptxtSize) - 1, bits = 0;
-      while (v) {
-        bits++;
-        v >>= 1;
+    return ckksFinish(std::move(parts), ptxt, error_bound, ptxtSize, scaling);
+  }
+  // B CKKS encryptions of the batched, already encoded `ptxt` (one scaling for all) as ONE batched ciphertext.  The
+  // samples (r, e0, e1 per element) are drawn in the order B consecutive CKKSencrypt calls would draw them, as
+  // EncryptBatch does; the batch takes ONE ef, from the largest element error bound, so that its elements share one
+  // ratFactor (element b equals CKKSencrypt of element b whenever its own ef is that one -- always at B = 1).
+  Ctxt CKKSencryptBatch(const DoubleCRT& ptxt, double ptxtSize = 1.0, double scaling = 0.0)
+  {
+    ckksChecks();
+    const IndexSet& idx = cc->ctxtPrimes;
+    const size_t n = (size_t)cc->phim;
+    const int B = ptxt.batch();
+    std::vector<long> r((size_t)B * n), e[2];
+    e[0].resize((size_t)B * n);
+    e[1].resize((size_t)B * n);
+    double error_bound = 0;
+    for (int b = 0; b < B; b++) {
+      double r_bound = 0;
+      const std::vector<long> rb = sampler.sampleSmallBounded(r_bound);
+      std::copy(rb.begin(), rb.end(), r.begin() + (size_t)b * n);
+      double eb = r_bound * pubEncrKeyNoise;
+      for (int i = 0; i < 2; i++) {
+        double e_bound = 0;
+        const std::vector<long> es = sampler.sampleGaussianBounded(sampler.errorStdev(), e_bound);
+        std::copy(es.begin(), es.end(), e[i].begin() + (size_t)b * n);
+        if (i == 1)
+          e_bound *= skBound;
+        eb += e_bound;
       }
-      ct.ptxtMag = std::ldexp(1.0, (int)bits);
+      error_bound = std::max(error_bound, eb);
     }
-    return ct;
+    DoubleCRT rr = fromCoeffsBatch(idx, r, B);
+    DoubleCRT parts[2] = {rr, rr};
+    const DoubleCRT* pk[2] = {pubEncrKey0.get(), pubEncrKey1.get()};
+    for (int i = 0; i < 2; i++) {
+      parts[i] *= *pk[i];   // (the key is one polynomial: broadcast over the batch)
+      parts[i] += fromCoeffsBatch(idx, e[i], B);
+    }
+    return ckksFinish(std::move(parts), ptxt, error_bound, ptxtSize, scaling);
   }
 
   // sum_parts part * s^r(X^t): what both decryptions start from (src/keys.cpp:1360-1381)
