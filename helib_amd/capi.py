@@ -59,6 +59,7 @@ SYMBOLS = [
     "hx_profile_begin", "hx_profile_end", "hx_ctx_arena_stats", "hx_ctx_reserve",
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
+    "hx_mul_add_many", "hx_poly_extract",
 ]
 
 
@@ -149,6 +150,8 @@ def lib():
             "hx_ckks_encode": [vp, vp, ip, ip, C.c_double, vp, vp],
             "hx_ckks_embed": [vp, vp, ip, vp],
             "hx_ckks_decode": [vp, C.c_double, vp],
+            "hx_mul_add_many": [vp, vp, vp, vp, vp, ip, ip],
+            "hx_poly_extract": [vp, vp, ip],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -655,6 +658,30 @@ def ckksDecode(poly, ln_rat_factor):
     ctx = poly.context
     out = np.zeros((poly.batch, ctx.phim // 2), dtype=np.complex128)
     _chk(lib().hx_ckks_decode(poly.h, float(ln_rat_factor), _p(out)))
+    return out
+
+
+def mulAddMany(out0, out1, consts, in0, in1, accumulate=True):
+    """out0 (+)= sum_t consts[t] * in0[t], out1 (+)= sum_t consts[t] * in1[t] in one pass (hx_mul_add_many): n x MulAdd
+    (src/matmul.cpp:391-408).  out1 / in1 = None for a one-part ciphertext."""
+    n = len(consts)
+    assert len(in0) == n and (in1 is None or len(in1) == n)
+
+    def arr(ps):
+        return (C.c_void_p * max(n, 1))(*[p.h for p in ps])
+    _chk(lib().hx_mul_add_many(out0.h, out1.h if out1 is not None else None, arr(consts), arr(in0),
+                               arr(in1) if in1 is not None else None, n, 1 if accumulate else 0))
+
+
+def splitBatch(poly):
+    """the batch elements of poly as batch-1 DoubleCRTs (hx_poly_extract)"""
+    if poly.batch == 1:
+        return [poly]
+    idx, out = poly.getIndexSet(), []
+    for b in range(poly.batch):
+        d = DoubleCRT(poly.context, idx, 1, zero=False)
+        _chk(lib().hx_poly_extract(d.h, poly.h, b))
+        out.append(d)
     return out
 
 

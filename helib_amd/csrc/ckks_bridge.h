@@ -1,5 +1,5 @@
-// ckks_bridge.h -- what ckks_slots.hip needs of engine.hip's objects (hx_ctx / hx_poly stay private to
-// engine.hip; everything else the slot unit does goes through the C ABI, include/helib_amd.h)
+// ckks_bridge.h -- what ckks_slots.hip and linalg.hip need of engine.hip's objects (hx_ctx / hx_poly stay private
+// to engine.hip; everything else those units do goes through the C ABI, include/helib_amd.h)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -17,11 +17,16 @@ struct CtxView {
   bool capturing;             // a graph capture is open
   void** state;               // the slot unit's per-context state ...
   void (**state_free)(void*); // ... and how the context releases it
+  void** linalg;              // the same pair for linalg.hip
+  void (**linalg_free)(void*);
+  const void* d_primes;       // the per-prime constants (hx::PrimeDev[], dev_common.h) on the device
 };
 // sets the device and fills v; the caller then takes *v->mu
 int ctx_enter(hx_ctx* c, CtxView* v);
 int fail_msg(int code, const char* msg);   // sets hx_last_error, returns code
 hx_ctx* poly_ctx(const hx_poly* p);
 int poly_rows_write(hx_poly* p, uint64_t** d);
+// p's rows are about to be read and rewritten in place: a shared slab is copied first
+int poly_rows_update(hx_poly* p, uint64_t** d);
 const uint64_t* poly_rows_read(const hx_poly* p);
 }  // namespace hxi

@@ -274,6 +274,9 @@ struct hx_ctx {
   // CKKS slot encoding (ckks_slots.hip): its tables and buffers, released with the context
   void* ckks = nullptr;
   void (*ckks_free)(void*) = nullptr;
+  // the fused multiply-add (linalg.hip): its pointer tables
+  void* linalg = nullptr;
+  void (*linalg_free)(void*) = nullptr;
 };
 
 struct hx_poly {
@@ -581,6 +584,8 @@ static void ctx_free(hx_ctx* c)
   hipDeviceSynchronize();
   if (c->ckks_free)   // the CKKS slot unit's tables and buffers (ckks_slots.hip)
     c->ckks_free(c->ckks);
+  if (c->linalg_free)   // linalg.hip's pointer tables
+    c->linalg_free(c->linalg);
   if (c->d_tw)
     hipFree(c->d_tw);
   for (auto& kv : c->plans) {
@@ -5115,8 +5120,8 @@ extern "C" int hx_intel_EltwiseMultModScalar(long* r, const long* a, long s, lon
 }
 
 // ------------------------------------------------------------------
-// bridge for the CKKS slot unit (ckks_slots.hip, ckks_bridge.h): the context's
-// stream, lock and state slot, and the rows of a poly -- the unit does everything else through the ABI
+// bridge for the CKKS slot unit and the fused multiply-add (ckks_slots.hip, linalg.hip; ckks_bridge.h): the context's
+// stream, lock and state slots, and the rows of a poly -- the units do everything else through the ABI
 // ------------------------------------------------------------------
 #include "ckks_bridge.h"
 namespace hxi {
@@ -5133,6 +5138,9 @@ int ctx_enter(hx_ctx* c, CtxView* v)
   v->capturing = c->capturing;
   v->state = &c->ckks;
   v->state_free = &c->ckks_free;
+  v->linalg = &c->linalg;
+  v->linalg_free = &c->linalg_free;
+  v->d_primes = c->d_primes;
   return HX_OK;
 }
 hx_ctx* poly_ctx(const hx_poly* p) { return p ? p->ctx : nullptr; }
@@ -5141,6 +5149,12 @@ int poly_rows_write(hx_poly* p, uint64_t** d)
 {
   const uint64_t* old;
   CHK(poly_fresh(p, &old));
+  *d = p->d;
+  return HX_OK;
+}
+int poly_rows_update(hx_poly* p, uint64_t** d)
+{
+  OWN(p);
   *d = p->d;
   return HX_OK;
 }

@@ -1,0 +1,382 @@
+// linalg.hip -- C ABI of the fused multiply-add of the matrix product (include/helib_amd.h: hx_mul_add_many):
+//   out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]
+// the inner loop of MatMul1DExec::mul, n x MulAdd (src/matmul.cpp:391-408: tmp = b; tmp *= a; x += tmp, the product
+// being DoubleCRT::Mul with matchIndexSets = false), in one pass over the data.  The unit reaches the context only
+// through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+#include <vector>
+
+#include "../../include/helib_amd.h"
+#include "ckks_bridge.h"
+#include "dev_common.h"
+#include "prof.h"
+
+namespace hx {
+
+// Products of canonical residues are accumulated unreduced in 128 bits.  With q <= QMAX = 2^60 - 1 (hx_ctx_add_prime
+// admits primes below 2^60) the accumulator starts from a residue (the old output word, or the value the previous
+// reduction left) and takes MAD_CHUNK products:
+//   (q - 1) + MAD_CHUNK (q - 1)^2 <= (2^60 - 2) + 256 (2^60 - 2)^2 < 2^128,
+// so one reduction per MAD_CHUNK = 256 terms, and one at the end, is enough.
+constexpr int MAD_CHUNK = 256;
+constexpr u128 MAD_QMAX = ((u128)1 << 60) - 1;
+static_assert((~(u128)0 - (MAD_QMAX - 1)) / ((MAD_QMAX - 1) * (MAD_QMAX - 1)) >= (u128)MAD_CHUNK,
+              "MAD_CHUNK products of residues and one residue must fit 128 bits");
+
+struct MadRows {
+  uint16_t p[MAX_ROWS];   // prime index of output row r
+};
+
+// x mod q for any 128-bit x: x = hi 2^64 + lo = (hi mod q)(2^64 mod q) + (lo mod q) (mod q), a value below
+// q^2 + q < 8 q^2, which is red128_wide's domain.  2^64 mod q = 2^64 - mu64 q (mu64 = floor(2^64 / q)), the low word
+// of -mu64 q.
+__device__ __forceinline__ uint64_t mad_reduce(u128 x, uint64_t q, uint64_t mu, uint64_t mu64, uint32_t k)
+{
+  const uint64_t r64 = 0 - mu64 * q;
+  const u128 y = (u128)red64((uint64_t)(x >> 64), q, mu64) * r64 + red64((uint64_t)x, q, mu64);
+  return red128_wide(y, q, mu, k);
+}
+
+// Table (device, uint64 words): [0, n) the bases of in0[t]; [n, 2n) of in1[t]; then per output row r and term t the
+// base of the matching row of c[t], bit 0 set when c[t] has one row per batch element (bases are 16-byte aligned).
+// It is read through the constant address space: the entries are wave-uniform, so they are scalar loads.
+//
+// One thread owns two adjacent coefficients of one prime row for BP batch elements.  Per term it loads the two
+// constant words once and uses them for all BP elements, loads PARTS * BP operand vectors (16 bytes each,
+// non-temporal: every operand word is read once) and multiplies into 128-bit accumulators; it stores PARTS * BP
+// vectors at the end.  No LDS: nothing is shared between threads.
+template <int PARTS, int BP>
+__global__ void __launch_bounds__(256)
+mul_add_many_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, ro_u64 tab, int n, int batch, uint32_t N,
+                    int accumulate, MadRows map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t k = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  u128 a0[BP][2], a1[BP][2];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    a0[b][0] = a0[b][1] = a1[b][0] = a1[b][1] = 0;
+    if (accumulate) {
+      const ulonglong2 v = ld_stream2(out0 + row_off + boff[b]);
+      a0[b][0] = v.x;
+      a0[b][1] = v.y;
+      if (PARTS == 2) {
+        const ulonglong2 w = ld_stream2(out1 + row_off + boff[b]);
+        a1[b][0] = w.x;
+        a1[b][1] = w.y;
+      }
+    }
+  }
+  ro_u64 ctab = tab + 2 * (size_t)n + (size_t)row * n;
+  for (int t0 = 0; t0 < n; t0 += MAD_CHUNK) {
+    const int t1 = t0 + MAD_CHUNK < n ? t0 + MAD_CHUNK : n;
+    for (int t = t0; t < t1; t++) {
+      const uint64_t ce = ctab[t];
+      const uint64_t* cp = reinterpret_cast<const uint64_t*>(ce & ~(uint64_t)1);
+      const bool per_elem = ce & 1;
+      const uint64_t* p0 = reinterpret_cast<const uint64_t*>(tab[t]) + row_off;
+      const uint64_t* p1 = PARTS == 2 ? reinterpret_cast<const uint64_t*>(tab[n + t]) + row_off : nullptr;
+      ulonglong2 c = *reinterpret_cast<const ulonglong2*>(cp + (per_elem ? boff[0] : 2 * (size_t)i));
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        if (b > 0 && per_elem)
+          c = *reinterpret_cast<const ulonglong2*>(cp + boff[b]);
+        const ulonglong2 x = ld_stream2(p0 + boff[b]);
+        a0[b][0] += (u128)c.x * x.x;
+        a0[b][1] += (u128)c.y * x.y;
+        if (PARTS == 2) {
+          const ulonglong2 y = ld_stream2(p1 + boff[b]);
+          a1[b][0] += (u128)c.x * y.x;
+          a1[b][1] += (u128)c.y * y.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      a0[b][0] = mad_reduce(a0[b][0], q, mu, mu64, k);
+      a0[b][1] = mad_reduce(a0[b][1], q, mu, mu64, k);
+      if (PARTS == 2) {
+        a1[b][0] = mad_reduce(a1[b][0], q, mu, mu64, k);
+        a1[b][1] = mad_reduce(a1[b][1], q, mu, mu64, k);
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    st_stream2(out0 + row_off + boff[b], make_ulonglong2((uint64_t)a0[b][0], (uint64_t)a0[b][1]));
+    if (PARTS == 2)
+      st_stream2(out1 + row_off + boff[b], make_ulonglong2((uint64_t)a1[b][0], (uint64_t)a1[b][1]));
+  }
+}
+
+}  // namespace hx
+
+namespace {
+
+constexpr int RING = 4;   // calls whose table copy may still be in flight
+
+// per-context state: pinned staging buffers for the pointer table (one per call in flight) and its device copy
+struct LinState {
+  uint64_t* h_tab[RING] = {nullptr, nullptr, nullptr, nullptr};
+  size_t h_cap[RING] = {0, 0, 0, 0};
+  hipEvent_t copied[RING] = {nullptr, nullptr, nullptr, nullptr};
+  bool pending[RING] = {false, false, false, false};
+  int next = 0;
+  uint64_t* d_tab = nullptr;
+  size_t d_cap = 0;
+};
+void state_free(void* p)
+{
+  LinState* s = static_cast<LinState*>(p);
+  if (!s)
+    return;
+  for (int i = 0; i < RING; i++) {
+    if (s->h_tab[i])
+      hipHostFree(s->h_tab[i]);
+    if (s->copied[i])
+      hipEventDestroy(s->copied[i]);
+  }
+  hipFree(s->d_tab);
+  delete s;
+}
+
+int err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int err(int code, const char* fmt, ...)
+{
+  char b[400];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  return hxi::fail_msg(code, b);
+}
+#define CK(expr)                                                                                               \
+  do {                                                                                                         \
+    hipError_t _e = (expr);                                                                                    \
+    if (_e != hipSuccess) {                                                                                    \
+      (void)hipGetLastError();                                                                                 \
+      return err(HX_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
+    }                                                                                                          \
+  } while (0)
+#define RC(expr)        \
+  do {                  \
+    int _rc = (expr);   \
+    if (_rc != HX_OK)   \
+      return _rc;       \
+  } while (0)
+
+int shape_of(const hx_poly* p, int* batch, std::vector<int>* idx)
+{
+  int n = 0;
+  RC(hx_poly_shape(p, batch, &n, nullptr));
+  idx->assign(n > 0 ? n : 1, 0);
+  RC(hx_poly_primes(p, idx->data()));
+  idx->resize(n);
+  return HX_OK;
+}
+
+template <int PARTS>
+void launch(int bp, dim3 grid, hipStream_t st, uint64_t* o0, uint64_t* o1, const uint64_t* tab, int n, int batch,
+            uint32_t N, int accumulate, const hx::MadRows& map, const hx::PrimeDev* primes)
+{
+  if (bp == 1)
+    HX_LAUNCH((hx::mul_add_many_kernel<PARTS, 1>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, batch, N,
+              accumulate, map, primes);
+  else
+    HX_LAUNCH((hx::mul_add_many_kernel<PARTS, 4>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, batch, N,
+              accumulate, map, primes);
+}
+
+}  // namespace
+
+extern "C" int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* const* c, const hx_poly* const* in0,
+                               const hx_poly* const* in1, int n, int accumulate)
+{
+  if (!out0 || !c || !in0)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((out1 == nullptr) != (in1 == nullptr))
+    return err(HX_ERR_INVALID, "out1 and in1 go together (both null for a one-part ciphertext)");
+  if (n < 1)
+    return err(HX_ERR_INVALID, "hx_mul_add_many needs at least one term (n = %d)", n);
+  if (out0 == out1)
+    return err(HX_ERR_INVALID, "out0 and out1 are the same poly");
+  const int parts = out1 ? 2 : 1;
+  hx_ctx* ctx = hxi::poly_ctx(out0);
+  for (int t = 0; t < n; t++) {
+    if (!c[t] || !in0[t] || (in1 && !in1[t]))
+      return err(HX_ERR_INVALID, "null poly (term %d)", t);
+    if (hxi::poly_ctx(c[t]) != ctx || hxi::poly_ctx(in0[t]) != ctx || (in1 && hxi::poly_ctx(in1[t]) != ctx))
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects (term %d)", t);
+    if (in0[t] == out0 || in0[t] == out1 || (in1 && (in1[t] == out0 || in1[t] == out1)) || c[t] == out0 ||
+        c[t] == out1)
+      return err(HX_ERR_INVALID, "an output is also an input (term %d)", t);
+  }
+  if (out1 && hxi::poly_ctx(out1) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  if (v.capturing)
+    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_many uploads a pointer table and cannot be captured in a graph");
+  int batch = 0, b2 = 0;
+  std::vector<int> idx, other;
+  RC(shape_of(out0, &batch, &idx));
+  const int rows = (int)idx.size();
+  if (rows > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  if (out1) {
+    RC(shape_of(out1, &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "out0 and out1 differ in batch or prime set");
+  }
+  const uint32_t N = v.phim;
+  if (N < 2 || (N & 1))
+    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_many needs an even number of coefficients");
+  // host table: the shapes are checked while it is filled; device addresses go in after the outputs own their rows
+  std::vector<int> crow((size_t)rows * n), cper(n);
+  for (int t = 0; t < n; t++) {
+    RC(shape_of(in0[t], &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "in0[%d] differs from the output in batch or prime set", t);
+    if (in1) {
+      RC(shape_of(in1[t], &b2, &other));
+      if (b2 != batch || other != idx)
+        return err(HX_ERR_INVALID, "in1[%d] differs from the output in batch or prime set", t);
+    }
+    RC(shape_of(c[t], &b2, &other));
+    if (b2 != batch && b2 != 1)
+      return err(HX_ERR_INVALID, "c[%d]: batch %d is neither 1 nor %d", t, b2, batch);
+    cper[t] = b2 == batch && batch > 1;
+    for (int r = 0; r < rows; r++) {
+      int at = -1;
+      for (size_t j = 0; j < other.size(); j++)
+        if (other[j] == idx[r]) {
+          at = (int)j;
+          break;
+        }
+      if (at < 0)
+        return err(HX_ERR_INVALID, "c[%d] has no row for prime %d", t, idx[r]);
+      crow[(size_t)r * n + t] = at;
+    }
+  }
+  if (rows == 0)
+    return HX_OK;
+  if (!*v.linalg) {
+    *v.linalg = new LinState();
+    *v.linalg_free = state_free;
+  }
+  LinState* s = static_cast<LinState*>(*v.linalg);
+  const hipStream_t st = v.stream;
+  const size_t words = (size_t)n * (2 + rows), bytes = words * 8;
+  const int slot = s->next;
+  s->next = (slot + 1) % RING;
+  if (s->pending[slot]) {   // the copy that last read this staging buffer
+    CK(hipEventSynchronize(s->copied[slot]));
+    s->pending[slot] = false;
+  }
+  if (s->h_cap[slot] < bytes) {
+    if (s->h_tab[slot])
+      CK(hipHostFree(s->h_tab[slot]));
+    s->h_tab[slot] = nullptr;
+    s->h_cap[slot] = 0;
+    CK(hipHostMalloc((void**)&s->h_tab[slot], bytes, hipHostMallocDefault));
+    s->h_cap[slot] = bytes;
+  }
+  if (!s->copied[slot])
+    CK(hipEventCreateWithFlags(&s->copied[slot], hipEventDisableTiming));
+  if (s->d_cap < bytes) {
+    CK(hipStreamSynchronize(st));   // an earlier launch may still read the old table
+    hipFree(s->d_tab);
+    s->d_tab = nullptr;
+    s->d_cap = 0;
+    CK(hipMalloc((void**)&s->d_tab, bytes));
+    s->d_cap = bytes;
+  }
+  uint64_t *o0 = nullptr, *o1 = nullptr;
+  if (accumulate) {
+    RC(hxi::poly_rows_update(out0, &o0));
+    if (out1)
+      RC(hxi::poly_rows_update(out1, &o1));
+  } else {
+    RC(hxi::poly_rows_write(out0, &o0));
+    if (out1)
+      RC(hxi::poly_rows_write(out1, &o1));
+  }
+  uint64_t* h = s->h_tab[slot];
+  const size_t rw = (size_t)batch * N;
+  for (int t = 0; t < n; t++) {
+    h[t] = (uint64_t)(uintptr_t)hxi::poly_rows_read(in0[t]);
+    h[n + t] = in1 ? (uint64_t)(uintptr_t)hxi::poly_rows_read(in1[t]) : 0;
+    const uint64_t* cb = hxi::poly_rows_read(c[t]);
+    const size_t crw = cper[t] ? rw : (size_t)N;
+    for (int r = 0; r < rows; r++)
+      h[2 * (size_t)n + (size_t)r * n + t] =
+          (uint64_t)(uintptr_t)(cb + (size_t)crow[(size_t)r * n + t] * crw) | (uint64_t)cper[t];
+    if ((h[t] | h[n + t] | (uint64_t)(uintptr_t)cb) & 15)
+      return err(HX_ERR_INVALID, "term %d: rows are not 16-byte aligned", t);
+  }
+  if (((uint64_t)(uintptr_t)o0 | (uint64_t)(uintptr_t)o1) & 15)
+    return err(HX_ERR_INVALID, "output rows are not 16-byte aligned");
+  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
+  CK(hipEventRecord(s->copied[slot], st));
+  s->pending[slot] = true;
+  hx::MadRows map;
+  for (int r = 0; r < rows; r++)
+    map.p[r] = (uint16_t)idx[r];
+  const int bp = batch == 1 ? 1 : 4;
+  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  if (parts == 2)
+    launch<2>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
+  else
+    launch<1>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_poly_extract(hx_poly* dst, const hx_poly* src, int b)
+{
+  if (!dst || !src || dst == src)
+    return err(HX_ERR_INVALID, "null argument");
+  hx_ctx* ctx = hxi::poly_ctx(src);
+  if (hxi::poly_ctx(dst) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  int sb = 0, db = 0;
+  std::vector<int> sidx, didx;
+  RC(shape_of(src, &sb, &sidx));
+  RC(shape_of(dst, &db, &didx));
+  if (db != 1 || didx != sidx)
+    return err(HX_ERR_INVALID, "hx_poly_extract: dst must have batch 1 and the prime set of src");
+  if (b < 0 || b >= sb)
+    return err(HX_ERR_INVALID, "hx_poly_extract: batch element %d of %d", b, sb);
+  if (sidx.empty())
+    return HX_OK;
+  uint64_t* d = nullptr;
+  RC(hxi::poly_rows_write(dst, &d));
+  const uint64_t* sp = hxi::poly_rows_read(src);
+  const size_t rowb = (size_t)v.phim * 8;
+  CK(hipMemcpy2DAsync(d, rowb, sp + (size_t)b * v.phim, rowb * sb, rowb, sidx.size(), hipMemcpyDeviceToDevice,
+                      v.stream));
+  return HX_OK;
+}

@@ -1175,6 +1175,10 @@ class Ctxt:
             k = k * pow(amt, -1, m) % m
         return self
 
+    def complexConj(self):
+        """Ctxt::complexConj (src/Ctxt.cpp:2517-2523): smartAutomorph(-1)"""
+        return self.smartAutomorph(self.context.m - 1)
+
     @timing.timed
     def multiplyBy(self, other):
         self.multLowLvl(other, lazyTensor=True)
@@ -1372,6 +1376,9 @@ class BasicAutomorphPrecon:
         res.ksw_auto = c.ksw_auto
         res.ptxtSpace, res.intFactor = c.ptxtSpace, c.intFactor
         res.primeSet = c.primeSet | frozenset(sp)
+        if ctx.ckks:                   # src/matmul.cpp:139-143: the factor grows with the special primes
+            res.ptxtMag = c.ptxtMag
+            res.lnRatFactor = c.lnRatFactor + ctx.logOfProduct(sp)
         part0 = c.parts["1"].copy()
         part0.automorph(k)
         part0.addPrimesAndScale(sp)

@@ -326,6 +326,24 @@ int hx_ckks_embed(hx_ctx* ctx, const double* coeffs, int batch, double* slots_ou
  * one download. */
 int hx_ckks_decode(const hx_poly* p, double ln_rat_factor, double* slots_out);
 
+/* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
+/* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
+ * Replaces n x { tmp = b; tmp *= a; x += tmp }: MulAdd, src/matmul.cpp:391-408, and DoubleCRT::Mul with
+ * matchIndexSets = false (the inner loop of MatMul1DExec::mul, src/matmul.cpp:973-1110, 1220-1322).
+ * All operands are in evaluation form, words canonical in [0, q); the result equals, word for word, the
+ * hx_mul / hx_add sequence.  in0[t], in1[t] have the batch and the prime set (same order) of out0, out1; in1 and
+ * out1 may both be null (a one-part ciphertext).  c[t] has batch 1 (broadcast over the batch) or the outputs'
+ * batch, and may live on more primes than the outputs: its rows are matched by prime index, a missing prime is
+ * HX_ERR_INVALID.  accumulate = 0 overwrites the outputs.  n < 1, a null entry, mismatched shapes and an output that
+ * is also an input are HX_ERR_INVALID.  The call is asynchronous on the context's stream.  It uploads a table of
+ * operand pointers, so it cannot be recorded: under an open graph capture it returns HX_ERR_UNSUPPORTED before
+ * touching the device. */
+int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* const* c, const hx_poly* const* in0,
+                    const hx_poly* const* in1, int n, int accumulate);
+/* dst (batch 1, the prime set of src in the same order) <- batch element b of src: how a batch of encoded diagonals
+ * becomes the batch-1 constants above.  Asynchronous on the context's stream; works under a graph capture. */
+int hx_poly_extract(hx_poly* dst, const hx_poly* src, int b);
+
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
  * host pointers, synchronous, in-place allowed.  FFTFwd / FFTRev1 are what

@@ -3,11 +3,16 @@
 // hx_ckks_decode, include/helib_amd.h).  m a power of two, 16 <= m <= 2^17.  Slot order is PAlgebra's (ZmStar::ith_rep):
 // slot s holds the value at zeta^-T[m/4-1-s].  EncryptedArrayCx::decrypt -- rawDecrypt plus noise against the
 // Li-Micciancio attack (src/Ctxt.cpp:3051-3115) from NTL's PRG -- is not offered: only rawDecrypt.
+// Between slots: rotate / shift (src/EaCx.cpp:142-236), totalSums / runningSums (src/EncryptedArray.cpp:695-735),
+// extractRealPart / extractImPart (src/EaCx.cpp:419-447).  MatMul1DExec is offered in python only
+// (helib_amd/linalg.py); its device call hx_mul_add_many is plain C ABI.
 // (A header of its own: host_session.cpp and the other headers do not call the slot entry points.)
 #pragma once
+#include <algorithm>
 #include <cmath>
 #include <complex>
 #include <cstring>
+#include <memory>
 #include <vector>
 
 #include "helib_amd_keys.hpp"
@@ -140,9 +145,131 @@ public:
     return r;
   }
 
+  // ---- between slots ----
+  // defaultErr / defaultScale (include/helib/EncryptedArray.h:1315-1349): neither depends on the data
+  double defaultErr() const { return cc->noiseBoundForUniform(0.5, (double)cc->phim); }
+  double defaultScale(double err, long prec = -1) const
+  {
+    if (err < 1.0)
+      err = 1.0;
+    const long r = prec < 0 ? cc->r : prec;
+    int e;
+    std::frexp(1 / err, &e);
+    return std::ldexp(1.0, (int)(r - e + 1));
+  }
+  // EncryptedArrayCx::rotate = rotate1D(ctxt, 0, amt) (src/EaCx.cpp:142-164, 222-228): slot j moves to slot
+  // (j + amt) mod size
+  void rotate(Ctxt& ctxt, long amt) const
+  {
+    const long ord = size();
+    amt %= ord;
+    if (amt == 0)
+      return;
+    if (amt < 0)
+      amt += ord;
+    ctxt.smartAutomorph(zMStar().genToPow(0, amt));
+  }
+  // EncryptedArrayCx::shift = shift1D(ctxt, 0, k) (src/EaCx.cpp:166-221, 229-235): the encoded 0/1 mask first
+  // (encode(EncodedPtxt&, ...), :238-278: mag = Norm(mask) = 1, the default scale and error), then the automorphism
+  void shift(Ctxt& ctxt, long k) const
+  {
+    const long ord = size();
+    if (k <= -ord || k >= ord) {
+      ctxt.parts.clear();
+      return;
+    }
+    long amt = k % ord;
+    if (amt == 0)
+      return;
+    if (amt < 0)
+      amt += ord;
+    const long val = zMStar().genToPow(0, k < 0 ? amt - ord : amt);
+    std::vector<cx_double> mask((size_t)ord);
+    for (long j = 0; j < ord; j++)
+      mask[(size_t)j] = (j + k >= ord || j + k < 0) ? 0.0 : 1.0;
+    if (!ctxt.parts.empty()) {
+      const double err = defaultErr(), scale = defaultScale(err);
+      DoubleCRT enc = encodeBatch({mask}, scale, sorted(ctxt.primeSet));
+      ctxt.multByConstantCKKS(enc, 1.0, scale, err);
+    }
+    ctxt.smartAutomorph(val);
+  }
+  // totalSums (src/EncryptedArray.cpp:707-735)
+  void totalSums(Ctxt& ctxt) const
+  {
+    const long n = size();
+    if (n == 1)
+      return;
+    const Ctxt orig = ctxt;
+    long k = 0;
+    while ((n >> k) != 0)
+      k++;   // NTL::NumBits(n)
+    long e = 1;
+    for (long i = k - 2; i >= 0; i--) {
+      Ctxt tmp1 = ctxt;
+      rotate(tmp1, e);
+      ctxt += tmp1;
+      e = 2 * e;
+      if ((n >> i) & 1) {
+        Ctxt tmp2 = orig;
+        rotate(tmp2, e);
+        ctxt += tmp2;
+        e += 1;
+      }
+    }
+  }
+  // runningSums (src/EncryptedArray.cpp:695-705)
+  void runningSums(Ctxt& ctxt) const
+  {
+    const long n = size();
+    for (long shamt = 1; shamt < n; shamt *= 2) {
+      Ctxt tmp = ctxt;
+      shift(tmp, shamt);
+      ctxt += tmp;
+    }
+  }
+  // src/EaCx.cpp:419-425: (c + conj(c)) * 0.5
+  void extractRealPart(Ctxt& c) const
+  {
+    Ctxt tmp = c;
+    tmp.complexConj();
+    c += tmp;
+    c.multByConstantCKKS(0.5);
+  }
+  // src/EaCx.cpp:432-447: (conj(c) - c) * i * 0.5, i encoded as encodei does (:368-372: size 1)
+  void extractImPart(Ctxt& c) const
+  {
+    {
+      Ctxt tmp = c;
+      c.complexConj();
+      c -= tmp;
+    }
+    if (c.parts.empty())
+      return;
+    const std::vector<cx_double> vi((size_t)size(), cx_double(0.0, 1.0));
+    const double f = factor({vi}, 1.0);
+    DoubleCRT enc = encodeBatch({vi}, f, sorted(c.primeSet));
+    c.multByConstantCKKS(enc, 1.0, f, cc->encodeRoundingError());
+    c.multByConstantCKKS(0.5);
+  }
+
 private:
+  template <class S>
+  static IndexSet sorted(const S& s)
+  {
+    IndexSet v(s.begin(), s.end());
+    std::sort(v.begin(), v.end());
+    return v;
+  }
+  const ZmStar& zMStar() const
+  {
+    if (!zm)
+      zm = std::make_shared<ZmStar>(cc->m, -1);
+    return *zm;
+  }
   const ChainContext* cc;
   const Context* dev;
+  mutable std::shared_ptr<ZmStar> zm;
 };
 
 }  // namespace helib_amd

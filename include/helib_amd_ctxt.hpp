@@ -1226,6 +1226,8 @@ public:
     powers.emplace(1, *this);
     *this = powerRec(powers, e);
   }
+  // Ctxt::complexConj (src/Ctxt.cpp:2517-2523): smartAutomorph(-1)
+  void complexConj() { smartAutomorph(context->m - 1); }
   // Ctxt::frobeniusAutomorph (src/Ctxt.cpp:2526-2545): X -> X^(p^j) for BGV (j mod ord(p)); for CKKS
   // complex conjugation when j is odd
   void frobeniusAutomorph(long j)
