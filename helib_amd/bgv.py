@@ -1,0 +1,218 @@
+"""EncryptedArray (include/helib/EncryptedArray.h, src/EncryptedArray.cpp, src/PAlgebra.cpp) over the device for BGV
+with d = ord_m(p) = 1 and r = 1: the plaintext prime p = 1 mod m splits Phi_m into phi(m) linear factors, a slot is an
+integer mod p, and slot vectors -- numpy int64 arrays of shape [B, phi(m)] (B independent vectors: a batch) -- go into
+ciphertexts and come back out.
+
+  maps                F_0 = X - rho, rho the largest primitive m-th root of unity mod p (the smallest factor by
+                      poly_comp, src/PAlgebra.cpp:67-81); F_i = X - rho^(1/t_i mod m), t_i = zMStar.ith_rep(i)
+                      (:726-733); encode(a) = balanced(H), H of degree < phi(m) with H(rho^(1/t_i)) = a_i mod p
+                      (CRT_reconstruct, src/EncryptedArray.cpp:438-447); decode: slot i = H(rho^(1/t_i)) mod p
+  encode / decode     helib_amd.capi.bgvEncode / bgvEmbed (hx_bgv_encode / hx_bgv_embed): the engine's transform for
+                      the prime p between a scatter and a lift kernel
+  encrypt[_batch]     encode with the factor Q mod p of PubKey::Encrypt's balanced_MulMod (src/keys.cpp:358-488) folded
+                      in, then PubKey.EncryptBatch
+  decrypt[_batch]     the secret-key inner product, then hx_bgv_decode (toPoly + PolyRed on the device, the factor of
+                      SecKey::Decrypt, the transform mod p; one download)
+  rotate1D            every dimension is native at d = 1: one automorphism (src/EncryptedArray.cpp:65-97)
+  encodePtxt / multByConstant / addConstant   the EncodedPtxt interface (src/Ctxt.cpp:1952-2000, 2187-2224)
+
+Out of scope: d > 1 (slots in GF(p^d)) and p^r with r > 1 -- refused with HX_ERR_UNSUPPORTED; the linear-array rotate /
+shift, totalSums and the matrix product for BGV.  Nothing here imports oracle/."""
+import math
+
+import numpy as np
+
+from . import capi
+from . import ctxt as hc
+from . import hostnt
+from .ckks import LogicError, innerProduct
+
+
+class DeviceEncoder:
+    """slot vectors <-> polynomials on the device (hx_bgv_*).  An EncryptedArray can be given another object with these
+    members (tests drive the host control flow over a CPU backend that way)."""
+
+    def __init__(self, hxctx, p):
+        self.g = hxctx
+        self.table = capi.BgvSlots(hxctx, p)
+
+    def dims(self):
+        """(gens, ords) of Z_m^*'s hypercube, as the device tables order the slots"""
+        return self.table.gens, self.table.ords
+
+    def encode(self, v, mul, idx, coeffs=False):
+        return capi.bgvEncode(self.table, v, idx, mul, coeffs=coeffs)
+
+    def embed(self, coeffs):
+        return capi.bgvEmbed(self.table, coeffs)
+
+    def decode(self, acc, factor_inv):
+        return capi.bgvDecode(self.table, acc, factor_inv)
+
+    def norm(self, coeffs):
+        """embeddingLargestCoeff of every zzX [B, phi(m)]"""
+        return capi.embeddingLargestCoeff(self.g, np.asarray(coeffs, dtype=np.float64))
+
+
+class EncodedPtxt:
+    """EncodedPtxt_BGV (include/helib/EncodedPtxt.h): the zzX of the encoded slots with its plaintext space.  The
+    slots are kept as well: the reference expands the zzX to a ciphertext's primes when it is used
+    (FatEncodedPtxt::expand); here that is one more encode on the device."""
+
+    def __init__(self, ea, v, poly, ptxtSpace):
+        self.ea, self.v, self.poly, self.ptxtSpace = ea, v, poly, ptxtSpace
+
+
+class EncryptedArray:
+    """context: a BGV helib_amd.ctxt.ChainContext with p = 1 mod m and r = 1; hxctx: the capi.Context holding its
+    primes."""
+
+    def __init__(self, context, hxctx, encoder=None):
+        if getattr(context, "ckks", False):
+            raise LogicError("EncryptedArray: a CKKS context takes EncryptedArrayCx")
+        self.cc, self.g = context, hxctx
+        self.m, self.p = context.m, context.p
+        if getattr(context, "r", 1) != 1 or context.ptxtSpace != self.p:
+            raise capi.HxError(capi.HX_ERR_UNSUPPORTED,
+                               "BGV slots: plaintext space p^r with r > 1 (Hensel lifting) is not built")
+        if math.gcd(self.p, self.m) == 1 and self.p % self.m != 1 % self.m:
+            d, x = 1, self.p % self.m
+            while x != 1:
+                x, d = x * self.p % self.m, d + 1
+            raise capi.HxError(capi.HX_ERR_UNSUPPORTED, "d = ord_m(p) = %d for p = %d, m = %d: only d = 1 (p = 1 mod m, "
+                               "slots in Z_p) is built" % (d, self.p, self.m))
+        self.enc = encoder if encoder is not None else DeviceEncoder(hxctx, self.p)
+        dims = getattr(self.enc, "dims", None)
+        gens, ords = dims() if dims is not None else ((), ())
+        self.zMStar = hostnt.ZmStar(self.m, self.p, gens, ords)
+
+    # ---- geometry ----
+    def size(self):
+        return self.cc.phim
+
+    def dimension(self):
+        return self.zMStar.numOfGens()
+
+    def sizeOfDimension(self, i):
+        return self.zMStar.OrderOf(i)
+
+    def nativeDimension(self, i):
+        return self.zMStar.SameOrd(i)
+
+    def getP(self):
+        return self.p
+
+    def getDegree(self):
+        return 1
+
+    def coordinate(self, i, k):
+        """PAlgebra::coordinate: the exponent of generator i in slot k"""
+        for d in self.zMStar.ords[i + 1:]:
+            k //= d
+        return k % self.zMStar.ords[i]
+
+    def _slots(self, v):
+        a = np.asarray(v)
+        if a.dtype == object or a.dtype.kind not in "iu" or a.dtype == np.uint64:
+            a = np.array([int(x) % self.p for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
+        a = a.astype(np.int64)
+        a = a.reshape(1, -1) if a.ndim == 1 else a
+        if a.ndim != 2 or a.shape[1] > self.size():
+            raise capi.InvalidArgument(capi.HX_ERR_INVALID, "more values than slots")
+        return a
+
+    # ---- encode / decode ----
+    def encode(self, v, idx=None, coeffs=False, mul=1):
+        """-> DoubleCRT over idx (default: the ctxt primes) in evaluation form holding balanced(mul * H mod p);
+        coeffs=True: (DoubleCRT, int64 coefficients [B, phi(m)])"""
+        idx = list(self.cc.ctxtPrimes) if idx is None else list(idx)
+        return self.enc.encode(self._slots(v), mul, idx, coeffs=coeffs)
+
+    def encodeCoeffs(self, v, mul=1):
+        """the zzX alone, [B, phi(m)]"""
+        return self.enc.encode(self._slots(v), mul, [], coeffs=True)[1]
+
+    def decode(self, coeffs):
+        """EncryptedArray::decode of plaintext polynomials [B, phi(m)] -> int64 slots [B, phi(m)] in [0, p)"""
+        c = np.asarray(coeffs)
+        if c.dtype == object:
+            c = np.array([int(x) % self.p for x in c.reshape(-1)], dtype=np.int64).reshape(c.shape)
+        return self.enc.embed(np.atleast_2d(c.astype(np.int64)))
+
+    # ---- encryption ----
+    def encrypt(self, pk, v):
+        v = self._slots(v)
+        if v.shape[0] != 1:
+            raise capi.InvalidArgument(capi.HX_ERR_INVALID, "encrypt takes one vector: use encrypt_batch")
+        return self.encrypt_batch(pk, v)
+
+    def encrypt_batch(self, pk, vs):
+        """B vectors -> one batched Ctxt, element b being what PubKey.Encrypt gives for the encoding of vs[b] (the
+        samples in the order of B consecutive calls): the plaintext term balanced(ptxt * Q mod p) comes from the
+        encoder"""
+        if pk.ptxtSpace != self.p:
+            raise LogicError("EncryptedArray.encrypt: the key's plaintext space is not p")
+        idx = list(self.cc.ctxtPrimes)
+        return pk.EncryptBatch(self.encode(vs, idx, mul=self.cc.productOfPrimes(idx) % self.p))
+
+    def decrypt_batch(self, ct, sk):
+        """SecKey::Decrypt + decode for every element of a batched Ctxt -> int64 [B, phi(m)] in [0, p)"""
+        if ct.ptxtSpace != self.p:
+            raise LogicError("EncryptedArray.decrypt: the ciphertext's plaintext space is not p")
+        acc = innerProduct(sk, ct)
+        if acc is None:
+            return np.zeros((1, self.size()), dtype=np.int64)
+        factor = self.cc.productOfPrimes(sorted(ct.primeSet)) % self.p * ct.intFactor % self.p   # src/keys.cpp:1388-1405
+        return self.enc.decode(acc, pow(factor, -1, self.p))
+
+    def decrypt(self, ct, sk):
+        return self.decrypt_batch(ct, sk)[0]
+
+    # ---- the EncodedPtxt interface ----
+    def encodePtxt(self, v):
+        """EncryptedArray::encode(EncodedPtxt&, array): the zzX and the plaintext space"""
+        v = self._slots(v)
+        return EncodedPtxt(self, v, self.encodeCoeffs(v), self.p)
+
+    def _space(self, ct, eptxt):
+        if ct.ptxtSpace != eptxt.ptxtSpace:   # the reference reduces the plaintext space to the gcd: 1 for a prime
+            raise LogicError("EncryptedArray: the ciphertext's plaintext space is not p")
+
+    def multByConstant(self, ct, eptxt):
+        """Ctxt::multByConstant(const EncodedPtxt&) (src/Ctxt.cpp:1958-2000): the zzX expanded to the ciphertext's
+        primes, its size embeddingLargestCoeff(zzX) (FatEncodedPtxt_BGV)"""
+        if not ct.parts:
+            return ct
+        self._space(ct, eptxt)
+        size = float(np.max(self.enc.norm(eptxt.poly)))
+        return ct.multByConstant(self.enc.encode(eptxt.v, 1, sorted(ct.primeSet)), size)
+
+    def addConstant(self, ct, eptxt, neg=False):
+        """Ctxt::addConstant(const EncodedPtxt_BGV&, neg) (src/Ctxt.cpp:2187-2224): the constant is scaled by
+        f = intFactor * Q mod p in the plaintext space -- balanced(f * zzX mod p), here the encoder's `mul` -- and
+        the noise grows by that polynomial's embeddingLargestCoeff"""
+        self._space(ct, eptxt)
+        p = self.p
+        primes = sorted(ct.primeSet)
+        f = self.cc.productOfPrimes(primes) % p * ct.intFactor % p if p > 2 else 1
+        dcrt, poly = self.enc.encode(eptxt.v, f, primes, coeffs=True)
+        ct.lnNoise = hc.logaddexp(ct.lnNoise, hc._ln(float(np.max(self.enc.norm(poly)))))
+        if "1" not in ct.parts:
+            raise RuntimeError("Ctxt::addPart: no part pointing at 1")
+        if neg:
+            ct.parts["1"] -= dcrt
+        else:
+            ct.parts["1"] += dcrt
+        return ct
+
+    # ---- between slots ----
+    def rotate1D(self, ct, i, amt):
+        """EncryptedArray::rotate1D (src/EncryptedArray.cpp:65-97) on a native dimension: the slot whose coordinate
+        in dimension i is c moves to coordinate c + amt (mod the order)"""
+        if not 0 <= i < self.dimension():
+            raise capi.InvalidArgument(capi.HX_ERR_INVALID, "i must be between 0 and dimension()")
+        ord_ = self.sizeOfDimension(i)
+        amt %= ord_
+        if amt == 0:
+            return ct
+        return ct.smartAutomorph(self.zMStar.genToPow(i, amt))

@@ -60,6 +60,7 @@ SYMBOLS = [
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract",
+    "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
 ]
 
 
@@ -152,6 +153,11 @@ def lib():
             "hx_ckks_decode": [vp, C.c_double, vp],
             "hx_mul_add_many": [vp, vp, vp, vp, vp, ip, ip],
             "hx_poly_extract": [vp, vp, ip],
+            "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
+            "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
+            "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
+            "hx_bgv_decode": [vp, vp, u64, vp],
+            "hx_bgv_embed": [vp, vp, ip, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -658,6 +664,68 @@ def ckksDecode(poly, ln_rat_factor):
     ctx = poly.context
     out = np.zeros((poly.batch, ctx.phim // 2), dtype=np.complex128)
     _chk(lib().hx_ckks_decode(poly.h, float(ln_rat_factor), _p(out)))
+    return out
+
+
+class BgvSlots:
+    """The slot tables of one (Context, p) pair (hx_bgv_slots): EncryptedArray for d = ord_m(p) = 1.  HxError with
+    HX_ERR_UNSUPPORTED when p is not 1 mod m."""
+
+    def __init__(self, context, p):
+        self.context, self.p = context, int(p)
+        self.h = C.c_void_p()
+        _chk(lib().hx_bgv_slots_create(context.h, self.p, C.byref(self.h)))
+        rho, nd = C.c_uint64(), C.c_int()
+        g, o = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+        _chk(lib().hx_bgv_slots_info(self.h, None, C.byref(rho), C.byref(nd), g, o))
+        self.rho = int(rho.value)
+        self.gens, self.ords = [int(x) for x in g[:nd.value]], [int(x) for x in o[:nd.value]]
+
+    def close(self):
+        if self.h:
+            lib().hx_bgv_slots_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _slots_i64(v):
+    """int64 [B, n]; python integers of any size are reduced by the caller (EncryptedArray._slots)"""
+    return np.ascontiguousarray(np.atleast_2d(np.asarray(v, dtype=np.int64)))
+
+
+def bgvEncode(table, slots, idx, mul=1, coeffs=False):
+    """EncryptedArray::encode of slots[B, nslots] (integers, nslots <= phi(m)) on the device: a DoubleCRT over the
+    prime indices `idx` holding balanced(mul * H mod p) in evaluation form (hx_bgv_encode).  coeffs=True also returns
+    the int64 coefficients [B, phi(m)] (the zzX)."""
+    v = _slots_i64(slots)
+    B, ns = v.shape
+    ctx = table.context
+    out = DoubleCRT(ctx, list(idx), B, zero=False)
+    cf = np.zeros((B, ctx.phim), dtype=np.int64) if coeffs else None
+    _chk(lib().hx_bgv_encode(table.h, _p(v) if ns else None, B, ns, int(mul) % table.p, out.h, _p(cf) if coeffs else None))
+    return (out, cf) if coeffs else out
+
+
+def bgvDecode(table, poly, factor_inv=1):
+    """SecKey::Decrypt's tail for slots: poly = sum_parts part*s^r in evaluation form -> int64 [B, phi(m)] in [0, p)
+    (hx_bgv_decode)."""
+    out = np.zeros((poly.batch, table.context.phim), dtype=np.int64)
+    _chk(lib().hx_bgv_decode(table.h, poly.h, int(factor_inv) % table.p, _p(out)))
+    return out
+
+
+def bgvEmbed(table, f):
+    """EncryptedArray::decode of plaintext polynomials f[B, phi(m)] (integers) -> int64 slots [B, phi(m)] in [0, p)
+    (hx_bgv_embed)."""
+    f = _slots_i64(f)
+    assert f.shape[1] == table.context.phim, f.shape
+    out = np.zeros_like(f)
+    _chk(lib().hx_bgv_embed(table.h, _p(f), f.shape[0], _p(out)))
     return out
 
 

@@ -1,0 +1,460 @@
+// bgv_slots.hip -- C ABI of BGV slot encoding and decoding (include/helib_amd.h: hx_bgv_slots_create, hx_bgv_encode,
+// hx_bgv_decode, hx_bgv_embed): EncryptedArray over PAlgebraMod (src/EncryptedArray.cpp, src/PAlgebra.cpp:680-772) for
+// the case d = ord_m(p) = 1, r = 1, where a slot is an element of Z_p and everything PAlgebraMod computes has a closed
+// form:
+//   factors of Phi_m mod p   X - a, a the primitive m-th roots of unity mod p; factor 0 is the smallest by poly_comp
+//                            (constant coefficient p - a first): F_0 = X - rho, rho the LARGEST primitive m-th root
+//   factor i                 F_i = X - rho^(1/t_i mod m), t_i = ith_rep(i) of Z_m^* (/ <p> = {1})
+//   encode                   the H of degree < phi(m) with H(rho^(1/t_i)) = a_i mod p, balanced
+//   decode                   slot i = H(rho^(1/t_i)) mod p
+// The engine's transform for the prime p evaluates at zeta^j, j in Z_m^* ascending (zeta = the engine's root for a
+// power-of-two m, its square otherwise).  With rho = zeta^k, slot i sits at the row position of k / t_i mod m: one
+// permutation table and its inverse, built here on the host.  p lives in a side context of its own, so the chain
+// primes of the caller's context keep their numbering.  Kernels: bgv_slots.h.  The unit reaches the contexts only
+// through ckks_bridge.h and the C ABI.
+#include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#include "../../include/helib_amd.h"
+#include "bgv_slots.h"
+#include "ckks_bridge.h"
+#include "hostmath.h"
+#include "prof.h"
+
+struct hx_bgv_slots {
+  hx_ctx* ctx = nullptr;    // the caller's context (not owned)
+  hx_ctx* side = nullptr;   // holds p as its only prime
+  uint64_t m = 0, p = 0, rho = 0, k = 0;
+  uint32_t N = 0;
+  int device = 0;
+  std::vector<uint64_t> gens, ords;
+  uint32_t* d_row2slot = nullptr;
+  uint32_t* d_slot2row = nullptr;
+  void* buf[3] = {nullptr, nullptr, nullptr};   // grow-only scratch: slots / coefficients, the prime table, results
+  size_t cap[3] = {0, 0, 0};
+};
+
+namespace {
+
+int err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+int err(int code, const char* fmt, ...)
+{
+  char b[400];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  return hxi::fail_msg(code, b);
+}
+#define CK(expr)                                                                                               \
+  do {                                                                                                         \
+    hipError_t _e = (expr);                                                                                    \
+    if (_e != hipSuccess) {                                                                                    \
+      (void)hipGetLastError();                                                                                 \
+      return err(HX_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
+    }                                                                                                          \
+  } while (0)
+#define RC(expr)        \
+  do {                  \
+    int _rc = (expr);   \
+    if (_rc != HX_OK)   \
+      return _rc;       \
+  } while (0)
+
+// findGenerators (src/NumbTh.cpp:276-430) for the quotient of Z_m^* by the trivial group (p = 1 mod m): the next
+// generator is an element of largest order in the running quotient, the smallest one whose order there is its order
+// in Z_m^* if there is one.  m < 2^24, so products fit 64 bits.
+void conj_classes(std::vector<uint32_t>& cl, uint64_t g, uint64_t m)
+{
+  for (uint64_t i = 0; i < m; i++) {
+    if (cl[i] == 0)
+      continue;
+    if (cl[i] < i) {
+      cl[i] = cl[cl[i]];
+      continue;
+    }
+    for (uint64_t j = i * g % m; cl[j] != i; j = j * g % m)
+      cl[cl[j]] = (uint32_t)i;
+  }
+}
+void find_generators(uint64_t m, std::vector<uint64_t>& gens, std::vector<uint64_t>& ords)
+{
+  std::vector<uint32_t> cl(m), order(m);
+  for (uint64_t i = 0; i < m; i++)
+    cl[i] = hxh::gcd(i, m) == 1 ? (uint32_t)i : 0;
+  conj_classes(cl, 1, m);
+  for (;;) {
+    std::fill(order.begin(), order.end(), 0u);
+    if (m > 1)
+      order[1] = 1;
+    uint32_t largest = 1;
+    for (uint64_t i = 2; i < m; i++) {
+      if (cl[i] <= 1) {
+        order[i] = cl[i] == 1 ? 1 : 0;
+        continue;
+      }
+      if (cl[i] < i) {
+        order[i] = order[cl[i]];
+        continue;
+      }
+      uint32_t o = 2;
+      for (uint64_t j = i * i % m; cl[j] != 1; j = j * i % m)
+        o++;
+      order[i] = o;
+      largest = std::max(largest, o);
+    }
+    if (largest <= 1)
+      break;
+    uint64_t best = 0;
+    for (uint64_t i = 0; i < m; i++)
+      if (order[i] == largest && hxh::powmod(i, largest, m) == 1) {   // "quality 2"; the power of any other
+        best = i;                                                      // candidate would have to lie in <p> = {1}
+        break;
+      }
+    if (!best)
+      break;
+    gens.push_back(best);
+    ords.push_back(largest);
+    conj_classes(cl, best, m);
+  }
+}
+
+int ensure_buf(hx_bgv_slots* t, hipStream_t st, int slot, size_t bytes)
+{
+  if (t->cap[slot] >= bytes)
+    return HX_OK;
+  CK(hipStreamSynchronize(st));   // the old buffer may still be read by work in flight
+  hipFree(t->buf[slot]);
+  t->buf[slot] = nullptr;
+  t->cap[slot] = 0;
+  CK(hipMalloc(&t->buf[slot], bytes));
+  t->cap[slot] = bytes;
+  return HX_OK;
+}
+
+// the caller's context: view, lock, no open capture; the side context follows its stream
+struct Enter {
+  hxi::CtxView v{};
+  std::unique_lock<std::recursive_mutex> lk;
+  int open(const hx_bgv_slots* t, const char* what)
+  {
+    RC(hxi::ctx_enter(t->ctx, &v));
+    lk = std::unique_lock<std::recursive_mutex>(*v.mu);
+    if (v.capturing)
+      return err(HX_ERR_INVALID, "%s waits for the device and cannot be captured in a graph", what);
+    return hx_ctx_set_stream(t->side, (void*)v.stream);
+  }
+};
+struct DrainOnExit {   // every return waits for the stream: no copy still reads a host buffer, no kernel a temporary
+  hipStream_t st;
+  ~DrainOnExit() { (void)hipStreamSynchronize(st); }
+};
+struct Drop {
+  hx_poly* t;
+  ~Drop() { hx_poly_destroy(t); }
+};
+
+unsigned blocks_for(size_t items)
+{
+  const size_t b = (items + 255) / 256;
+  return (unsigned)std::min<size_t>(std::max<size_t>(b, 1), hx::BGV_MAX_BLOCKS);
+}
+bool aligned16(const void* a) { return ((uintptr_t)a & 15) == 0; }
+
+// a batch of rows modulo p on the side context (one row per element)
+int side_poly(const hx_bgv_slots* t, int batch, hx_poly** out)
+{
+  const int zero = 0;
+  return hx_poly_create_uninit(t->side, batch, &zero, 1, out);
+}
+
+// rows (side poly, evaluation form modulo p, row order) -> slot order -> host
+int gather_out(hx_bgv_slots* t, hipStream_t st, hx_poly* sp, size_t words, int64_t* slots_out)
+{
+  RC(ensure_buf(t, st, 2, words * 8));
+  HX_LAUNCH(hx::bgv_gather_kernel, dim3(blocks_for(words)), dim3(256), 0, st, hxi::poly_rows_read(sp), t->d_slot2row, t->N,
+            words, (int64_t*)t->buf[2]);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(slots_out, t->buf[2], words * 8, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  return HX_OK;
+}
+
+// dst = (src mod p) * f mod p over `words` signed words
+int launch_redmul(const hx_bgv_slots* t, hipStream_t st, const int64_t* src, size_t words, uint64_t f, uint64_t* dst)
+{
+  const uint64_t p = t->p, mu = (uint64_t)(((hxh::u128)1 << 64) / p), fs = hxh::shoup(f, p);
+  if (words % 2 == 0 && aligned16(src) && aligned16(dst))
+    HX_LAUNCH(hx::bgv_redmul_kernel<2>, dim3(blocks_for(words / 2)), dim3(256), 0, st, src, words, p, mu, f, fs, dst);
+  else
+    HX_LAUNCH(hx::bgv_redmul_kernel<1>, dim3(blocks_for(words)), dim3(256), 0, st, src, words, p, mu, f, fs, dst);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+}  // namespace
+
+extern "C" int hx_bgv_slots_destroy(hx_bgv_slots* t)
+{
+  if (!t)
+    return HX_OK;
+  (void)hipSetDevice(t->device);
+  if (t->side)
+    hx_ctx_destroy(t->side);   // waits for the device
+  hipFree(t->d_row2slot);
+  hipFree(t->d_slot2row);
+  for (void* b : t->buf)
+    hipFree(b);
+  delete t;
+  return HX_OK;
+}
+
+extern "C" int hx_bgv_slots_create(hx_ctx* ctx, uint64_t p, hx_bgv_slots** out)
+{
+  if (!ctx || !out)
+    return err(HX_ERR_INVALID, "null argument");
+  *out = nullptr;
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  if (v.capturing)
+    return err(HX_ERR_INVALID, "hx_bgv_slots_create while a graph is being captured");
+  const uint64_t m = v.m;
+  if (p < 2 || p >= (1ull << 60) || !hxh::is_prime(p))
+    return err(HX_ERR_INVALID, "the plaintext modulus p = %llu is not a prime below 2^60", (unsigned long long)p);
+  if (m % p == 0)
+    return err(HX_ERR_INVALID, "p = %llu divides m = %llu", (unsigned long long)p, (unsigned long long)m);
+  if (p % m != 1) {
+    uint64_t d = 1;
+    for (uint64_t x = p % m; x != 1; x = x * (p % m) % m)
+      d++;
+    return err(HX_ERR_UNSUPPORTED,
+               "d = ord_m(p) = %llu for p = %llu, m = %llu: only d = 1 (p = 1 mod m, slots in Z_p) is built",
+               (unsigned long long)d, (unsigned long long)p, (unsigned long long)m);
+  }
+  const bool pow2 = (m & (m - 1)) == 0;
+  if (pow2 ? (m < 16 || m > (1u << 17)) : (m < 3))
+    return err(HX_ERR_UNSUPPORTED, "BGV slots on the device need a power-of-two m in [16, 2^17] or another m >= 3 (m = %llu)",
+               (unsigned long long)m);
+  if (!pow2 && m % 2 == 0 && (p - 1) % (2 * m) != 0)
+    return err(HX_ERR_UNSUPPORTED, "even m = %llu that is not a power of two needs 2m | p - 1 (p = %llu)",
+               (unsigned long long)m, (unsigned long long)p);
+  hx_bgv_slots* t = new hx_bgv_slots();
+  struct Guard {
+    hx_bgv_slots* t;
+    ~Guard() { hx_bgv_slots_destroy(t); }
+  } guard{t};
+  t->ctx = ctx;
+  t->m = m;
+  t->p = p;
+  t->N = v.phim;
+  t->device = v.device;
+  RC(hx_ctx_create(&t->side, v.device, m));
+  RC(hx_ctx_set_stream(t->side, (void*)v.stream));
+  int pidx = -1;
+  uint64_t root = 0;
+  RC(hx_ctx_add_prime(t->side, p, 0, &pidx));
+  RC(hx_ctx_prime(t->side, pidx, nullptr, &root));
+  // the evaluation points of the engine's rows: zeta^j, j in Z_m^* ascending
+  const uint64_t zeta = pow2 ? root : hxh::mulmod(root, root, p);
+  std::vector<uint32_t> zidx(m, hx::BGV_NO_SLOT);
+  uint32_t n = 0;
+  uint64_t pw = 1;
+  for (uint64_t j = 0; j < m; j++, pw = hxh::mulmod(pw, zeta, p))
+    if (hxh::gcd(j, m) == 1) {
+      zidx[j] = n++;
+      if (pw > t->rho) {   // the largest primitive m-th root: the factor X - rho is the smallest by poly_comp
+        t->rho = pw;
+        t->k = j;
+      }
+    }
+  if (n != t->N || hxh::powmod(zeta, m, p) != 1)
+    return err(HX_ERR_DEVICE, "internal: the transform's root for p = %llu is not an m-th root of unity", (unsigned long long)p);
+  find_generators(m, t->gens, t->ords);
+  uint64_t nslots = 1;
+  for (uint64_t o : t->ords)
+    nslots *= o;
+  if (nslots != t->N)
+    return err(HX_ERR_DEVICE, "internal: the hypercube of Z_%llu^* has %llu points, not phi(m)", (unsigned long long)m,
+               (unsigned long long)nslots);
+  // slot i: exponent vector of i over gens, the last generator's exponent fastest (ith_rep)
+  std::vector<uint32_t> slot2row(t->N), row2slot(t->N, hx::BGV_NO_SLOT);
+  const size_t ng = t->gens.size();
+  std::vector<uint64_t> e(ng, 0), part(ng + 1, 1);   // part[g] = prod_(g' < g) gens^e
+  for (uint32_t i = 0; i < t->N; i++) {
+    const uint64_t ti = part[ng];
+    const uint64_t pos = hxh::mulmod(t->k, hxh::invmod(ti, m), m);
+    const uint32_t r = zidx[pos];
+    if (r == hx::BGV_NO_SLOT || row2slot[r] != hx::BGV_NO_SLOT)
+      return err(HX_ERR_DEVICE, "internal: slot table collision at m = %llu", (unsigned long long)m);
+    slot2row[i] = r;
+    row2slot[r] = i;
+    // next exponent vector
+    size_t g = ng;
+    while (g-- > 0) {
+      if (++e[g] < t->ords[g])
+        break;
+      e[g] = 0;
+    }
+    if (g == (size_t)-1)
+      break;
+    for (size_t h = g; h < ng; h++)
+      part[h + 1] = hxh::mulmod(part[h], hxh::powmod(t->gens[h], e[h], m), m);
+  }
+  CK(hipMalloc((void**)&t->d_row2slot, sizeof(uint32_t) * t->N));
+  CK(hipMalloc((void**)&t->d_slot2row, sizeof(uint32_t) * t->N));
+  CK(hipMemcpy(t->d_row2slot, row2slot.data(), sizeof(uint32_t) * t->N, hipMemcpyHostToDevice));
+  CK(hipMemcpy(t->d_slot2row, slot2row.data(), sizeof(uint32_t) * t->N, hipMemcpyHostToDevice));
+  guard.t = nullptr;
+  *out = t;
+  return HX_OK;
+}
+
+extern "C" int hx_bgv_slots_info(const hx_bgv_slots* t, uint64_t* p, uint64_t* rho, int* ndims, uint64_t* gens, uint64_t* ords)
+{
+  if (!t)
+    return err(HX_ERR_INVALID, "null argument");
+  if (p)
+    *p = t->p;
+  if (rho)
+    *rho = t->rho;
+  if (ndims)
+    *ndims = (int)t->gens.size();
+  for (size_t i = 0; i < t->gens.size() && i < 8; i++) {
+    if (gens)
+      gens[i] = t->gens[i];
+    if (ords)
+      ords[i] = t->ords[i];
+  }
+  return HX_OK;
+}
+
+extern "C" int hx_bgv_encode(const hx_bgv_slots* tc, const int64_t* slots, int batch, int nslots, uint64_t mul, hx_poly* out,
+                             int64_t* coeffs_out)
+{
+  if (!tc || !out || (nslots > 0 && !slots))
+    return err(HX_ERR_INVALID, "null argument");
+  hx_bgv_slots* t = const_cast<hx_bgv_slots*>(tc);   // (its scratch buffers grow; the caller's lock covers them)
+  if (hxi::poly_ctx(out) != t->ctx)
+    return err(HX_ERR_INVALID, "the output poly belongs to another context than the slot table");
+  const uint32_t N = t->N;
+  if (batch < 1 || nslots < 0 || (uint32_t)nslots > N)
+    return err(HX_ERR_INVALID, "bad batch / slot count (batch %d, %d slots of at most %u)", batch, nslots, N);
+  int pb = 0, nrows = 0;
+  RC(hx_poly_shape(out, &pb, &nrows, nullptr));
+  if (pb != batch)
+    return err(HX_ERR_INVALID, "output batch %d != %d", pb, batch);
+  if (nrows > hx::BGV_MAXPRIMES)
+    return err(HX_ERR_UNSUPPORTED, "more than %d primes", hx::BGV_MAXPRIMES);
+  Enter E;
+  RC(E.open(t, "hx_bgv_encode"));
+  std::vector<int> idx(nrows > 0 ? nrows : 1);
+  RC(hx_poly_primes(out, idx.data()));
+  std::vector<ulonglong2> qm(nrows > 0 ? nrows : 1);
+  for (int r = 0; r < nrows; r++) {
+    uint64_t q;
+    RC(hx_ctx_prime(t->ctx, idx[r], &q, nullptr));
+    qm[r] = make_ulonglong2(q, (uint64_t)(((hxh::u128)1 << 64) / q));
+  }
+  const uint64_t p = t->p;
+  mul %= p;
+  const hipStream_t st = E.v.stream;
+  hx_poly* sp = nullptr;
+  RC(side_poly(t, batch, &sp));
+  Drop drop{sp};
+  DrainOnExit drain{st};
+  const size_t words = (size_t)batch * N, vbytes = (size_t)batch * nslots * 8;
+  RC(ensure_buf(t, st, 0, std::max<size_t>(vbytes, 16)));
+  RC(ensure_buf(t, st, 1, sizeof(ulonglong2) * qm.size()));
+  if (coeffs_out)
+    RC(ensure_buf(t, st, 2, words * 8));
+  if (vbytes)
+    CK(hipMemcpyAsync(t->buf[0], slots, vbytes, hipMemcpyHostToDevice, st));
+  CK(hipMemcpyAsync(t->buf[1], qm.data(), sizeof(ulonglong2) * qm.size(), hipMemcpyHostToDevice, st));
+  uint64_t* h;
+  RC(hxi::poly_rows_write(sp, &h));
+  HX_LAUNCH(hx::bgv_scatter_kernel, dim3(blocks_for(words)), dim3(256), 0, st, (const int64_t*)t->buf[0], (uint32_t)nslots,
+            t->d_row2slot, N, words, p, (uint64_t)(((hxh::u128)1 << 64) / p), h);
+  CK(hipGetLastError());
+  RC(hx_ntt_inverse(sp));   // CRT_reconstruct: the H with the given values at the roots
+  const uint64_t* hc = hxi::poly_rows_read(sp);
+  uint64_t* rows = nullptr;
+  if (nrows > 0)
+    RC(hxi::poly_rows_write(out, &rows));
+  int64_t* d_coeffs = coeffs_out ? (int64_t*)t->buf[2] : nullptr;
+  if (nrows > 0 || d_coeffs) {
+    const uint64_t muls = hxh::shoup(mul, p);
+    if (words % 2 == 0 && aligned16(hc) && aligned16(rows) && aligned16(d_coeffs))
+      HX_LAUNCH(hx::bgv_lift_kernel<2>, dim3(blocks_for(words / 2)), dim3(256), 0, st, hc, words, p, mul, muls,
+                (const ulonglong2*)t->buf[1], nrows, rows, d_coeffs);
+    else
+      HX_LAUNCH(hx::bgv_lift_kernel<1>, dim3(blocks_for(words)), dim3(256), 0, st, hc, words, p, mul, muls,
+                (const ulonglong2*)t->buf[1], nrows, rows, d_coeffs);
+    CK(hipGetLastError());
+  }
+  if (nrows > 0)
+    RC(hx_ntt_forward(out));
+  if (coeffs_out)
+    CK(hipMemcpyAsync(coeffs_out, d_coeffs, words * 8, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  return HX_OK;
+}
+
+extern "C" int hx_bgv_embed(const hx_bgv_slots* tc, const int64_t* coeffs, int batch, int64_t* slots_out)
+{
+  if (!tc || !coeffs || !slots_out)
+    return err(HX_ERR_INVALID, "null argument");
+  if (batch < 1)
+    return err(HX_ERR_INVALID, "bad batch %d", batch);
+  hx_bgv_slots* t = const_cast<hx_bgv_slots*>(tc);
+  Enter E;
+  RC(E.open(t, "hx_bgv_embed"));
+  const hipStream_t st = E.v.stream;
+  hx_poly* sp = nullptr;
+  RC(side_poly(t, batch, &sp));
+  Drop drop{sp};
+  DrainOnExit drain{st};
+  const size_t words = (size_t)batch * t->N;
+  RC(ensure_buf(t, st, 0, words * 8));
+  CK(hipMemcpyAsync(t->buf[0], coeffs, words * 8, hipMemcpyHostToDevice, st));
+  uint64_t* h;
+  RC(hxi::poly_rows_write(sp, &h));
+  RC(launch_redmul(t, st, (const int64_t*)t->buf[0], words, 1, h));
+  RC(hx_ntt_forward(sp));
+  return gather_out(t, st, sp, words, slots_out);
+}
+
+extern "C" int hx_bgv_decode(const hx_bgv_slots* tc, const hx_poly* acc, uint64_t factor_inv, int64_t* slots_out)
+{
+  if (!tc || !acc || !slots_out)
+    return err(HX_ERR_INVALID, "null argument");
+  hx_bgv_slots* t = const_cast<hx_bgv_slots*>(tc);
+  if (hxi::poly_ctx(acc) != t->ctx)
+    return err(HX_ERR_INVALID, "the poly belongs to another context than the slot table");
+  Enter E;
+  RC(E.open(t, "hx_bgv_decode"));
+  int batch = 0, n = 0;
+  RC(hx_poly_shape(acc, &batch, &n, nullptr));
+  const size_t words = (size_t)batch * t->N;
+  if (n == 0) {   // the zero polynomial
+    memset(slots_out, 0, words * 8);
+    return HX_OK;
+  }
+  const hipStream_t st = E.v.stream;
+  hx_poly* sp = nullptr;
+  RC(side_poly(t, batch, &sp));
+  Drop drop{sp};
+  DrainOnExit drain{st};
+  const uint64_t* d_rem;
+  RC(hxi::poly_rem_device(acc, t->p, &d_rem));   // toPoly + PolyRed(p), exact, in [0, p)
+  uint64_t* h;
+  RC(hxi::poly_rows_write(sp, &h));
+  RC(launch_redmul(t, st, (const int64_t*)d_rem, words, factor_inv % t->p, h));
+  RC(hx_ntt_forward(sp));
+  return gather_out(t, st, sp, words, slots_out);
+}

@@ -1,4 +1,4 @@
-// ckks_bridge.h -- what ckks_slots.hip and linalg.hip need of engine.hip's objects (hx_ctx / hx_poly stay private
+// ckks_bridge.h -- what ckks_slots.hip, bgv_slots.hip and linalg.hip need of engine.hip's objects (hx_ctx / hx_poly stay private
 // to engine.hip; everything else those units do goes through the C ABI, include/helib_amd.h)
 #pragma once
 #include <hip/hip_runtime.h>
@@ -20,6 +20,7 @@ struct CtxView {
   void** linalg;              // the same pair for linalg.hip
   void (**linalg_free)(void*);
   const void* d_primes;       // the per-prime constants (hx::PrimeDev[], dev_common.h) on the device
+  int device;
 };
 // sets the device and fills v; the caller then takes *v->mu
 int ctx_enter(hx_ctx* c, CtxView* v);
@@ -29,4 +30,7 @@ int poly_rows_write(hx_poly* p, uint64_t** d);
 // p's rows are about to be read and rewritten in place: a shared slab is copied first
 int poly_rows_update(hx_poly* p, uint64_t** d);
 const uint64_t* poly_rows_read(const hx_poly* p);
+// hx_poly_rem's arithmetic (toPoly + PolyRed(t), exact) with the result kept on the device: *d_out = [batch][phi(m)]
+// words in [0, t) in the context's scratch, valid until the next call on that context (hold its lock); a has rows
+int poly_rem_device(const hx_poly* a, uint64_t t, const uint64_t** d_out);
 }  // namespace hxi

@@ -3506,21 +3506,13 @@ extern "C" int hx_add_primes(hx_poly* a, const int* add_idx, int nadd)
 // src/NumbTh.cpp:775-803): out[b][j] = (coefficient j of the centred polynomial) mod t in [0,t).
 // This is the tail of SecKey::Decrypt (src/keys.cpp:1383-1405) without big integers: inverse
 // transform of a copy, Garner mixed-radix digits, centring, residue modulo t -- exact.
-extern "C" int hx_poly_rem(const hx_poly* a, uint64_t t, uint64_t* out_host)
+// the arithmetic of hx_poly_rem with the result left on the device: *d_out = batch * phi(m) words in the
+// context's scratch, valid until the next call on the context (the caller holds the context's lock); a has rows
+static int poly_rem_dev(const hx_poly* a, uint64_t t, const uint64_t** d_out)
 {
-  if (!a || !out_host)
-    return fail(HX_ERR_INVALID, "null argument");
-  if (t < 2 || t >= (1ull << 60))
-    return fail(HX_ERR_INVALID, "modulus must be in [2, 2^60)");
   hx_ctx* c = a->ctx;
-  CTX_ENTER(c);
-  NO_CAPTURE(c, "hx_poly_rem");
   const int n = a->nrows();
   const size_t rw = a->row_words();
-  if (n == 0) {  // the zero polynomial
-    memset(out_host, 0, rw * 8);
-    return HX_OK;
-  }
   if (n > MAX_EXT_SRC)
     return fail(HX_ERR_UNSUPPORTED, "toPoly from more than %d primes on the device", MAX_EXT_SRC);
   CHK(ensure_scratch(c, 0, (size_t)(n + 1) * rw));
@@ -3538,7 +3530,27 @@ extern "C" int hx_poly_rem(const hx_poly* a, uint64_t t, uint64_t* out_host)
     args.src_row[k] = (uint16_t)k;
   args.dst_row[0] = (uint16_t)n;
   CHK(launch_extend(c, pl, args, rw));
-  HIPCHK(hipMemcpyAsync(out_host, c->scratch[0] + (size_t)n * rw, rw * 8, hipMemcpyDeviceToHost, c->stream));
+  *d_out = c->scratch[0] + (size_t)n * rw;
+  return HX_OK;
+}
+
+extern "C" int hx_poly_rem(const hx_poly* a, uint64_t t, uint64_t* out_host)
+{
+  if (!a || !out_host)
+    return fail(HX_ERR_INVALID, "null argument");
+  if (t < 2 || t >= (1ull << 60))
+    return fail(HX_ERR_INVALID, "modulus must be in [2, 2^60)");
+  hx_ctx* c = a->ctx;
+  CTX_ENTER(c);
+  NO_CAPTURE(c, "hx_poly_rem");
+  const size_t rw = a->row_words();
+  if (a->nrows() == 0) {  // the zero polynomial
+    memset(out_host, 0, rw * 8);
+    return HX_OK;
+  }
+  const uint64_t* d_rem;
+  CHK(poly_rem_dev(a, t, &d_rem));
+  HIPCHK(hipMemcpyAsync(out_host, d_rem, rw * 8, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
   return HX_OK;
 }
@@ -5120,7 +5132,7 @@ extern "C" int hx_intel_EltwiseMultModScalar(long* r, const long* a, long s, lon
 }
 
 // ------------------------------------------------------------------
-// bridge for the CKKS slot unit and the fused multiply-add (ckks_slots.hip, linalg.hip; ckks_bridge.h): the context's
+// bridge for the slot units and the fused multiply-add (ckks_slots.hip, bgv_slots.hip, linalg.hip; ckks_bridge.h): the context's
 // stream, lock and state slots, and the rows of a poly -- the units do everything else through the ABI
 // ------------------------------------------------------------------
 #include "ckks_bridge.h"
@@ -5141,6 +5153,7 @@ int ctx_enter(hx_ctx* c, CtxView* v)
   v->linalg = &c->linalg;
   v->linalg_free = &c->linalg_free;
   v->d_primes = c->d_primes;
+  v->device = c->device;
   return HX_OK;
 }
 hx_ctx* poly_ctx(const hx_poly* p) { return p ? p->ctx : nullptr; }
@@ -5159,4 +5172,11 @@ int poly_rows_update(hx_poly* p, uint64_t** d)
   return HX_OK;
 }
 const uint64_t* poly_rows_read(const hx_poly* p) { return p->d; }
+int poly_rem_device(const hx_poly* a, uint64_t t, const uint64_t** d_out)
+{
+  if (!a || !d_out || a->nrows() == 0 || t < 2 || t >= (1ull << 60))
+    return fail(HX_ERR_INVALID, "internal: bad argument to poly_rem_device");
+  CTX_ENTER(a->ctx);
+  return poly_rem_dev(a, t, d_out);
+}
 }  // namespace hxi

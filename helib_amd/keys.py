@@ -347,6 +347,54 @@ class PubKey:
         return self._newCtxt(parts[0], parts[1], noise, ptxtSpace)
 
 
+    def EncryptBatch(self, enc, ptxtSpace=0):
+        """PubKey::Encrypt of every element of the batched DoubleCRT `enc` into one batched Ctxt.  enc holds, over the
+        ctxt primes in evaluation form, the plaintext term ready-made: balanced_MulMod(ptxt, Q mod p, p) of every
+        element (what helib_amd.bgv.EncryptedArray.encode gives with mul = Q mod p).  The samples (r, e0, e1 per
+        element) are drawn in the order B consecutive Encrypt calls would draw them, and the noise bound is
+        Encrypt's, which does not depend on the data: element b equals Encrypt of the b-th polynomial word for
+        word."""
+        cc, be = self.cc, self.be
+        if cc.ckks:
+            raise RuntimeError("EncryptBatch on a CKKS context: use CKKSencryptBatch")
+        if self.pubEncrKey is None:
+            raise RuntimeError("no public encryption key")
+        ptxtSpace = ptxtSpace or self.ptxtSpace
+        if ptxtSpace != self.ptxtSpace:
+            ptxtSpace = math.gcd(ptxtSpace, self.ptxtSpace)
+            if ptxtSpace <= 1:
+                raise RuntimeError("Plaintext-space mismatch on encryption")
+        idx = list(cc.ctxtPrimes)
+        if sorted(enc.getIndexSet()) != sorted(idx):
+            raise RuntimeError("EncryptBatch: the encoded plaintext is not over the ctxt primes")
+        B = enc.batch
+        stdev = cc.stdev if cc.pow2 else cc.stdev * math.sqrt(cc.m)
+        rr, ee, noise = [], [[], []], 0.0
+        for _ in range(B):
+            r, r_bound = self.sampler.sampleSmallBounded()
+            rr.append(r)
+            noise = r_bound * self.pubEncrKeyNoise
+            for i in range(2):
+                e, e_bound = self.sampler.sampleGaussianBounded(stdev)
+                ee[i].append(e)
+                e_bound *= ptxtSpace
+                if i == 1:
+                    e_bound *= self.getSKeyBound()
+                noise += e_bound
+        R = be.fromCoeffsBatch(idx, rr)
+        parts = []
+        for i in range(2):
+            c = R.copy()
+            c *= self.pubEncrKey[i]         # r * pk_i, the key broadcast over the batch
+            E = be.fromCoeffsBatch(idx, ee[i])
+            E.mulConstant(ptxtSpace)
+            c += E
+            parts.append(c)
+        parts[0] += enc
+        noise += cc.noiseBoundForMod(ptxtSpace, cc.phim)
+        return self._newCtxt(parts[0], parts[1], noise, ptxtSpace)
+
+
 class SecKey(PubKey):
     def __init__(self, context, backend, seed=None):
         super().__init__(context, backend, seed)
@@ -623,6 +671,12 @@ class HxBackend:
         idx = list(idx)
         rows = self._rows(idx, coeffs)
         return self.hx.DoubleCRT(self.gctx, idx, 1, rows[:, None, :]).FFT()
+
+    def fromCoeffsBatch(self, idx, polys):
+        """B coefficient vectors -> one batched DoubleCRT (element b = fromCoeffs(idx, polys[b]))"""
+        idx = list(idx)
+        rows = np.stack([self._rows(idx, c) for c in polys], axis=1)
+        return self.hx.DoubleCRT(self.gctx, idx, len(polys), rows).FFT()
 
     def randomize(self, idx, rng):
         """DoubleCRT::randomize on the device: no host fill, no upload (hx_randomize; one fresh

@@ -326,6 +326,38 @@ int hx_ckks_embed(hx_ctx* ctx, const double* coeffs, int batch, double* slots_ou
  * one download. */
 int hx_ckks_decode(const hx_poly* p, double ln_rat_factor, double* slots_out);
 
+/* ---------------- BGV slots: EncryptedArray for d = ord_m(p) = 1, r = 1 (src/EncryptedArray.cpp) ----------------
+ * The plaintext prime p splits Phi_m completely (p = 1 mod m): phi(m) slots, each an element of Z_p.  Factor 0 of
+ * Phi_m mod p is X - rho with rho the largest primitive m-th root of unity mod p (the smallest factor by poly_comp,
+ * src/PAlgebra.cpp:67-81), factor i is X - rho^(1/t_i mod m), t_i = ith_rep(i) of Z_m^* in hypercube order
+ * (src/PAlgebra.cpp:520-570, 726-733).  Slot vectors are int64; the encoding of a is the H of degree < phi(m) with
+ * H(rho^(1/t_i)) = a_i mod p for every i.  Rings: m a power of two with 16 <= m <= 2^17, or any other m >= 3 through
+ * the general transform (an even m that is not a power of two needs 2m | p - 1, else HX_ERR_UNSUPPORTED).  All calls
+ * synchronise the context's stream and fail with HX_ERR_INVALID under an open graph capture. */
+typedef struct hx_bgv_slots hx_bgv_slots; /* the tables of one (context, p) pair */
+/* p not a prime below 2^60, or p | m: HX_ERR_INVALID.  d = ord_m(p) > 1: HX_ERR_UNSUPPORTED, the message names d.  p
+ * becomes the only prime of a side context of the table: the primes of ctx and their indices are untouched.  Destroy
+ * the table before its context. */
+int hx_bgv_slots_create(hx_ctx* ctx, uint64_t p, hx_bgv_slots** out);
+int hx_bgv_slots_destroy(hx_bgv_slots* t);
+/* p, rho, and the hypercube of Z_m^*: ndims generators with their orders (at most 8 are written); any output may be
+ * NULL. */
+int hx_bgv_slots_info(const hx_bgv_slots* t, uint64_t* p, uint64_t* rho, int* ndims, uint64_t* gens, uint64_t* ords);
+/* EncryptedArray::encode (src/EncryptedArray.cpp:438-447) of `batch` vectors of nslots <= phi(m) integers each
+ * ([batch][nslots], host; missing slots are 0, any int64 is reduced mod p): `out` (batch elements on its own prime
+ * set, a poly of the table's context) receives balanced(mul * H mod p) in evaluation form -- mul = 1 is the plain
+ * encoding, mul = Q mod p the balanced_MulMod of PubKey::Encrypt (src/keys.cpp:358-488); coeffs_out (optional, host,
+ * [batch][phi(m)]) receives that zzX, every coefficient in (-p/2, p/2). */
+int hx_bgv_encode(const hx_bgv_slots* t, const int64_t* slots, int batch, int nslots, uint64_t mul, hx_poly* out,
+                  int64_t* coeffs_out);
+/* The decode behind SecKey::Decrypt (src/keys.cpp:1383-1405): acc = sum_parts part * s^r in evaluation form (at most
+ * 64 primes; unchanged) -> slots_out[batch][phi(m)] (host) in [0, p): the centred CRT value reduced mod p (the
+ * arithmetic of hx_poly_rem, kept on the device), times factor_inv mod p (the inverse of productOfPrimes * intFactor;
+ * 1 if none), evaluated at the slots.  One download. */
+int hx_bgv_decode(const hx_bgv_slots* t, const hx_poly* acc, uint64_t factor_inv, int64_t* slots_out);
+/* EncryptedArray::decode of `batch` plaintext polynomials (host, [batch][phi(m)], any int64) -> slots_out as above. */
+int hx_bgv_embed(const hx_bgv_slots* t, const int64_t* coeffs, int batch, int64_t* slots_out);
+
 /* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
 /* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
  * Replaces n x { tmp = b; tmp *= a; x += tmp }: MulAdd, src/matmul.cpp:391-408, and DoubleCRT::Mul with
