@@ -15,9 +15,18 @@ ciphertexts and come back out.
                       SecKey::Decrypt, the transform mod p; one download)
   rotate1D            every dimension is native at d = 1: one automorphism (src/EncryptedArray.cpp:65-97)
   encodePtxt / multByConstant / addConstant   the EncodedPtxt interface (src/Ctxt.cpp:1952-2000, 2187-2224)
+  maskSlots           maskTable[i][j] (PAlgebraModDerived::genMaskTable, src/PAlgebra.cpp:1316-1338) as its 0/1 slot
+                      vector; a mask is encoded by the device encoder when it is used and kept in a small cache
+  shift1D / rotate / shift                    the linear array over the hypercube (src/EncryptedArray.cpp:130-174,
+                      181-285, 288-355): per dimension below the last one  tmp = ct * mask; ct -= tmp  -- copy /
+                      multByConstant / -= or, fused=True, one device call for the parts (capi.maskSplit: hx_mask_split,
+                      DESIGN 3.9d); the words and the bookkeeping (lnNoise, primeSet, intFactor, ptxtSpace) are the same
+                      either way, fused=None follows EncryptedArray.fuseMaskSplit
+  totalSums / runningSums                     src/EncryptedArray.cpp:695-736
 
-Out of scope: d > 1 (slots in GF(p^d)) and p^r with r > 1 -- refused with HX_ERR_UNSUPPORTED; the linear-array rotate /
-shift, totalSums and the matrix product for BGV.  Nothing here imports oracle/."""
+Out of scope: d > 1 (slots in GF(p^d)) and p^r with r > 1 -- refused with HX_ERR_UNSUPPORTED; the matrix products
+(MatMul1D / MatMulFull) for BGV.  Nothing here imports oracle/."""
+import collections
 import math
 
 import numpy as np
@@ -26,6 +35,7 @@ from . import capi
 from . import ctxt as hc
 from . import hostnt
 from .ckks import LogicError, innerProduct
+from .linalg import _like
 
 
 class DeviceEncoder:
@@ -216,3 +226,194 @@ class EncryptedArray:
         if amt == 0:
             return ct
         return ct.smartAutomorph(self.zMStar.genToPow(i, amt))
+
+    # ---- masks ----
+    MASK_CACHE = 32     # encoded masks kept per EncryptedArray (least recently used goes first)
+    fuseMaskSplit = False  # fused=None: term by term until hx_mask_split has been measured as the faster form
+
+    def _coords(self, i):
+        """PAlgebra::coordinate(i, k) for every slot k"""
+        stride = 1
+        for d in self.zMStar.ords[i + 1:]:
+            stride *= d
+        return np.arange(self.size(), dtype=np.int64) // stride % self.zMStar.ords[i]
+
+    def maskSlots(self, i, j):
+        """maskTable[i][j] (genMaskTable, src/PAlgebra.cpp:1316-1338) as slots: 1 where coordinate(i, k) >= j -- all
+        ones for j = 0, all zeros for j = OrderOf(i).  The table's polynomial is the encoding of this vector (a sum of
+        the idempotents crtTable[k])."""
+        if not 0 <= i < self.dimension():
+            raise capi.InvalidArgument(capi.HX_ERR_INVALID, "i must be between 0 and dimension()")
+        if not 0 <= j <= self.sizeOfDimension(i):
+            raise capi.InvalidArgument(capi.HX_ERR_INVALID, "j must be between 0 and the order of dimension i")
+        return (self._coords(i) >= j).astype(np.int64)
+
+    def _nextMask(self, mask, i, v):
+        """mask * (maskTable[i][v] - maskTable[i][v + 1]) + maskTable[i][v + 1]  (mod Phi_m)
+        (src/EncryptedArray.cpp:280-281, 344-345): products mod Phi_m are slot-wise, so it is done on the slots"""
+        hi = self.maskSlots(i, v + 1)
+        return (mask * (self.maskSlots(i, v) - hi) + hi) % self.p
+
+    def _encodedMask(self, mask, primeSet):
+        """(DoubleCRT(balanced_zzX(mask)) on primeSet, embeddingLargestCoeff of that zzX -- the size
+        Ctxt::multByConstant(const zzX&) takes, src/Ctxt.cpp:1872-1882).  Cached by (mask bytes, prime set), at most
+        MASK_CACHE entries: totalSums asks for the same few masks at every step."""
+        cache = self.__dict__.setdefault("_masks", collections.OrderedDict())
+        idx = sorted(primeSet)
+        key = (mask.tobytes(), tuple(idx))
+        hit = cache.get(key)
+        if hit is not None:
+            cache.move_to_end(key)
+            return hit
+        dcrt, poly = self.enc.encode(mask.reshape(1, -1), 1, idx, coeffs=True)
+        hit = cache[key] = (dcrt, float(np.max(self.enc.norm(poly))))
+        while len(cache) > self.MASK_CACHE:
+            cache.popitem(last=False)
+        return hit
+
+    def _multByMask(self, ct, mask):
+        """ctxt.multByConstant(balanced_zzX(mask))"""
+        if ct.parts:
+            ct.multByConstant(*self._encodedMask(mask, ct.primeSet))
+        return ct
+
+    def _maskSplit(self, ct, mask, fused=None):
+        """tmp = ctxt; tmp.multByConstant(mask_poly); ctxt -= tmp  (src/EncryptedArray.cpp:270-274, 334-338) -> tmp.
+        Fused: one capi.maskSplit per pair of parts, and the bookkeeping of the three calls done here --
+        multByConstant's lnNoise + ln(size) on tmp, addCtxt's noise and ptxtMag sums on ctxt (same prime set, plaintext
+        space and intFactor on both sides, so addCtxt changes nothing else).  It needs parts and a backend with
+        maskSplit (the scheme is BGV and the mask is encoded on ct's own prime set by construction); fused=True
+        insists on it, fused=False goes term by term."""
+        if not ct.parts:
+            return ct.clone()
+        ct._materializeTensor()
+        can = hasattr(ct.ops, "maskSplit")
+        if fused and not can:
+            raise LogicError("EncryptedArray: fused=True, but the mask split cannot be fused here")
+        if not ((self.fuseMaskSplit if fused is None else fused) and can):
+            tmp = ct.clone()
+            self._multByMask(tmp, mask)
+            ct -= tmp
+            return tmp
+        dcrt, size = self._encodedMask(mask, ct.primeSet)
+        keep = list(ct.parts.items())
+        take = {h: ct.ops.likeUninit(p) for h, p in keep}
+        for a in range(0, len(keep), 2):
+            (h0, k0), (h1, k1) = keep[a], keep[a + 1] if a + 1 < len(keep) else (None, None)
+            ct.ops.maskSplit(k0, k1, take[h0], take[h1] if k1 is not None else None, dcrt)
+        tmp = _like(ct, take)
+        tmp.lnNoise = tmp.lnNoise + hc._ln(size)
+        ct.ptxtMag += tmp.ptxtMag
+        ct.lnNoise = hc.logaddexp(ct.lnNoise, tmp.lnNoise)
+        return tmp
+
+    # ---- the linear array ----
+    def shift1D(self, ct, i, k):
+        """EncryptedArray::shift1D (src/EncryptedArray.cpp:130-174): k positions along dimension i with zero fill"""
+        if not 0 <= i < self.dimension():
+            raise capi.InvalidArgument(capi.HX_ERR_INVALID,
+                                       "i must be non-negative and less than the PAlgebra's generator count")
+        ord_ = self.sizeOfDimension(i)
+        if k <= -ord_ or k >= ord_:
+            ct.clear()
+            return ct
+        amt = k % ord_                       # in [1, ord - 1]
+        if amt == 0:
+            return ct
+        mask = self.maskSlots(i, ord_ - amt)
+        if k < 0:
+            val = self.zMStar.genToPow(i, amt - ord_)
+        else:
+            mask = 1 - mask
+            val = self.zMStar.genToPow(i, amt)
+        self._multByMask(ct, mask)           # zero out slots where mask = 0
+        return ct.smartAutomorph(val)
+
+    def rotate(self, ct, amt, fused=None):
+        """EncryptedArray::rotate (src/EncryptedArray.cpp:181-285): slot j moves to slot j + amt mod nslots"""
+        ngens = self.dimension()
+        if ngens == 1:                       # simple case: just one generator
+            return self.rotate1D(ct, 0, amt)
+        amt %= self.size()                   # in [1, nslots - 1]
+        if amt == 0:
+            return ct
+        # one dimension at a time
+        i = ngens - 1
+        v = self.coordinate(i, amt)
+        mask = self.maskSlots(i, v)
+        # :221-264 fold a non-native last dimension's own mask into the loop.  At d = 1 <p> is trivial, every
+        # generator has the same order in Z_m^* / <p> as in Z_m^* (SameOrd), and that branch cannot be reached.
+        if not self.nativeDimension(i):
+            raise LogicError("EncryptedArray::rotate: a non-native dimension at d = 1")
+        self.rotate1D(ct, i, v)
+        for i in range(i - 1, -1, -1):
+            v = self.coordinate(i, amt)
+            tmp = self._maskSplit(ct, mask, fused)      # tmp: the slots in which mask = 1; ct: those with mask = 0
+            self.rotate1D(tmp, i, v)
+            self.rotate1D(ct, i, v + 1)
+            ct += tmp
+            if i > 0:
+                mask = self._nextMask(mask, i, v)
+        return ct
+
+    def shift(self, ct, k, fused=None):
+        """EncryptedArray::shift (src/EncryptedArray.cpp:288-355): slot j moves to slot j + k, zeros come in"""
+        ngens = self.dimension()
+        if ngens == 1:
+            return self.shift1D(ct, 0, k)
+        n = self.size()
+        if k <= -n or k >= n:                # an all-zero ciphertext
+            return ct.multByScalar(0)
+        amt = k % n                          # in [1, nslots - 1]
+        if amt == 0:
+            return ct
+        i = ngens - 1
+        v = self.coordinate(i, amt)
+        mask = self.maskSlots(i, v)
+        self.rotate1D(ct, i, v)
+        for i in range(i - 1, -1, -1):
+            v = self.coordinate(i, amt)
+            tmp = self._maskSplit(ct, mask, fused)
+            if i > 0:
+                self.rotate1D(ct, i, v + 1)
+                self.rotate1D(tmp, i, v)
+                ct += tmp
+                mask = self._nextMask(mask, i, v)
+            else:
+                if k < 0:
+                    v -= self.sizeOfDimension(0)
+                self.shift1D(tmp, 0, v)
+                self.shift1D(ct, 0, v + 1)   # may leave ct empty: += then copies tmp (Ctxt::addCtxt, src/Ctxt.cpp:1420-1426)
+                ct += tmp
+        return ct
+
+    def runningSums(self, ct, fused=None):
+        """runningSums (src/EncryptedArray.cpp:695-706): slot j <- sum of slots 0 .. j"""
+        n = self.size()
+        shamt = 1
+        while shamt < n:
+            tmp = ct.clone()
+            self.shift(tmp, shamt, fused=fused)
+            ct += tmp                        # ct = ct + (ct >> shamt)
+            shamt *= 2
+        return ct
+
+    def totalSums(self, ct, fused=None):
+        """totalSums (src/EncryptedArray.cpp:708-736): every slot <- the sum of all slots; the recursion follows the
+        bits of n, which need not be a power of two"""
+        n = self.size()
+        if n == 1:
+            return ct
+        orig = ct.clone()
+        e = 1
+        for i in range(n.bit_length() - 2, -1, -1):
+            tmp1 = ct.clone()
+            self.rotate(tmp1, e, fused=fused)
+            ct += tmp1                       # ct = ct + (ct >>> e)
+            e *= 2
+            if (n >> i) & 1:
+                tmp2 = orig.clone()
+                self.rotate(tmp2, e, fused=fused)
+                ct += tmp2                   # ct = ct + (orig >>> e)
+                e += 1
+        return ct

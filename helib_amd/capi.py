@@ -59,7 +59,7 @@ SYMBOLS = [
     "hx_profile_begin", "hx_profile_end", "hx_ctx_arena_stats", "hx_ctx_reserve",
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
-    "hx_mul_add_many", "hx_poly_extract",
+    "hx_mul_add_many", "hx_poly_extract", "hx_mask_split",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
 ]
 
@@ -153,6 +153,7 @@ def lib():
             "hx_ckks_decode": [vp, C.c_double, vp],
             "hx_mul_add_many": [vp, vp, vp, vp, vp, ip, ip],
             "hx_poly_extract": [vp, vp, ip],
+            "hx_mask_split": [vp, vp, vp, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -739,6 +740,22 @@ def mulAddMany(out0, out1, consts, in0, in1, accumulate=True):
         return (C.c_void_p * max(n, 1))(*[p.h for p in ps])
     _chk(lib().hx_mul_add_many(out0.h, out1.h if out1 is not None else None, arr(consts), arr(in0),
                                arr(in1) if in1 is not None else None, n, 1 if accumulate else 0))
+
+
+def maskSplit(keep0, keep1, take0, take1, mask):
+    """take = keep * mask, keep -= take on the one or two parts of a ciphertext in one pass (hx_mask_split): tmp = ctxt;
+    tmp.multByConstant(mask); ctxt -= tmp (src/EncryptedArray.cpp:270-274).  keep1 / take1 = None for a one-part
+    ciphertext; take* are overwritten (make them with likeUninit).  In a context created under HX_NO_MASK_SPLIT=1 the
+    call issues hx_poly_copy, hx_mul and hx_sub per part instead; the words are the same."""
+    if (keep1 is None) != (take1 is None):
+        raise InvalidArgument(HX_ERR_INVALID, "keep1 and take1 go together (both None for a one-part ciphertext)")
+    _chk(lib().hx_mask_split(keep0.h, keep1.h if keep1 is not None else None, take0.h,
+                             take1.h if take1 is not None else None, mask.h))
+
+
+def likeUninit(poly):
+    """a DoubleCRT with poly's batch and prime set whose rows are about to be overwritten"""
+    return DoubleCRT(poly.context, poly.getIndexSet(), poly.batch, zero=False)
 
 
 def splitBatch(poly):

@@ -15,6 +15,7 @@ struct CtxView {
   uint64_t m;
   uint32_t phim;
   bool capturing;             // a graph capture is open
+  bool no_mask_split;         // the context's HX_NO_MASK_SPLIT (switches.h)
   void** state;               // the slot unit's per-context state ...
   void (**state_free)(void*); // ... and how the context releases it
   void** linalg;              // the same pair for linalg.hip

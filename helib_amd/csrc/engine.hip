@@ -5148,6 +5148,7 @@ int ctx_enter(hx_ctx* c, CtxView* v)
   v->m = c->m;
   v->phim = c->phim;
   v->capturing = c->capturing;
+  v->no_mask_split = c->sw.no_mask_split;
   v->state = &c->ckks;
   v->state_free = &c->ckks_free;
   v->linalg = &c->linalg;

@@ -1,8 +1,11 @@
 // linalg.hip -- C ABI of the fused multiply-add of the matrix product (include/helib_amd.h: hx_mul_add_many):
 //   out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]
 // the inner loop of MatMul1DExec::mul, n x MulAdd (src/matmul.cpp:391-408: tmp = b; tmp *= a; x += tmp, the product
-// being DoubleCRT::Mul with matchIndexSets = false), in one pass over the data.  The unit reaches the context only
-// through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
+// being DoubleCRT::Mul with matchIndexSets = false), in one pass over the data; and of the mask split of the
+// linear-array rotate / shift (hx_mask_split):
+//   take = keep * mask,  keep -= take
+// (src/EncryptedArray.cpp:270-274: tmp = ctxt; tmp.multByConstant(mask); ctxt -= tmp), in one pass as well.  The unit
+// reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
 #include <hip/hip_runtime.h>
 
 #include <cstdarg>
@@ -124,6 +127,61 @@ mul_add_many_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, ro
     st_stream2(out0 + row_off + boff[b], make_ulonglong2((uint64_t)a0[b][0], (uint64_t)a0[b][1]));
     if (PARTS == 2)
       st_stream2(out1 + row_off + boff[b], make_ulonglong2((uint64_t)a1[b][0], (uint64_t)a1[b][1]));
+  }
+}
+
+// take = keep * mask, keep = keep - take (hx_mask_split): what hx_poly_copy, hx_mul and hx_sub leave, word for word --
+// the product is ew_binary_kernel<EW_MUL>'s mul_mod, the difference its sub_mod.  One thread owns two adjacent
+// coefficients of one prime row for BP batch elements: it loads the two mask words once when the mask has batch 1
+// (mask_per_elem = 0) and uses them for all BP elements, loads PARTS * BP keep vectors (16 bytes each, non-temporal:
+// every word is read once) and stores 2 * PARTS * BP vectors.  map.brow[r] is the mask's row for output row r.  No
+// LDS: nothing is shared between threads.  All addresses are kernel arguments, so a launch can be captured.
+template <int PARTS, int BP>
+__global__ void __launch_bounds__(256)
+mask_split_kernel(uint64_t* __restrict__ keep0, uint64_t* __restrict__ keep1, uint64_t* __restrict__ take0,
+                  uint64_t* __restrict__ take1, const uint64_t* __restrict__ mask, int mask_per_elem, int batch,
+                  uint32_t N, RowMap2 map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu;
+  const uint32_t k = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  const uint64_t* mrow = mask + (size_t)map.brow[row] * (mask_per_elem ? batch : 1) * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  ulonglong2 x0[BP], x1[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    x0[b] = ld_stream2(keep0 + row_off + boff[b]);
+    if (PARTS == 2)
+      x1[b] = ld_stream2(keep1 + row_off + boff[b]);
+  }
+  ulonglong2 c = *reinterpret_cast<const ulonglong2*>(mrow + (mask_per_elem ? boff[0] : 2 * (size_t)i));
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    if (b > 0 && mask_per_elem)
+      c = *reinterpret_cast<const ulonglong2*>(mrow + boff[b]);
+    ulonglong2 t;
+    t.x = mul_mod(x0[b].x, c.x, q, mu, k);
+    t.y = mul_mod(x0[b].y, c.y, q, mu, k);
+    st_stream2(take0 + row_off + boff[b], t);
+    st_stream2(keep0 + row_off + boff[b], make_ulonglong2(sub_mod(x0[b].x, t.x, q), sub_mod(x0[b].y, t.y, q)));
+    if (PARTS == 2) {
+      t.x = mul_mod(x1[b].x, c.x, q, mu, k);
+      t.y = mul_mod(x1[b].y, c.y, q, mu, k);
+      st_stream2(take1 + row_off + boff[b], t);
+      st_stream2(keep1 + row_off + boff[b], make_ulonglong2(sub_mod(x1[b].x, t.x, q), sub_mod(x1[b].y, t.y, q)));
+    }
   }
 }
 
@@ -348,6 +406,107 @@ extern "C" int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* cons
     launch<2>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
   else
     launch<1>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+template <int PARTS>
+static void launch_split(int bp, dim3 grid, hipStream_t st, uint64_t* k0, uint64_t* k1, uint64_t* t0, uint64_t* t1,
+                         const uint64_t* mask, int per_elem, int batch, uint32_t N, const hx::RowMap2& map,
+                         const hx::PrimeDev* primes)
+{
+  if (bp == 1)
+    HX_LAUNCH((hx::mask_split_kernel<PARTS, 1>), grid, dim3(256), 0, st, k0, k1, t0, t1, mask, per_elem, batch, N, map,
+              primes);
+  else
+    HX_LAUNCH((hx::mask_split_kernel<PARTS, 4>), grid, dim3(256), 0, st, k0, k1, t0, t1, mask, per_elem, batch, N, map,
+              primes);
+}
+
+extern "C" int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_poly* take1, const hx_poly* mask)
+{
+  if (!keep0 || !take0 || !mask)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((keep1 == nullptr) != (take1 == nullptr))
+    return err(HX_ERR_INVALID, "keep1 and take1 go together (both null for a one-part ciphertext)");
+  const int parts = keep1 ? 2 : 1;
+  hx_poly* outs[4] = {keep0, take0, keep1, take1};
+  for (int a = 0; a < 2 * parts; a++) {
+    if (outs[a] == mask)
+      return err(HX_ERR_INVALID, "an output is also the mask");
+    for (int b = a + 1; b < 2 * parts; b++)
+      if (outs[a] == outs[b])
+        return err(HX_ERR_INVALID, "keep0, keep1, take0 and take1 must be different polys");
+  }
+  hx_ctx* ctx = hxi::poly_ctx(keep0);
+  for (int a = 1; a < 2 * parts; a++)
+    if (hxi::poly_ctx(outs[a]) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  if (hxi::poly_ctx(mask) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  int batch = 0, b2 = 0;
+  std::vector<int> idx, other;
+  RC(shape_of(keep0, &batch, &idx));
+  const int rows = (int)idx.size();
+  if (rows > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  static const char* const name[4] = {"keep0", "take0", "keep1", "take1"};
+  for (int a = 1; a < 2 * parts; a++) {
+    RC(shape_of(outs[a], &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "%s differs from keep0 in batch or prime set", name[a]);
+  }
+  RC(shape_of(mask, &b2, &other));
+  if (b2 != batch && b2 != 1)
+    return err(HX_ERR_INVALID, "mask: batch %d is neither 1 nor %d", b2, batch);
+  const int per_elem = b2 == batch && batch > 1;
+  hx::RowMap2 map;
+  for (int r = 0; r < rows; r++) {
+    int at = -1;
+    for (size_t j = 0; j < other.size(); j++)
+      if (other[j] == idx[r]) {
+        at = (int)j;
+        break;
+      }
+    if (at < 0)
+      return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the mask has no row for prime %d)", idx[r]);
+    map.p[r] = (uint16_t)idx[r];
+    map.brow[r] = (uint16_t)at;
+  }
+  const uint32_t N = v.phim;
+  if (N < 2 || (N & 1))
+    return err(HX_ERR_UNSUPPORTED, "hx_mask_split needs an even number of coefficients");
+  if (rows == 0)
+    return HX_OK;
+  if (v.no_mask_split) {   // HX_NO_MASK_SPLIT: the sequence the kernel replaces
+    for (int a = 0; a < parts; a++) {
+      RC(hx_poly_copy(outs[2 * a + 1], outs[2 * a]));
+      RC(hx_mul(outs[2 * a + 1], mask));
+      RC(hx_sub(outs[2 * a], outs[2 * a + 1]));
+    }
+    return HX_OK;
+  }
+  // take first: one that still shares keep's rows (a lazy hx_poly_copy) lets go of them, and keep is then updated in
+  // place without a copy
+  uint64_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
+  for (int a = 0; a < parts; a++)
+    RC(hxi::poly_rows_write(outs[2 * a + 1], &d[2 * a + 1]));
+  for (int a = 0; a < parts; a++)
+    RC(hxi::poly_rows_update(outs[2 * a], &d[2 * a]));
+  const uint64_t* mp = hxi::poly_rows_read(mask);
+  if (((uint64_t)(uintptr_t)d[0] | (uint64_t)(uintptr_t)d[1] | (uint64_t)(uintptr_t)d[2] | (uint64_t)(uintptr_t)d[3] |
+       (uint64_t)(uintptr_t)mp) & 15)
+    return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
+  const int bp = batch == 1 ? 1 : 4;
+  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  if (parts == 2)
+    launch_split<2>(bp, grid, v.stream, d[0], d[2], d[1], d[3], mp, per_elem, batch, N, map, primes);
+  else
+    launch_split<1>(bp, grid, v.stream, d[0], nullptr, d[1], nullptr, mp, per_elem, batch, N, map, primes);
   CK(hipGetLastError());
   return HX_OK;
 }

@@ -28,6 +28,8 @@ struct Switches {
   bool no_mfma_ext = false;      // HX_NO_MFMA_EXT=1     rns_extend_wide_kernel (VALU limb products) instead of the matrix-core form
                                  //                      rns_extend_mfma_kernel (17..40 sources; HX_NO_WIDE_EXTEND implies it)
   int mfma_min_n = 9;            // HX_MFMA_MIN_N=n      ... from n source primes on (9 .. 16: the fast kernels' plans; 17 .. 40 always)
+  bool no_mask_split = false;    // HX_NO_MASK_SPLIT=1   hx_mask_split as hx_poly_copy + hx_mul + hx_sub per part instead of mask_split_kernel
+                                 //                      (linalg.hip)
   int brk_lds_pad_rows = 0;      // HX_BRK_LDS_PAD=n     digit kernel: n more (unused) LDS rows per thread -- lowers its occupancy, an A/B probe
   // fused ciphertext-level paths
   bool no_tensor_multi = false;  // HX_NO_TENSOR_MULTI=1 tensor product + several-primes mod-switch as two steps
@@ -72,6 +74,7 @@ inline Switches read()
   s.no_mfma_ext = on("HX_NO_MFMA_EXT") || s.no_wide_extend;
   if (const char* e = std::getenv("HX_MFMA_MIN_N"))
     s.mfma_min_n = std::atoi(e);
+  s.no_mask_split = on("HX_NO_MASK_SPLIT");
   if (const char* e = std::getenv("HX_BRK_LDS_PAD"))
     s.brk_lds_pad_rows = std::atoi(e);
   s.half15 = on("HX_HALF15");

@@ -473,6 +473,15 @@ class Ctxt:
         c.lnNoise = math.log(context.freshNoiseBound())
         return c
 
+    def clear(self):
+        """Ctxt::clear (include/helib/Ctxt.h:1347-1354): an empty ciphertext on the ctxt primes"""
+        self._pending, self._pendT = [], None
+        self.parts = {}
+        self.primeSet = frozenset(self.context.ctxtPrimes)
+        self._ln = -math.inf
+        self.intFactor = 1
+        self.ptxtMag, self.lnRatFactor = 1.0, 0.0
+
     def clone(self):
         self._materializeTensor()
         c = Ctxt(self.context, self.ops, self.ksw, self.ksw_ptxtSpace, self.ksw_lnNoise)

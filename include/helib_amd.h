@@ -204,6 +204,7 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
  *                                            margin of an HPS quotient (default 2^-30); HPS from n sources on (9)
  *   HX_NO_LAZY_RNS                            no 128-bit lazy sums / single-subtraction Garner steps
  *   HX_NO_FAST_BREAK, HX_NO_FAST_EXTEND, HX_NO_WIDE_EXTEND   generic breakIntoDigits / basis-extension kernels
+ *   HX_NO_MASK_SPLIT                          hx_mask_split as hx_poly_copy + hx_mul + hx_sub per part
  *   HX_NO_TENSOR_MULTI, HX_NO_MULRELIN_FUSE   tensor product as a pass of its own in front of the several-primes
  *                                            mod-switch / inside hx_mul_relin
  *   HX_NO_PROTH                               row transforms: Shoup butterflies on every row (by default rows of primes
@@ -375,6 +376,19 @@ int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* const* c, const
 /* dst (batch 1, the prime set of src in the same order) <- batch element b of src: how a batch of encoded diagonals
  * becomes the batch-1 constants above.  Asynchronous on the context's stream; works under a graph capture. */
 int hx_poly_extract(hx_poly* dst, const hx_poly* src, int b);
+/* The mask split of the linear-array rotate / shift (src/EncryptedArray.cpp:270-274, 334-338:
+ *   tmp = ctxt;  tmp.multByConstant(mask);  ctxt -= tmp;)
+ * on the parts of one ciphertext, in one pass:  take = keep * mask,  keep = keep - take,  row by row modulo each
+ * prime, every word canonical in [0, q) and equal to what hx_poly_copy(take, keep), hx_mul(take, mask),
+ * hx_sub(keep, take) leave.  keep1 and take1 are both null for a one-part operand.  take0 / take1 are written, not
+ * read; they have the batch and the prime set (same order) of keep0 / keep1.  mask is in evaluation form, with batch 1
+ * (broadcast over the batch) or the batch of keep, and may live on more primes than keep: its rows are matched by
+ * prime index, a missing prime is HX_ERR_PRIMESET (as hx_mul's).  Null arguments, an output that is also the mask,
+ * keep and take (or the two parts) being one poly, a poly of another context and mismatched shapes are
+ * HX_ERR_INVALID; an odd phi(m) is HX_ERR_UNSUPPORTED; a refused call touches no output.  Every pointer travels as a
+ * kernel argument: the call is asynchronous on the context's stream and may be recorded in a graph capture.
+ * HX_NO_MASK_SPLIT=1 runs the three calls per part instead. */
+int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_poly* take1, const hx_poly* mask);
 
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
