@@ -14,8 +14,13 @@ CSRC = os.path.join(HERE, "csrc")
 LIBDIR = os.path.join(HERE, "lib")
 SO = os.path.join(LIBDIR, "libhelib_amd.so")
 # (source, extra flags, object): ntt_kernels.hip is compiled once per ring size, in parallel (see the top of that file)
-UNITS = [("ntt_kernels.hip", ["-DHX_NTT_ONLY=13"], "ntt_kernels_13.o"), ("ntt_kernels.hip", ["-DHX_NTT_ONLY=14"], "ntt_kernels_14.o"),
-         ("ntt_kernels.hip", ["-DHX_NTT_ONLY=15"], "ntt_kernels_15.o"), ("ntt_dispatch.hip", [], "ntt_dispatch.o"),
+# (HX_NTT_PART=2: the fused last-digit key switch of that ring size alone, 1: everything else)
+UNITS = [("ntt_kernels.hip", ["-DHX_NTT_ONLY=13", "-DHX_NTT_PART=1"], "ntt_kernels_13.o"),
+         ("ntt_kernels.hip", ["-DHX_NTT_ONLY=14", "-DHX_NTT_PART=1"], "ntt_kernels_14.o"),
+         ("ntt_kernels.hip", ["-DHX_NTT_ONLY=15", "-DHX_NTT_PART=1"], "ntt_kernels_15.o"),
+         ("ntt_kernels.hip", ["-DHX_NTT_ONLY=13", "-DHX_NTT_PART=2"], "ntt_kslast_13.o"),
+         ("ntt_kernels.hip", ["-DHX_NTT_ONLY=14", "-DHX_NTT_PART=2"], "ntt_kslast_14.o"),
+         ("ntt_kernels.hip", ["-DHX_NTT_ONLY=15", "-DHX_NTT_PART=2"], "ntt_kslast_15.o"), ("ntt_dispatch.hip", [], "ntt_dispatch.o"),
          ("conv_kernels.hip", [], "conv_kernels.o"), ("pfa_kernels.hip", [], "pfa_kernels.o"), ("rns_mfma_kernels.hip", [], "rns_mfma_kernels.o"),
          ("ckks_slots.hip", [], "ckks_slots.o"), ("bgv_slots.hip", [], "bgv_slots.o"), ("linalg.hip", [], "linalg.o"),
          ("engine.hip", [], "engine.o")]

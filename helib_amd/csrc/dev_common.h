@@ -180,6 +180,33 @@ struct RowScalars {
   uint64_t cp[MAX_ROWS];  // Shoup precon floor(c*2^64/q)
 };
 
+// Key switch (rns_kernels.h keyswitch_kernel, ntt_kernels.hip ntt_keyswitch_last_kernel): per-row constants of the
+// own-row rebuild, one entry per output row, in device memory
+constexpr int KS_MAXD = 8;
+struct KsFix {
+  int64_t owner;        // digit owning this row, -1 for special primes
+  TW pinv[KS_MAXD];     // P_e^-1 mod q_row for e < owner
+  TW pscale;            // product of the special primes mod q_row (addPrimesAndScale factor)
+};
+// ntt_keyswitch_last_kernel: the key switch of output row j with the forward transform of ONE of its extension rows
+// -- digit fd[j], the last digit that does not own the row -- done in the same workgroup
+struct KsLastPlan {
+  uint16_t fd[MAX_ROWS];
+};
+struct KsLastArgs {
+  const uint64_t* dig_in;   // [ndig][nall][batch][N] digit rows as the digit kernel left them (coefficients, lazy words)
+  const uint64_t* dig_ev;   // the same block where the other extension rows stand transformed (may be dig_in)
+  const uint64_t* kb;       // [ndig][wrows][N] key rows, shared by the batch
+  const uint64_t* ka;
+  uint64_t* out0;           // [nall][batch][N]
+  uint64_t* out1;
+  const uint64_t* own_src;  // [L][batch][N] evaluation rows of the s^2 part (own-row rebuild)
+  const uint64_t* acc0;     // [L][batch][N] what the owned rows start from: the unscaled parts (1), (s) (scale_parts = 1),
+  const uint64_t* acc1;     // or out0 / out1 themselves (scale_parts = 0); acc1 null: no (s) part, zero
+  const KsFix* fix;         // [nall]
+  int nall, wrows, batch, scale_parts;
+};
+
 typedef unsigned __int128 u128;
 
 // Read-only tables (basis-extension plans, per-row constants): pointers into the CONSTANT address

@@ -35,6 +35,8 @@ hipError_t launch_ntt_pow2(int logn, bool inverse, const uint64_t* in, uint64_t*
                            const TW* tw_arena, hipStream_t st);
 hipError_t launch_ntt_pow2_lazy_in(int logn, const uint64_t* in, uint64_t* out, const NttRows& rows, int nrows, int batch,
                                    const PrimeDev* primes, const TW* tw_arena, hipStream_t st);
+hipError_t launch_keyswitch_last_pow2(int logn, int nd, const KsLastArgs& A, const RowMap2& map, const KsLastPlan& plan, int device,
+                                      const PrimeDev* primes, const TW* tw_arena, hipStream_t st);
 hipError_t launch_ntt_half15_fwd(bool lazy_in, const uint64_t* in, uint64_t* out, const NttRows& rows, int nrows, int batch,
                                  const PrimeDev* sub_primes, const TW* tw_arena, hipStream_t st);
 hipError_t launch_moddown_pow2(int logn, const PolyBases& data, const PolyBases& out, int drop_row,
@@ -4668,6 +4670,55 @@ extern "C" int hx_tensor(const hx_poly* c0, const hx_poly* c1, const hx_poly* d0
   return tensor_launch(c0, c1, d0, d1, o0->d, o1->d, o2->d, nullptr);
 }
 
+// cached per-row table of the key switch's own-row rebuild (hx::KsFix): owner digit of every row, P_e^-1 mod q_row
+// for the earlier digits, and the addPrimesAndScale factor of the parts (1), (s)
+static int ks_fix_table(hx_ctx* c, const std::vector<int>& all, const std::vector<int>& owner,
+                        const std::vector<std::vector<int>>& digit_primes, const hx::KsFix** out)
+{
+  const int nall = (int)all.size();
+  std::vector<uint64_t> key;
+  key.push_back(0xF1F1F1F1ull);
+  for (int r : all)
+    key.push_back((uint64_t)r);
+  for (auto& dp : digit_primes) {
+    key.push_back(0xFFFFull);
+    for (int p : dp)
+      key.push_back((uint64_t)p);
+  }
+  auto it = c->plans.find(key);
+  if (it == c->plans.end()) {
+    if ((int)digit_primes.size() > hx::KS_MAXD)
+      return fail(HX_ERR_UNSUPPORTED, "more than %d digits", hx::KS_MAXD);
+    std::vector<hx::KsFix> h(nall);
+    for (int r = 0; r < nall; r++) {
+      memset(&h[r], 0, sizeof(hx::KsFix));
+      h[r].owner = owner[r];
+      uint64_t q = c->primes[all[r]].q;
+      for (int e = 0; e < (int)digit_primes.size(); e++) {
+        uint64_t pe = 1;
+        for (int p : digit_primes[e])
+          pe = hxh::mulmod(pe, c->primes[p].q % q, q);
+        uint64_t inv = (h[r].owner >= 0 && e < h[r].owner) ? hxh::invmod(pe, q) : 0;
+        h[r].pinv[e].w = inv;
+        h[r].pinv[e].wp = hxh::shoup(inv, q);
+      }
+      uint64_t ps = 1;
+      for (int t = 0; t < nall; t++)
+        if (owner[t] < 0)
+          ps = hxh::mulmod(ps, c->primes[all[t]].q % q, q);
+      h[r].pscale.w = ps;
+      h[r].pscale.wp = hxh::shoup(ps, q);
+    }
+    ExtPlan* pl = new ExtPlan();
+    memset(&pl->dev, 0, sizeof pl->dev);
+    HIPCHK(hipMalloc(&pl->blob, sizeof(hx::KsFix) * nall));
+    HIPCHK(hipMemcpy(pl->blob, h.data(), sizeof(hx::KsFix) * nall, hipMemcpyHostToDevice));
+    it = c->plans.emplace(key, pl).first;
+  }
+  *out = reinterpret_cast<const hx::KsFix*>(it->second->blob);
+  return HX_OK;
+}
+
 // own_src/owner: when given, digit `owner[r]` of row r is not read from `dig` but rebuilt in the
 // evaluation domain from the s^2 part and the earlier digits (src/DoubleCRT.cpp:552-556 applied
 // row-wise): own = (...((c - d_0)/P_0 - d_1)/P_1 ...).
@@ -4698,49 +4749,8 @@ static int keyswitch_launch(hx_ctx* c, const uint64_t* dig, const hx_ksk* W,
     if (hxh::bitlen(c->primes[r].q) > 60)
       lazy = 0;
   const hx::KsFix* d_fix = nullptr;
-  if (own_src || ts) {
-    // cached table: owner digit of every row and P_e^-1 mod q_row for the earlier digits
-    std::vector<uint64_t> key;
-    key.push_back(0xF1F1F1F1ull);
-    for (int r : all)
-      key.push_back((uint64_t)r);
-    for (auto& dp : *digit_primes) {
-      key.push_back(0xFFFFull);
-      for (int p : dp)
-        key.push_back((uint64_t)p);
-    }
-    auto it = c->plans.find(key);
-    if (it == c->plans.end()) {
-      if ((int)digit_primes->size() > hx::KS_MAXD)
-        return fail(HX_ERR_UNSUPPORTED, "more than %d digits", hx::KS_MAXD);
-      std::vector<hx::KsFix> h(nall);
-      for (int r = 0; r < nall; r++) {
-        memset(&h[r], 0, sizeof(hx::KsFix));
-        h[r].owner = (*owner)[r];
-        uint64_t q = c->primes[all[r]].q;
-        for (int e = 0; e < (int)digit_primes->size(); e++) {
-          uint64_t pe = 1;
-          for (int p : (*digit_primes)[e])
-            pe = hxh::mulmod(pe, c->primes[p].q % q, q);
-          uint64_t inv = (h[r].owner >= 0 && e < h[r].owner) ? hxh::invmod(pe, q) : 0;
-          h[r].pinv[e].w = inv;
-          h[r].pinv[e].wp = hxh::shoup(inv, q);
-        }
-        uint64_t ps = 1;
-        for (int t = 0; t < nall; t++)
-          if ((*owner)[t] < 0)
-            ps = hxh::mulmod(ps, c->primes[all[t]].q % q, q);
-        h[r].pscale.w = ps;
-        h[r].pscale.wp = hxh::shoup(ps, q);
-      }
-      ExtPlan* pl = new ExtPlan();
-      memset(&pl->dev, 0, sizeof pl->dev);
-      HIPCHK(hipMalloc(&pl->blob, sizeof(hx::KsFix) * nall));
-      HIPCHK(hipMemcpy(pl->blob, h.data(), sizeof(hx::KsFix) * nall, hipMemcpyHostToDevice));
-      it = c->plans.emplace(key, pl).first;
-    }
-    d_fix = reinterpret_cast<const hx::KsFix*>(it->second->blob);
-  }
+  if (own_src || ts)
+    CHK(ks_fix_table(c, all, *owner, *digit_primes, &d_fix));
 #define HX_KS_LAUNCH(ND)                                                                                           \
   HX_LAUNCH(hx::keyswitch_kernel<ND>, ew_grid(rw, nall), dim3(256), 0, c->stream, dig, W->d_b, W->d_a, out0, out1,  \
             map, ndig, nall, (int)W->row_idx.size(), batch, c->phim, accumulate_rows, c->d_primes, own_src, d_fix,  \
@@ -4754,6 +4764,70 @@ static int keyswitch_launch(hx_ctx* c, const uint64_t* dig, const hx_ksk* W,
   }
 #undef HX_KS_LAUNCH
   HIPCHK(hipGetLastError());
+  return HX_OK;
+}
+
+// The key switch of relin_core with each output row's last digit transform fused in (ntt_kernels.hip
+// ntt_keyswitch_last_kernel).  fd[r] = the last digit that does not own row r: its extension row is
+// transformed inside the key switch's workgroup of (r, element) and never stored.
+static std::vector<int> ks_last_digit(const std::vector<int>& owner, int ndig)
+{
+  std::vector<int> fd(owner.size());
+  for (size_t r = 0; r < owner.size(); r++)
+    fd[r] = owner[r] == ndig - 1 ? ndig - 2 : ndig - 1;
+  return fd;
+}
+// the route applies: a row-kernel ring, 2 .. 4 digits, primes in (2^32, 2^60) (the kernel's 128-bit lazy sums and its
+// 32-bit-reciprocal normalisation), rows < L exactly the rows some digit owns, and the switch not set
+static bool ks_last_ok(const hx_ctx* c, const hx_ksk* W, const std::vector<int>& all, const std::vector<int>& owner, int L,
+                       int ndig)
+{
+  if (c->sw.no_ks_last_fuse || !c->pow2 || c->logn < 13 || c->logn > 15 || ndig < 2 || ndig > 4 || W->ndig > 8 ||
+      (int)all.size() > MAX_ROWS)
+    return false;
+  for (size_t r = 0; r < all.size(); r++) {
+    const uint64_t q = c->primes[(size_t)all[r]].q;
+    if (hxh::bitlen(q) > 60 || (q >> 32) == 0 || (owner[r] >= 0) != ((int)r < L) || owner[r] >= ndig)
+      return false;
+  }
+  return true;
+}
+static int keyswitch_last_launch(hx_ctx* c, const uint64_t* dig_in, const uint64_t* dig_ev, const hx_ksk* W,
+                                 const std::vector<int>& all, int batch, uint64_t* out0, uint64_t* out1, const uint64_t* own_src,
+                                 const std::vector<int>& owner, const std::vector<std::vector<int>>& digit_primes, int ndig,
+                                 const uint64_t* t0s, const uint64_t* t1s)
+{
+  const int nall = (int)all.size();
+  RowMap2 map;
+  hx::KsLastPlan plan;
+  const std::vector<int> fd = ks_last_digit(owner, ndig);
+  for (int r = 0; r < nall; r++) {
+    int wr = find_row(W->row_idx, all[r]);
+    if (wr < 0)
+      return fail(HX_ERR_PRIMESET, "key-switching matrix is not defined on the operand's primes");
+    map.p[r] = (uint16_t)all[r];
+    map.brow[r] = (uint16_t)wr;
+    plan.fd[r] = (uint16_t)fd[r];
+  }
+  hx::KsLastArgs A;
+  CHK(ks_fix_table(c, all, owner, digit_primes, &A.fix));
+  A.dig_in = dig_in;
+  A.dig_ev = dig_ev;
+  A.kb = W->d_b;
+  A.ka = W->d_a;
+  A.out0 = out0;
+  A.out1 = out1;
+  A.own_src = own_src;
+  // the owned rows start from the unscaled parts (1), (s) -- or, without them, from what out0 / out1 already hold
+  A.acc0 = t0s ? t0s : out0;
+  A.acc1 = t0s ? t1s : out1;
+  A.scale_parts = t0s ? 1 : 0;
+  A.nall = nall;
+  A.wrows = (int)W->row_idx.size();
+  A.batch = batch;
+  hipError_t e = hx::launch_keyswitch_last_pow2(c->logn, ndig, A, map, plan, c->device, c->d_primes, c->d_tw, c->stream);
+  if (e != hipSuccess)
+    return fail(HX_ERR_DEVICE, "key-switch launch failed: %s", hipGetErrorString(e));
   return HX_OK;
 }
 
@@ -4835,11 +4909,14 @@ static int relin_core(hx_ctx* c, const uint64_t* t2e, const std::vector<int>& ow
   }
   // forward NTT of the extension rows only: D*(L+K) - L transforms, as in the reference
   uint64_t* digits_eval = c->scratch[1];
+  // each output row's last extension row is transformed inside the key switch instead (keyswitch_last_launch)
+  const bool fuse_last = !ts && ks_last_ok(c, W, all, owner, L, ndig);
+  const std::vector<int> fd = fuse_last ? ks_last_digit(owner, ndig) : std::vector<int>(nall, -1);
   {
     std::vector<std::pair<int, int>> rows;
     for (int d = 0; d < ndig; d++)
       for (int r = 0; r < nall; r++)
-        if (owner[r] != d)
+        if (owner[r] != d && fd[r] != d)
           rows.emplace_back(d * nall + r, all[r]);
     // N = 2^15: out of place, so that the two-workgroups-per-row forward kernel applies (ntt_launch); the key switch
     // reads the extension rows only, all of which are written there
@@ -4852,6 +4929,8 @@ static int relin_core(hx_ctx* c, const uint64_t* t2e, const std::vector<int>& ow
   std::vector<std::vector<int>> dprimes(ndig);
   for (int d = 0; d < ndig; d++)
     dprimes[d].assign(dig_idx + dig_off[d], dig_idx + dig_off[d + 1]);
+  if (fuse_last)
+    return keyswitch_last_launch(c, c->scratch[1], digits_eval, W, all, batch, out0, out1, t2e, owner, dprimes, ndig, t0s, t1s);
   return keyswitch_launch(c, digits_eval, W, all, batch, out0, out1, L, t2e, &owner, &dprimes, ndig,
                           t0s, t1s, ts);
 }

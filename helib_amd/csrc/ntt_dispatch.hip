@@ -1,6 +1,7 @@
 // ntt_dispatch.hip -- the row-transform entry points of ntt_kernels.hip, picking the translation unit of the ring
-// size: ntt_kernels.hip is compiled three times (-DHX_NTT_ONLY=13|14|15, in parallel), each unit exporting its
-// entry points with the suffix _L13 / _L14 / _L15 (see the top of that file).  Rings below 2^13 (the small-ring
+// size: ntt_kernels.hip is compiled per ring size (-DHX_NTT_ONLY=13|14|15, in parallel; the fused key switch as a
+// unit of its own, -DHX_NTT_PART=2), each unit exporting its entry points with the suffix _L13 / _L14 / _L15 (see the
+// top of that file).  Rings below 2^13 (the small-ring
 // kernel, one workgroup per row in LDS) are in every unit; the 2^14 one serves them.
 #include "dev_common.h"
 
@@ -49,7 +50,11 @@ namespace hx {
   E(S, launch_ntt_inv_mul_pow2,                                                                                            \
     (int logn, const uint64_t* a, const uint64_t* b, uint64_t* out, const NttRows& rows, int nrows, int batch,            \
      const PrimeDev* primes, const TW* tw_arena, hipStream_t st),                                                          \
-    (logn, a, b, out, rows, nrows, batch, primes, tw_arena, st))
+    (logn, a, b, out, rows, nrows, batch, primes, tw_arena, st))                                                           \
+  E(S, launch_keyswitch_last_pow2,                                                                                         \
+    (int logn, int nd, const KsLastArgs& A, const RowMap2& map, const KsLastPlan& plan, int device,                       \
+     const PrimeDev* primes, const TW* tw_arena, hipStream_t st),                                                          \
+    (logn, nd, A, map, plan, device, primes, tw_arena, st))
 
 // declarations of the per-size units' entry points
 #define HX_DECL(S, name, params, args) hipError_t name##_L##S params;

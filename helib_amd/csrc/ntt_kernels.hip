@@ -858,6 +858,284 @@ ntt_row_kernel(const uint64_t* in, uint64_t* out, NttRows rows, int batch,
   ntt_body<LOGN, INV>(lds, io, tw, pd);
 }
 
+// The translation units of one ring size: HX_NTT_PART=1 -- every kernel but the fused key switch below, 2 -- that one
+// alone (helib_amd/build.py compiles the two side by side); without the macro the file is the whole thing.
+#if !defined(HX_NTT_PART) || HX_NTT_PART == 2
+// =====================================================================
+// Key switch with the LAST digit transform of every output row fused in.
+// Output row j of Ctxt::keySwitchDigits sums over the digits (rns_kernels.h keyswitch_kernel); each digit that does not
+// own j contributes an extension row that the forward transform wrote and the key switch read back.  Here the
+// workgroup of (row j, element b) transforms ONE of them itself -- digit fd[j], the last one that does not own the row
+// -- exactly as ntt_row_kernel<., false, 8> would, keeps the 32 evaluation words per thread in registers, and its store
+// phase is the whole key-switch arithmetic of the row: the other digits' words, the s^2 row of the own-row rebuild,
+// the parts (1) and (s) and the 2 D key words are streamed in, out0[j] and out1[j] are written.  That extension row is
+// neither written nor read back: 16 N bytes per (row, element) less, and no accumulator has to survive a transform.
+//   * every output word is the canonical residue the two-launch route computes (exact integer arithmetic: the same
+//     128-bit sum of D products plus the accumulator through the same reduction), so the routes agree word for word;
+//   * operand words come through pinned loads and explicit vmcnt waits, as in ModDownTensorIO::store_part.  Beside the
+//     64-register coefficient file and ~35 registers of 128-bit arithmetic, 128 VGPRs leave room for about 14 operand
+//     words.  D = 2 (7 words per coefficient) requests them one coefficient AHEAD in a double buffer; D = 3 (10 words;
+//     twice that built at 128 VGPRs + 16 spilled) requests the next coefficient's words into the same registers once
+//     this one's products are summed -- they arrive under the two reductions and the stores; D = 4 (13 words: 5
+//     registers spilled even so) also splits the coefficient: the ka words are requested into the kb words' registers
+//     once the out0 sum is formed.  No form uses scratch: a spill is a vector memory operation the waits do not count;
+//   * nothing in the store loop may issue another vector memory operation (the waits count them): every uniform
+//     constant is fetched through the scalar cache before the loop.
+// The host (engine.hip relin_core) takes this route only for primes in (2^32, 2^60) -- the 128-bit lazy sums and the
+// 32-bit-reciprocal normalisation (QC::mu32) -- and when rows < L are exactly the rows some digit owns.
+// =====================================================================
+template <int ND>
+struct KsLastIO {
+  static constexpr int LOAD_BOUND = 8;   // the load of BufIOT<8>: the digit kernel's lazy words
+#ifndef HX_DIGITS_LB8
+  template <class AR>
+  static constexpr int load_bound() { return AR::PROTH ? 2 : 8; }
+#endif
+  static constexpr bool LAZY_STORE = true;
+  static constexpr bool PIPELINED = false;
+  static constexpr int DEPTH = ND <= 2 ? 2 : 1;   // coefficients in flight (see above)
+  static constexpr bool SPLIT = ND >= 4;          // the ka words as a second request per coefficient
+  struct StorePrefetch {};
+  v4i32 rin;
+  const KsLastArgs& A;
+  unsigned row, b, brow, fd;
+  int owner;
+  uint64_t q, mu63, mu64;
+  uint32_t k;
+  TW ps;            // addPrimesAndScale factor of the parts (1), (s) -- or the identity when they come scaled
+  TW pinv[ND - 1];  // P_e^-1 of the digits before the owner (own-row rebuild)
+  __device__ KsLastIO(const KsLastArgs& A_, unsigned row_, unsigned b_, unsigned brow_, unsigned fd_, unsigned bytes,
+                      const PrimeDev* pd)
+      : rin(make_rsrc(A_.dig_in + (((size_t)fd_ * (size_t)A_.nall + row_) * (size_t)A_.batch + b_) * (size_t)(bytes / 8u), bytes)),
+        A(A_), row(row_), b(b_), brow(brow_), fd(fd_), q(pd->q), mu63(pd->mu63), mu64(pd->mu64), k(pd->k)
+  {
+    ro_u64 fw = as_ro(reinterpret_cast<const uint64_t*>(A_.fix + row_));
+    constexpr unsigned PINV = offsetof(KsFix, pinv) / 8u, PSC = offsetof(KsFix, pscale) / 8u;
+    owner = (int)(int64_t)fw[0];
+    // (x 1 with the companion floor(2^64 / q) is the identity on canonical words: what a branch would skip is
+    // multiplied through instead -- a branch per coefficient fragments the schedule of the store loop)
+    ps.w = A_.scale_parts ? fw[PSC] : 1;
+    ps.wp = A_.scale_parts ? fw[PSC + 1] : mu64;
+#pragma unroll
+    for (int e = 0; e < ND - 1; e++) {
+      const bool in = e < owner;
+      pinv[e].w = in ? fw[PINV + 2 * e] : 1;
+      pinv[e].wp = in ? fw[PINV + 2 * e + 1] : mu64;
+    }
+  }
+  __device__ __forceinline__ uint64_t load(unsigned tid, unsigned c) const
+  {
+    v2i32 r = hx_buffer_load_v2(rin, (int)(tid * 8u), (int)(c * 8u), HX_NT);
+    return ((uint64_t)(uint32_t)r.y << 32) | (uint32_t)r.x;
+  }
+  template <int LOGN>
+  __device__ __forceinline__ void store_prefetch(unsigned, StorePrefetch&) const {}
+  // (loads and stores the compiler can neither move, merge nor split: ModDownIO::ld_pinned)
+  template <bool NT>
+  static __device__ __forceinline__ uint64_t ld_pinned(const v4i32& r, unsigned tid, int soff)
+  {
+    uint64_t x;
+    if constexpr (NT)
+      asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" HX_NT_ASM : "=v"(x) : "v"((int)(tid * 8u)), "s"(r), "s"(soff) : "memory");
+    else
+      asm volatile("buffer_load_dwordx2 %0, %1, %2, %3 offen" : "=v"(x) : "v"((int)(tid * 8u)), "s"(r), "s"(soff) : "memory");
+    return x;
+  }
+  static __device__ __forceinline__ void put(const v4i32& r, unsigned tid, unsigned c, uint64_t o)
+  {
+    asm volatile("buffer_store_dwordx2 %0, %1, %2, %3 offen" HX_NT_ASM : : "v"(o), "v"((int)(tid * 8u)), "s"(r), "s"((int)(c * 8u)) : "memory");
+  }
+#define HX_KV(i) "+v"(x[i])
+#define HX_KS_WAIT(NW, ...)                                                                \
+  template <int N>                                                                         \
+  static __device__ __forceinline__ void pinned_wait(uint64_t (&x)[NW])                    \
+  {                                                                                        \
+    asm volatile("s_waitcnt vmcnt(%" #NW ")" : __VA_ARGS__ : "n"(N) : "memory");           \
+  }
+  HX_KS_WAIT(4, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3))
+  HX_KS_WAIT(5, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4))
+  HX_KS_WAIT(7, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4), HX_KV(5), HX_KV(6))
+  HX_KS_WAIT(9, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4), HX_KV(5), HX_KV(6), HX_KV(7), HX_KV(8))
+  HX_KS_WAIT(8, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4), HX_KV(5), HX_KV(6), HX_KV(7))
+  HX_KS_WAIT(10, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4), HX_KV(5), HX_KV(6), HX_KV(7), HX_KV(8), HX_KV(9))
+  HX_KS_WAIT(11, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4), HX_KV(5), HX_KV(6), HX_KV(7), HX_KV(8), HX_KV(9), HX_KV(10))
+  HX_KS_WAIT(13, HX_KV(0), HX_KV(1), HX_KV(2), HX_KV(3), HX_KV(4), HX_KV(5), HX_KV(6), HX_KV(7), HX_KV(8), HX_KV(9), HX_KV(10),
+             HX_KV(11), HX_KV(12))
+#undef HX_KS_WAIT
+#undef HX_KV
+  // OWNED: a row some digit owns (rows < L): that digit's word is rebuilt from the s^2 row, and the row starts from
+  // the parts (1), (s); else a special-prime row: D - 1 digits from memory, nothing to start from.
+  // Words of one coefficient, in request order: the NMEM digits read from memory (ascending), [s^2, (1), (s)], then
+  // kb and ka of: those digits, the fused digit, [the owner].
+  template <int LOGN, class AR, int B, bool OWNED>
+  __device__ __forceinline__ void store_rows(unsigned tid, uint64_t (&v)[32], const QC& qc) const
+  {
+    constexpr int NMEM = OWNED ? ND - 2 : ND - 1, NACC = OWNED ? 3 : 0, NW = NMEM + NACC + (SPLIT ? ND : 2 * ND);
+    constexpr int KB0 = NMEM + NACC, KA0 = KB0 + ND;
+    constexpr size_t N = Geo<LOGN>::N;
+    constexpr unsigned bytes = (unsigned)N * 8u;
+    const size_t eoff = ((size_t)row * (size_t)A.batch + b) * N;       // (row, element) of a [rows][batch][N] block
+    const size_t dstride = (size_t)A.nall * (size_t)A.batch * N;       // words between two digits' blocks
+    const unsigned kstride = (unsigned)A.wrows * bytes;                // bytes between two digits' key rows
+    // memory slot s holds digit s, or s + 1 from the owner on (the fused digit is the last one or, on the rows the
+    // last digit owns, the one before it: it never lies between two memory digits)
+    v4i32 rm[NMEM > 0 ? NMEM : 1];
+    int kd[ND];   // key-row byte offset of: the memory slots, the fused digit, the owner
+#pragma unroll
+    for (int s = 0; s < NMEM; s++) {
+      const unsigned d = (OWNED && s >= owner) ? (unsigned)s + 1u : (unsigned)s;
+      rm[s] = make_rsrc(A.dig_ev + (size_t)d * dstride + eoff, bytes);
+      kd[s] = (int)(d * kstride);
+    }
+    kd[NMEM] = (int)(fd * kstride);
+    if constexpr (OWNED)
+      kd[NMEM + 1] = (int)((unsigned)owner * kstride);
+    const v4i32 rkb = make_rsrc(A.kb + (size_t)brow * N, (unsigned)(ND - 1) * kstride + bytes);
+    const v4i32 rka = make_rsrc(A.ka + (size_t)brow * N, (unsigned)(ND - 1) * kstride + bytes);
+    const v4i32 ro0 = make_rsrc(A.out0 + eoff, bytes), ro1 = make_rsrc(A.out1 + eoff, bytes);
+    // (no (s) part: the (1) row stands in for it and its product is masked away)
+    const v4i32 rown = make_rsrc(OWNED ? A.own_src + eoff : A.out0 + eoff, bytes);
+    const v4i32 ra0 = make_rsrc(OWNED ? A.acc0 + eoff : A.out0 + eoff, bytes);
+    const v4i32 ra1 = make_rsrc(OWNED ? (A.acc1 ? A.acc1 : A.acc0) + eoff : A.out0 + eoff, bytes);
+    const uint64_t m1 = A.acc1 ? ~(uint64_t)0 : 0;
+    // own-row rebuild: a memory slot before the owner takes its step, any other the identity step on a zeroed word
+    uint32_t cm[NMEM > 0 ? NMEM : 1];   // (one scalar register each: the two halves of a word take the same mask)
+#pragma unroll
+    for (int s = 0; s < NMEM; s++)
+      cm[s] = s < owner ? ~0u : 0u;
+    const uint32_t cmf = (owner == ND - 1) ? ~0u : 0u;   // the fused digit lies before the owner
+    auto masked = [](uint64_t x, uint32_t m) { return ((uint64_t)((uint32_t)(x >> 32) & m) << 32) | ((uint32_t)x & m); };
+    auto request = [&](auto I, uint64_t (&w)[NW]) {
+      constexpr int i = decltype(I)::value;
+      const int c8 = (int)(eval_const<LOGN>(i) * 8u);
+      static_for<0, NMEM>([&](auto S) { w[decltype(S)::value] = ld_pinned<true>(rm[decltype(S)::value], tid, c8); });
+      if constexpr (OWNED) {
+        w[NMEM] = ld_pinned<true>(rown, tid, c8);
+        w[NMEM + 1] = ld_pinned<true>(ra0, tid, c8);
+        w[NMEM + 2] = ld_pinned<true>(ra1, tid, c8);
+      }
+      // (key rows: default policy -- the whole batch reads them, they are what this XCD's L2 should keep)
+      static_for<0, ND>([&](auto S) { w[KB0 + decltype(S)::value] = ld_pinned<false>(rkb, tid, kd[decltype(S)::value] + c8); });
+      if constexpr (!SPLIT)
+        static_for<0, ND>([&](auto S) { w[KA0 + decltype(S)::value] = ld_pinned<false>(rka, tid, kd[decltype(S)::value] + c8); });
+    };
+    uint64_t wb[DEPTH][NW];
+    uint64_t k2[ND];   // SPLIT: the ka words
+    request(std::integral_constant<int, 0>{}, wb[0]);
+    static_for<0, 32>([&](auto II) {
+      constexpr int i = decltype(II)::value;
+      constexpr bool more = i + 1 < 32;
+      uint64_t(&w)[NW] = wb[DEPTH == 2 ? (i & 1) : 0];
+      if constexpr (DEPTH == 2) {
+        if constexpr (more)
+          request(std::integral_constant<int, i + 1>{}, wb[(i + 1) & 1]);
+        // in flight behind coefficient i's words: the two stores of coefficient i-1 and the NW loads of i+1
+        pinned_wait<(i > 0 ? 2 : 0) + (more ? NW : 0)>(w);
+      } else {
+        // (the stores of coefficient i-1 that were issued after these loads: both, or the out1 store alone)
+        pinned_wait<(i > 0 ? (SPLIT ? 1 : 2) : 0)>(w);
+      }
+      // the word ntt_row_kernel<., false, 8> would have stored: canonical (the rebuild and the 128-bit sums assume it)
+      const uint64_t xf = norm_from<B, true>(v[i], qc);
+      const unsigned c = eval_const<LOGN>(i);
+      uint64_t x[ND];   // the digit words in key order: the memory slots, the fused digit, the owner's rebuilt word
+      static_for<0, NMEM>([&](auto S) { x[decltype(S)::value] = w[decltype(S)::value]; });
+      x[NMEM] = xf;
+      u128 s0 = 0, s1 = 0;
+      if constexpr (OWNED) {
+        uint64_t own = w[NMEM];
+        static_for<0, NMEM>([&](auto S) {
+          constexpr int s = decltype(S)::value;
+          own = mul_shoup(own + q - masked(w[s], cm[s]), pinv[s].w, pinv[s].wp, q);
+        });
+        x[NMEM + 1] = mul_shoup(own + q - masked(xf, cmf), pinv[ND - 2].w, pinv[ND - 2].wp, q);
+        s0 = mul_shoup(w[NMEM + 1], ps.w, ps.wp, q);
+        s1 = mul_shoup(w[NMEM + 2], ps.w, ps.wp, q) & m1;
+      }
+      // (D q^2 + q stays far inside the reduction's domain, S < 8 q^2, for D <= 4)
+      static_for<0, ND>([&](auto S) { s0 += (u128)x[decltype(S)::value] * w[KB0 + decltype(S)::value]; });
+      if constexpr (SPLIT) {
+        const int c8 = (int)(c * 8u);
+        static_for<0, ND>([&](auto S) { k2[decltype(S)::value] = ld_pinned<false>(rka, tid, kd[decltype(S)::value] + c8); });
+        put(ro0, tid, c, tensor_red128(s0, q, mu63, k));
+        pinned_wait<1>(k2);   // (behind them: the out0 store)
+        static_for<0, ND>([&](auto S) { s1 += (u128)x[decltype(S)::value] * k2[decltype(S)::value]; });
+        if constexpr (more)
+          request(std::integral_constant<int, i + 1>{}, wb[0]);
+        put(ro1, tid, c, tensor_red128(s1, q, mu63, k));
+      } else {
+        static_for<0, ND>([&](auto S) { s1 += (u128)x[decltype(S)::value] * w[KA0 + decltype(S)::value]; });
+        if constexpr (DEPTH == 1 && more)
+          request(std::integral_constant<int, i + 1>{}, wb[0]);   // (this coefficient's words are consumed)
+        put(ro0, tid, c, tensor_red128(s0, q, mu63, k));
+        put(ro1, tid, c, tensor_red128(s1, q, mu63, k));
+      }
+      HX_SCHED_FENCE();
+    });
+  }
+  template <int LOGN, class AR, int B, bool EST>
+  __device__ __forceinline__ void store_all(unsigned tid, uint64_t (&v)[32], const QC& qc, StorePrefetch&) const
+  {
+    // (EST = false is a prime below 2^32: the host never sends one here, and the instantiation stays empty -- a
+    // second copy of the two loops per arithmetic would double this kernel's code for rows that do not exist)
+    if constexpr (EST) {
+      if (owner >= 0)   // (wave-uniform: one of the two loops runs)
+        store_rows<LOGN, AR, B, true>(tid, v, qc);
+      else
+        store_rows<LOGN, AR, B, false>(tid, v, qc);
+    }
+  }
+  __device__ __forceinline__ TW last_tw(TW def, int) const { return def; }
+  __device__ __forceinline__ TWM last_tw(TWM def, int) const { return def; }
+};
+template <int LOGN, int ND>
+__global__ void __launch_bounds__(Geo<LOGN>::T, HX_NTT_MINWAVES(LOGN))
+ntt_keyswitch_last_kernel(KsLastArgs A, RowMap2 map, KsLastPlan plan, const PrimeDev* __restrict__ primes,
+                          const TW* __restrict__ tw_arena)
+{
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+  const KsWork W = ks_last_work(blockIdx.x, (unsigned)A.nall, (unsigned)A.batch);
+  const PrimeDev* pd = primes + uniform_u16(map.p, W.row);
+  const KsLastIO<ND> io(A, W.row, W.b, uniform_u16(map.brow, W.row), uniform_u16(plan.fd, W.row), (unsigned)Geo<LOGN>::N * 8u, pd);
+  ntt_body<LOGN, false>(lds, io, tw_arena + pd->tw_fwd_off, pd);
+}
+template <int LOGN, int ND>
+static hipError_t launch_ks_last(const KsLastArgs& A, const RowMap2& map, const KsLastPlan& plan, int device,
+                                 const PrimeDev* primes, const TW* tw_arena, hipStream_t st)
+{
+  constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
+  hipError_t e = hxp::dyn_lds((const void*)ntt_keyswitch_last_kernel<LOGN, ND>, (int)lds_bytes, device);
+  if (e != hipSuccess)
+    return e;
+  HX_LAUNCH((ntt_keyswitch_last_kernel<LOGN, ND>), dim3((unsigned)A.nall * (unsigned)A.batch), dim3(Geo<LOGN>::T), lds_bytes,
+            st, A, map, plan, primes, tw_arena);
+  return hipGetLastError();
+}
+template <int LOGN>
+static hipError_t launch_ks_last_nd(int nd, const KsLastArgs& A, const RowMap2& map, const KsLastPlan& plan, int device,
+                                    const PrimeDev* primes, const TW* tw_arena, hipStream_t st)
+{
+  switch (nd) {
+    case 2: return launch_ks_last<LOGN, 2>(A, map, plan, device, primes, tw_arena, st);
+    case 3: return launch_ks_last<LOGN, 3>(A, map, plan, device, primes, tw_arena, st);
+    case 4: return launch_ks_last<LOGN, 4>(A, map, plan, device, primes, tw_arena, st);
+  }
+  return hipErrorInvalidValue;
+}
+// nd = 2, 3, 4 digits; `device`: the context's (the dynamic-LDS limit is raised once per device and kernel)
+hipError_t HX_ENTRY(launch_keyswitch_last_pow2)(int logn, int nd, const KsLastArgs& A, const RowMap2& map, const KsLastPlan& plan,
+                                                int device, const PrimeDev* primes, const TW* tw_arena, hipStream_t st)
+{
+  switch (logn) {
+    HX_SZ(13, launch_ks_last_nd<13>(nd, A, map, plan, device, primes, tw_arena, st))
+    HX_SZ(14, launch_ks_last_nd<14>(nd, A, map, plan, device, primes, tw_arena, st))
+    HX_SZ(15, launch_ks_last_nd<15>(nd, A, map, plan, device, primes, tw_arena, st))
+  }
+  return hipErrorInvalidValue;
+}
+#endif   // HX_NTT_PART 2
+
+#if !defined(HX_NTT_PART) || HX_NTT_PART == 1
 // inverse transform of a(X) * b(X) given in evaluation form: the s^2 part of a tensor product (a1 b1) goes
 // straight from the operands' rows to its coefficient rows (hx_mul_relin: toPoly side of breakIntoDigits)
 // PROTH (rows of Proth-form primes, ntt_core.h ArProth): the 128-bit product goes through mont_redc128 alone -- two
@@ -943,13 +1221,9 @@ static hipError_t launch_inv_mul(const uint64_t* a, const uint64_t* b, uint64_t*
                                  int batch, const PrimeDev* primes, const TW* tw_arena, hipStream_t st)
 {
   constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
-  bool attr_set = false;   // (hxp::dyn_lds is idempotent per device)
-  if (!attr_set) {
-    hipError_t e = hxp::dyn_lds((const void*)ntt_inv_mul_kernel<LOGN>, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    attr_set = true;
-  }
+  hipError_t e = hxp::dyn_lds((const void*)ntt_inv_mul_kernel<LOGN>, (int)lds_bytes);
+  if (e != hipSuccess)
+    return e;
   HX_LAUNCH((ntt_inv_mul_kernel<LOGN>), dim3((unsigned)nrows * (unsigned)batch), dim3(Geo<LOGN>::T), lds_bytes, st, a, b,
             out, rows, batch, primes, tw_arena);
   return hipGetLastError();
@@ -977,14 +1251,9 @@ static hipError_t launch_one(const uint64_t* in, uint64_t* out, const NttRows& r
 #else
   static const size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
 #endif
-  bool attr_set = false;   // (hxp::dyn_lds is idempotent per device)
-  if (!attr_set) {
-    hipError_t e = hxp::dyn_lds((const void*)ntt_row_kernel<LOGN, INV, LB>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    attr_set = true;
-  }
+  hipError_t e = hxp::dyn_lds((const void*)ntt_row_kernel<LOGN, INV, LB>, (int)lds_bytes);
+  if (e != hipSuccess)
+    return e;
   dim3 grid((unsigned)nrows * (unsigned)batch), block(Geo<LOGN>::T);
   HX_LAUNCH((ntt_row_kernel<LOGN, INV, LB>), grid, block, lds_bytes, st, in, out, rows, batch,
                      primes, tw_arena);
@@ -995,22 +1264,14 @@ template <int LOGN>
 static hipError_t moddown_attrs()
 {
   constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
-  bool attr_set = false;   // (hxp::dyn_lds is idempotent per device)
-  if (!attr_set) {
-    hipError_t e = hxp::dyn_lds((const void*)ntt_moddown_prep_kernel<LOGN>, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hxp::dyn_lds((const void*)ntt_moddown_prep_multi_kernel<LOGN>, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hxp::dyn_lds((const void*)ntt_moddown_apply_kernel<LOGN, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hxp::dyn_lds((const void*)ntt_moddown_apply_kernel<LOGN, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    attr_set = true;
-  }
-  return hipSuccess;
+  hipError_t e = hxp::dyn_lds((const void*)ntt_moddown_prep_kernel<LOGN>, (int)lds_bytes);
+  if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_prep_multi_kernel<LOGN>, (int)lds_bytes);
+  if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_apply_kernel<LOGN, false>, (int)lds_bytes);
+  if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_apply_kernel<LOGN, true>, (int)lds_bytes);
+  return e;
 }
 static unsigned moddown_apply_grid(unsigned npoly, unsigned nkeep, unsigned batch)
 {
@@ -1064,22 +1325,14 @@ template <int LOGN>
 static hipError_t moddown_tensor_attrs()
 {
   constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
-  bool attr_set = false;   // (hxp::dyn_lds is idempotent per device)
-  if (!attr_set) {
-    hipError_t e = hxp::dyn_lds((const void*)ntt_moddown_prep_tensor_kernel<LOGN>, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hxp::dyn_lds((const void*)ntt_moddown_prep_multi_tensor_kernel<LOGN>, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hxp::dyn_lds((const void*)ntt_moddown_apply_tensor_kernel<LOGN, false>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e == hipSuccess)
-      e = hxp::dyn_lds((const void*)ntt_moddown_apply_tensor_kernel<LOGN, true>,
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    attr_set = true;
-  }
-  return hipSuccess;
+  hipError_t e = hxp::dyn_lds((const void*)ntt_moddown_prep_tensor_kernel<LOGN>, (int)lds_bytes);
+  if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_prep_multi_tensor_kernel<LOGN>, (int)lds_bytes);
+  if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_apply_tensor_kernel<LOGN, false>, (int)lds_bytes);
+  if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_apply_tensor_kernel<LOGN, true>, (int)lds_bytes);
+  return e;
 }
 template <int LOGN>
 static hipError_t launch_moddown_tensor(const TensorSrc& T, const PolyBases& outs, int drop_row, int drop_prime,
@@ -1448,5 +1701,7 @@ hipError_t HX_ENTRY(launch_ntt_pow2)(int logn, bool inverse, const uint64_t* in,
   }
   return hipErrorInvalidValue;
 }
+
+#endif   // HX_NTT_PART 1
 
 }  // namespace hx

@@ -16,6 +16,7 @@
 #include <cxxabi.h>
 #include <algorithm>
 #include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <map>
@@ -26,24 +27,53 @@
 
 namespace hxp {
 
-// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: raise it once per (device, kernel),
-// under a lock -- a process-wide `static bool` (rounds 1-5) left a second context on another device with the default
-// 64 KiB limit (its first large-LDS launch failed) and let two contexts' threads race on the flag.
-inline hipError_t dyn_lds(const void* kern, int bytes)
+// hipFuncAttributeMaxDynamicSharedMemorySize is a per-DEVICE property of a kernel: raise it once per (device, kernel)
+// -- a process-wide `static bool` (rounds 1-5) left a second context on another device with the default 64 KiB limit
+// (its first large-LDS launch failed) and let two contexts' threads race on the flag.
+// The registry is a fixed open-addressed table of atomics keyed on (device, kernel): the steady state -- every launch
+// after a kernel's first on a device -- is one probe of two loads, no lock (a mutex and a std::map lookup
+// sat on every row-kernel launch).  `device`: the context's own (hx_ctx::device, the current device under CTX_ENTER);
+// call sites without a context at hand leave it out and the current device is asked for.
+inline hipError_t dyn_lds(const void* kern, int bytes, int device = -1)
 {
-  static std::mutex mu;
-  static std::map<std::pair<int, const void*>, int> done;   // (device, kernel) -> bytes granted
-  int dev = 0;
-  hipError_t e = hipGetDevice(&dev);
-  if (e != hipSuccess)
-    return e;
+  struct Slot {
+    std::atomic<uintptr_t> key{0};   // kernel address | (device + 1) << 48; 0: free
+    std::atomic<int> bytes{0};       // limit granted (published before the key)
+  };
+  constexpr unsigned SLOTS = 4096;   // (a few hundred kernels x the devices of one box)
+  static Slot tab[SLOTS];
+  static std::mutex mu;              // taken by the first launch of a kernel on a device only
+  if (device < 0) {
+    hipError_t e = hipGetDevice(&device);
+    if (e != hipSuccess)
+      return e;
+  }
+  const uintptr_t key = ((uintptr_t)kern & (((uintptr_t)1 << 48) - 1)) | ((uintptr_t)(device + 1) << 48);
+  const unsigned h0 = (unsigned)((key * 0x9E3779B97F4A7C15ull) >> 52);   // 12 bits
+  for (unsigned i = 0, h = h0; i < SLOTS; i++, h = (h + 1) & (SLOTS - 1)) {
+    const uintptr_t k = tab[h].key.load(std::memory_order_acquire);
+    if (k == key) {
+      if (tab[h].bytes.load(std::memory_order_acquire) >= bytes)
+        return hipSuccess;
+      break;
+    }
+    if (k == 0)
+      break;
+  }
   std::lock_guard<std::mutex> lk(mu);
-  auto it = done.find({dev, kern});
-  if (it != done.end() && it->second >= bytes)
+  Slot* s = nullptr;
+  for (unsigned i = 0, h = h0; i < SLOTS && !s; i++, h = (h + 1) & (SLOTS - 1)) {
+    const uintptr_t k = tab[h].key.load(std::memory_order_relaxed);
+    if (k == key || k == 0)
+      s = &tab[h];
+  }
+  if (s && s->key.load(std::memory_order_relaxed) == key && s->bytes.load(std::memory_order_relaxed) >= bytes)
     return hipSuccess;
-  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
-  if (e == hipSuccess)
-    done[{dev, kern}] = bytes;
+  const hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess && s) {   // (a full table: the attribute is set again at every launch, which is still correct)
+    s->bytes.store(bytes, std::memory_order_release);
+    s->key.store(key, std::memory_order_release);
+  }
   return e;
 }
 // (the signature of hipFuncSetAttribute, for the call sites that were written against it)

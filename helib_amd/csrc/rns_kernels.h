@@ -237,18 +237,13 @@ __device__ __forceinline__ uint64_t red128_q8_lazy(u128 S, uint64_t q, uint64_t 
 #ifndef HX_BRK_WAVES
 #define HX_BRK_WAVES 7
 #endif
-constexpr int KS_MAXD = 8;
 // (occupancy A/B, round 2: capped at 64 VGPRs / 8 waves per SIMD the kernel spills 60 bytes per lane
 // inside its loop and the fixed-level multiply drops from 66 k to 52 k mult/s; at 72 VGPRs / 7 waves
 // it is the same as uncapped -- 78 VGPRs, 6 waves: gpurun_out/variants.log, profiles/r02_variants_keyswitch_waves.txt)
 #ifndef HX_KS_WAVES
 #define HX_KS_WAVES
 #endif
-struct KsFix {
-  int64_t owner;        // digit owning this row, -1 for special primes
-  TW pinv[KS_MAXD];     // P_e^-1 mod q_row for e < owner
-  TW pscale;            // product of the special primes mod q_row (addPrimesAndScale factor)
-};
+// (struct KsFix, KS_MAXD: dev_common.h -- the fused last-digit kernel of ntt_kernels.hip reads the same table)
 
 // ND: compile-time digit count (2..4: every digit's words and key words are requested before the first is used
 // -- the run-time loop of ND = 0 waits for each digit's loads in turn, one or two 16-byte loads in flight per lane)

@@ -34,6 +34,9 @@ struct Switches {
   // fused ciphertext-level paths
   bool no_tensor_multi = false;  // HX_NO_TENSOR_MULTI=1 tensor product + several-primes mod-switch as two steps
   bool no_mulrelin_fuse = false; // HX_NO_MULRELIN_FUSE=1 hx_mul_relin with a tensor pass
+  bool no_ks_last_fuse = false;  // HX_NO_KS_LAST_FUSE=1 relinearisation: every extension row through ntt_row_kernel<., false, 8> and the
+                                 //                      key switch as keyswitch_kernel<D>, instead of each output row's last digit transform
+                                 //                      fused into the key switch (ntt_keyswitch_last_kernel)
   // row transforms (ntt_core.h)
   bool half15 = false;           // HX_HALF15=1          N = 2^15 forward rows (out of place) as two 2^14-point workgroups per row: measured 3-4 % SLOWER
                                  //                      than the one-workgroup kernel (profiles/r06_ab_half_row_forward_2p15.json); kept as a probe
@@ -80,6 +83,7 @@ inline Switches read()
   s.half15 = on("HX_HALF15");
   s.no_tensor_multi = on("HX_NO_TENSOR_MULTI");
   s.no_mulrelin_fuse = on("HX_NO_MULRELIN_FUSE");
+  s.no_ks_last_fuse = on("HX_NO_KS_LAST_FUSE");
   s.no_proth = on("HX_NO_PROTH");
   s.blue_old = on("HX_BLUE_OLD");
   s.no_pfa = on("HX_NO_PFA") || s.blue_old;

@@ -66,4 +66,21 @@ HXW MdWork md_work(unsigned block, unsigned nkeep, unsigned npb)
   return w;
 }
 
+// Work map of the fused last-digit transform + key switch (ntt_keyswitch_last_kernel): one workgroup per (output row,
+// batch element).  The `batch` workgroups of one row all read that row's 2 D key rows and its twiddle table, so they
+// must follow each other in ONE XCD's dispatch order: the 1-D remap above over the row-major (row, element) space
+// gives every XCD one contiguous range of it -- nrows / 8 rows (2.75 at the timed 22 x 128), at most two rows of
+// which are cut by a chunk boundary -- and inside the range the row changes every `batch` slots.
+struct KsWork {
+  unsigned row, b;
+};
+HXW KsWork ks_last_work(unsigned block, unsigned nrows, unsigned batch)
+{
+  const unsigned w = xcd_remap_id(block, nrows * batch);
+  KsWork k;
+  k.row = w / batch;
+  k.b = w % batch;
+  return k;
+}
+
 }  // namespace hx

@@ -207,6 +207,9 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
  *   HX_NO_MASK_SPLIT                          hx_mask_split as hx_poly_copy + hx_mul + hx_sub per part
  *   HX_NO_TENSOR_MULTI, HX_NO_MULRELIN_FUSE   tensor product as a pass of its own in front of the several-primes
  *                                            mod-switch / inside hx_mul_relin
+ *   HX_NO_KS_LAST_FUSE                        relinearisation: every extension row transformed by the row kernel and the key
+ *                                            switch as a launch of its own, instead of each output row's last digit transform
+ *                                            fused into the key switch
  *   HX_NO_PROTH                               row transforms: Shoup butterflies on every row (by default rows of primes
  *                                            q = 1 mod 2^32 -- every chain prime of the benchmarks -- run the Proth-form ones)
  *   HX_NO_PROTH_RNS                           exact-RNS kernels: Barrett / Shoup products on Proth-form primes too (by default
