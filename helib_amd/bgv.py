@@ -23,9 +23,11 @@ ciphertexts and come back out.
                       DESIGN 3.9d); the words and the bookkeeping (lnNoise, primeSet, intFactor, ptxtSpace) are the same
                       either way, fused=None follows EncryptedArray.fuseMaskSplit
   totalSums / runningSums                     src/EncryptedArray.cpp:695-736
+  matrix products     helib_amd.bgv_matmul: MatMul1DExec / MatMulFullExec over rotate1D, with the diagonals read out of a
+                      device-resident matrix (DeviceEncoder.matrix / encodeDiagonals: hx_bgv_encode_diagonals)
 
-Out of scope: d > 1 (slots in GF(p^d)) and p^r with r > 1 -- refused with HX_ERR_UNSUPPORTED; the matrix products
-(MatMul1D / MatMulFull) for BGV.  Nothing here imports oracle/."""
+Out of scope: d > 1 (slots in GF(p^d)) and p^r with r > 1 -- refused with HX_ERR_UNSUPPORTED.  Nothing here imports
+oracle/."""
 import collections
 import math
 
@@ -52,6 +54,21 @@ class DeviceEncoder:
 
     def encode(self, v, mul, idx, coeffs=False):
         return capi.bgvEncode(self.table, v, idx, mul, coeffs=coeffs)
+
+    max_batch = 64      # diagonals per encodeDiagonals call: the scratch is max_batch transforms mod p
+
+    def matrix(self, a, dim=-1):
+        """a plaintext matrix on the device: [phi(m), phi(m)] by slot (dim = -1) or [D, D] by the coordinate in
+        dimension dim"""
+        return capi.BgvMatrix(self.table, a, dim)
+
+    def encodeDiagonals(self, matrix, diags, idx=None, coeffs=False):
+        """diags: [(off, rot_dim, rot_amt)] -> (DoubleCRT batch len(diags) over idx, zzX or None, non-zero flags);
+        idx = None: the flags alone"""
+        return capi.bgvEncodeDiagonals(self.table, matrix, diags, idx, coeffs=coeffs)
+
+    def split(self, poly):
+        return capi.splitBatch(poly)
 
     def embed(self, coeffs):
         return capi.bgvEmbed(self.table, coeffs)

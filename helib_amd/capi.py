@@ -61,6 +61,7 @@ SYMBOLS = [
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
+    "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
 ]
 
 
@@ -159,6 +160,8 @@ def lib():
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
             "hx_bgv_decode": [vp, vp, u64, vp],
             "hx_bgv_embed": [vp, vp, ip, vp],
+            "hx_bgv_matrix_create": [vp, vp, ip, ip, ip, vp], "hx_bgv_matrix_destroy": [vp],
+            "hx_bgv_encode_diagonals": [vp, vp, vp, ip, vp, vp, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -728,6 +731,61 @@ def bgvEmbed(table, f):
     out = np.zeros_like(f)
     _chk(lib().hx_bgv_embed(table.h, _p(f), f.shape[0], _p(out)))
     return out
+
+
+class BgvMatrix:
+    """A plaintext matrix on the device (hx_bgv_matrix): a[phi(m), phi(m)] indexed by slot for dim = -1, a[D, D] indexed
+    by the coordinate in dimension dim otherwise (D = ords[dim]).  Any int64; the entries count mod p."""
+
+    def __init__(self, table, a, dim=-1):
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.int64))
+        if a.ndim != 2:
+            raise InvalidArgument(HX_ERR_INVALID, "a matrix has two axes")
+        self.table, self.dim, self.shape = table, int(dim), a.shape
+        self.h = C.c_void_p()
+        _chk(lib().hx_bgv_matrix_create(table.h, _p(a), a.shape[0], a.shape[1], self.dim, C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().hx_bgv_matrix_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+# hx_bgv_diag: off[8], rot_dim, rot_amt
+BGV_DIAG_WORDS = 10
+
+
+def bgvDiags(diags):
+    """[(off, rot_dim, rot_amt)] -> the int32 [n, 10] array of hx_bgv_diag; off is a sequence of at most 8 offsets, one
+    per dimension"""
+    d = np.zeros((len(diags), BGV_DIAG_WORDS), dtype=np.int32)
+    for k, (off, rot_dim, rot_amt) in enumerate(diags):
+        d[k, :len(off)] = off
+        d[k, 8], d[k, 9] = rot_dim, rot_amt
+    return d
+
+
+def bgvEncodeDiagonals(table, matrix, diags, idx=None, out=None, coeffs=False):
+    """The diagonals `diags` ([(off, rot_dim, rot_amt)] or the array of bgvDiags) of a BgvMatrix, encoded on the device
+    (hx_bgv_encode_diagonals): -> (DoubleCRT of batch len(diags) over the prime indices idx, int64 coefficients
+    [n, phi(m)] or None, bool non-zero flags [n]).  idx = None: the flags alone, (None, None, flags).  out: a DoubleCRT
+    to write into instead of a new one."""
+    d = np.ascontiguousarray(diags, dtype=np.int32) if isinstance(diags, np.ndarray) else bgvDiags(diags)
+    assert d.ndim == 2 and d.shape[1] == BGV_DIAG_WORDS, d.shape
+    n, ctx = d.shape[0], table.context
+    if out is None and idx is not None:
+        out = DoubleCRT(ctx, list(idx), n, zero=False)
+    cf = np.zeros((n, ctx.phim), dtype=np.int64) if coeffs else None
+    nz = np.zeros(max(n, 1), dtype=np.int32)
+    _chk(lib().hx_bgv_encode_diagonals(table.h, matrix.h, _p(d) if n else None, n, out.h if out is not None else None,
+                                       _p(cf) if coeffs else None, _p(nz)))
+    return out, cf, nz[:n] != 0
 
 
 def mulAddMany(out0, out1, consts, in0, in1, accumulate=True):

@@ -5,6 +5,8 @@
 // itself is the engine's (a side context holding p); the kernels here are the glue around it, all streaming:
 //   bgv_scatter_kernel  slots -> row order, reduced mod p      reads 8 B/slot (random inside one row) + 4 B index,
 //                                                              writes 8 B/word coalesced
+//   bgv_diag_scatter_kernel  the same for a diagonal of a device-resident matrix: 4 B index + 8 B matrix word per word
+//                                                              (one word per 128 B line at worst), writes 8 B/word coalesced
 //   bgv_lift_kernel     coefficients mod p -> balanced(mul * h mod p) modulo every prime of the output
 //                                                              reads 8 B/word once, writes 8 L B/word (+ 8 for the zzX)
 //   bgv_redmul_kernel   signed words -> (w mod p) * f mod p    reads 8, writes 8 B/word
@@ -52,6 +54,69 @@ bgv_scatter_kernel(const int64_t* __restrict__ slots, uint32_t nslots, const uin
     const size_t b = i / N;
     const uint32_t s = row2slot[i - b * N];
     rows[i] = s < nslots ? bgv_red_signed(slots[b * nslots + s], p, mu) : 0;
+  }
+}
+
+// The hypercube of the slots, by value: slot s has coordinate (s / stride[i]) % ord[i] in dimension i (the last
+// dimension fastest).  dim = -1: the matrix is phi(m) x phi(m), indexed by slot; dim = i: ord[i] x ord[i], indexed by
+// the coordinate in dimension i.
+struct BgvDiagGeom {
+  int32_t nd, dim;
+  uint32_t ord[8], stride[8];
+  uint32_t cols;
+};
+// one diagonal (hx_bgv_diag with off[i] and rot_amt brought into [0, ord) by the host)
+struct BgvDiag {
+  int32_t off[8];
+  int32_t rot_dim, rot_amt;
+};
+
+// rows[t][j] = A[.] mod p, the slot row2slot[j] of diagonal t read straight out of the matrix (MatMul1D's
+// processDiagonal1 / MatMulFullHelper::processDiagonal, then plaintextAutomorph, src/matmul.cpp:449-504, 1998-2024,
+// 375-389): with c the coordinates of the slot, c[rot_dim] -= rot_amt gives the slot s0 the value comes from,
+//   full matrix    A[r, s0],  r the slot with coordinates c_i(s0) - off[i]
+//   dimension dim  A[c_dim(s0) - off[dim], c_dim(s0)]
+// all mod the orders.  One thread per word; rows = nullptr only raises the flags.  nz[t] |= 1 where a word is non-zero
+// (a vector atomic, skipped once the flag is seen set).  Per word: 4 B index + 8 B matrix word, one per 128 B line in
+// the worst case, + 8 B coalesced store; the descriptors are 40 B per diagonal, cached.
+__global__ void __launch_bounds__(256)
+bgv_diag_scatter_kernel(const int64_t* __restrict__ A, BgvDiagGeom g, const BgvDiag* __restrict__ diags,
+                        const uint32_t* __restrict__ row2slot, uint32_t N, size_t words, uint64_t p, uint64_t mu,
+                        uint64_t* __restrict__ rows, uint32_t* nz)
+{
+  const size_t stride = (size_t)gridDim.x * blockDim.x;
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < words; i += stride) {
+    const size_t t = i / N;
+    const uint32_t s = row2slot[i - t * N];
+    uint64_t w = 0;
+    if (s < N) {
+      const BgvDiag* d = diags + t;
+      const int32_t rot_dim = d->rot_dim;
+      const uint32_t rot_amt = (uint32_t)d->rot_amt;
+      size_t s0 = 0, r = 0, cd = 0, rd = 0;
+      for (int k = 0; k < g.nd; k++) {
+        const uint32_t o = g.ord[k];
+        uint32_t c = (s / g.stride[k]) % o;
+        if (k == rot_dim) {
+          c += o - rot_amt;
+          c = c >= o ? c - o : c;
+        }
+        uint32_t rr = c + o - (uint32_t)d->off[k];
+        rr = rr >= o ? rr - o : rr;
+        s0 += (size_t)c * g.stride[k];
+        r += (size_t)rr * g.stride[k];
+        if (k == g.dim) {
+          cd = c;
+          rd = rr;
+        }
+      }
+      const size_t at = g.dim < 0 ? r * g.cols + s0 : rd * g.cols + cd;
+      w = bgv_red_signed(A[at], p, mu);
+    }
+    if (rows)
+      rows[i] = w;
+    if (w && __atomic_load_n(nz + t, __ATOMIC_RELAXED) == 0)
+      atomicOr(nz + t, 1u);
   }
 }
 

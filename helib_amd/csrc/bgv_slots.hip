@@ -334,6 +334,92 @@ extern "C" int hx_bgv_slots_info(const hx_bgv_slots* t, uint64_t* p, uint64_t* r
   return HX_OK;
 }
 
+namespace {
+
+// What hx_bgv_encode and hx_bgv_encode_diagonals share.  check: the output's shape.  open: the caller's context, the
+// prime table (buf[1]) and the side poly whose rows the caller's scatter kernel fills.  finish: the inverse transform
+// mod p (CRT_reconstruct: the H with the given values at the roots), the lift, the forward transforms, the zzX.
+struct Encode {
+  hx_bgv_slots* t;
+  hx_poly* out;
+  int batch, nrows = 0;
+  size_t words = 0;
+  Enter E;
+  hx_poly* sp = nullptr;
+  hipStream_t st = nullptr;
+  std::vector<ulonglong2> qm;
+  ~Encode()
+  {
+    if (st)
+      (void)hipStreamSynchronize(st);   // no copy still reads a host buffer, no kernel a temporary
+    if (sp)
+      hx_poly_destroy(sp);
+  }
+  int check()
+  {
+    if (!out)
+      return HX_OK;
+    if (hxi::poly_ctx(out) != t->ctx)
+      return err(HX_ERR_INVALID, "the output poly belongs to another context than the slot table");
+    int pb = 0;
+    RC(hx_poly_shape(out, &pb, &nrows, nullptr));
+    if (pb != batch)
+      return err(HX_ERR_INVALID, "output batch %d != %d", pb, batch);
+    if (nrows > hx::BGV_MAXPRIMES)
+      return err(HX_ERR_UNSUPPORTED, "more than %d primes", hx::BGV_MAXPRIMES);
+    return HX_OK;
+  }
+  int open(const char* what, bool coeffs, uint64_t** h)
+  {
+    RC(E.open(t, what));
+    std::vector<int> idx(nrows > 0 ? nrows : 1);
+    if (out)
+      RC(hx_poly_primes(out, idx.data()));
+    qm.resize(nrows > 0 ? nrows : 1);
+    for (int r = 0; r < nrows; r++) {
+      uint64_t q;
+      RC(hx_ctx_prime(t->ctx, idx[r], &q, nullptr));
+      qm[r] = make_ulonglong2(q, (uint64_t)(((hxh::u128)1 << 64) / q));
+    }
+    RC(side_poly(t, batch, &sp));
+    st = E.v.stream;
+    words = (size_t)batch * t->N;
+    RC(ensure_buf(t, st, 1, sizeof(ulonglong2) * qm.size()));
+    if (coeffs)
+      RC(ensure_buf(t, st, 2, words * 8));
+    CK(hipMemcpyAsync(t->buf[1], qm.data(), sizeof(ulonglong2) * qm.size(), hipMemcpyHostToDevice, st));
+    return hxi::poly_rows_write(sp, h);
+  }
+  int finish(uint64_t mul, int64_t* coeffs_out)
+  {
+    const uint64_t p = t->p;
+    RC(hx_ntt_inverse(sp));
+    const uint64_t* hc = hxi::poly_rows_read(sp);
+    uint64_t* rows = nullptr;
+    if (nrows > 0)
+      RC(hxi::poly_rows_write(out, &rows));
+    int64_t* d_coeffs = coeffs_out ? (int64_t*)t->buf[2] : nullptr;
+    if (nrows > 0 || d_coeffs) {
+      const uint64_t muls = hxh::shoup(mul, p);
+      if (words % 2 == 0 && aligned16(hc) && aligned16(rows) && aligned16(d_coeffs))
+        HX_LAUNCH(hx::bgv_lift_kernel<2>, dim3(blocks_for(words / 2)), dim3(256), 0, st, hc, words, p, mul, muls,
+                  (const ulonglong2*)t->buf[1], nrows, rows, d_coeffs);
+      else
+        HX_LAUNCH(hx::bgv_lift_kernel<1>, dim3(blocks_for(words)), dim3(256), 0, st, hc, words, p, mul, muls,
+                  (const ulonglong2*)t->buf[1], nrows, rows, d_coeffs);
+      CK(hipGetLastError());
+    }
+    if (nrows > 0)
+      RC(hx_ntt_forward(out));
+    if (coeffs_out)
+      CK(hipMemcpyAsync(coeffs_out, d_coeffs, words * 8, hipMemcpyDeviceToHost, st));
+    CK(hipStreamSynchronize(st));
+    return HX_OK;
+  }
+};
+
+}  // namespace
+
 extern "C" int hx_bgv_encode(const hx_bgv_slots* tc, const int64_t* slots, int batch, int nslots, uint64_t mul, hx_poly* out,
                              int64_t* coeffs_out)
 {
@@ -345,63 +431,136 @@ extern "C" int hx_bgv_encode(const hx_bgv_slots* tc, const int64_t* slots, int b
   const uint32_t N = t->N;
   if (batch < 1 || nslots < 0 || (uint32_t)nslots > N)
     return err(HX_ERR_INVALID, "bad batch / slot count (batch %d, %d slots of at most %u)", batch, nslots, N);
-  int pb = 0, nrows = 0;
-  RC(hx_poly_shape(out, &pb, &nrows, nullptr));
-  if (pb != batch)
-    return err(HX_ERR_INVALID, "output batch %d != %d", pb, batch);
-  if (nrows > hx::BGV_MAXPRIMES)
-    return err(HX_ERR_UNSUPPORTED, "more than %d primes", hx::BGV_MAXPRIMES);
-  Enter E;
-  RC(E.open(t, "hx_bgv_encode"));
-  std::vector<int> idx(nrows > 0 ? nrows : 1);
-  RC(hx_poly_primes(out, idx.data()));
-  std::vector<ulonglong2> qm(nrows > 0 ? nrows : 1);
-  for (int r = 0; r < nrows; r++) {
-    uint64_t q;
-    RC(hx_ctx_prime(t->ctx, idx[r], &q, nullptr));
-    qm[r] = make_ulonglong2(q, (uint64_t)(((hxh::u128)1 << 64) / q));
-  }
+  Encode e{t, out, batch};
+  RC(e.check());
+  uint64_t* h;
+  RC(e.open("hx_bgv_encode", coeffs_out != nullptr, &h));
+  const hipStream_t st = e.st;
   const uint64_t p = t->p;
-  mul %= p;
-  const hipStream_t st = E.v.stream;
-  hx_poly* sp = nullptr;
-  RC(side_poly(t, batch, &sp));
-  Drop drop{sp};
-  DrainOnExit drain{st};
-  const size_t words = (size_t)batch * N, vbytes = (size_t)batch * nslots * 8;
+  const size_t vbytes = (size_t)batch * nslots * 8;
   RC(ensure_buf(t, st, 0, std::max<size_t>(vbytes, 16)));
-  RC(ensure_buf(t, st, 1, sizeof(ulonglong2) * qm.size()));
-  if (coeffs_out)
-    RC(ensure_buf(t, st, 2, words * 8));
   if (vbytes)
     CK(hipMemcpyAsync(t->buf[0], slots, vbytes, hipMemcpyHostToDevice, st));
-  CK(hipMemcpyAsync(t->buf[1], qm.data(), sizeof(ulonglong2) * qm.size(), hipMemcpyHostToDevice, st));
-  uint64_t* h;
-  RC(hxi::poly_rows_write(sp, &h));
-  HX_LAUNCH(hx::bgv_scatter_kernel, dim3(blocks_for(words)), dim3(256), 0, st, (const int64_t*)t->buf[0], (uint32_t)nslots,
-            t->d_row2slot, N, words, p, (uint64_t)(((hxh::u128)1 << 64) / p), h);
+  HX_LAUNCH(hx::bgv_scatter_kernel, dim3(blocks_for(e.words)), dim3(256), 0, st, (const int64_t*)t->buf[0], (uint32_t)nslots,
+            t->d_row2slot, N, e.words, p, (uint64_t)(((hxh::u128)1 << 64) / p), h);
   CK(hipGetLastError());
-  RC(hx_ntt_inverse(sp));   // CRT_reconstruct: the H with the given values at the roots
-  const uint64_t* hc = hxi::poly_rows_read(sp);
-  uint64_t* rows = nullptr;
-  if (nrows > 0)
-    RC(hxi::poly_rows_write(out, &rows));
-  int64_t* d_coeffs = coeffs_out ? (int64_t*)t->buf[2] : nullptr;
-  if (nrows > 0 || d_coeffs) {
-    const uint64_t muls = hxh::shoup(mul, p);
-    if (words % 2 == 0 && aligned16(hc) && aligned16(rows) && aligned16(d_coeffs))
-      HX_LAUNCH(hx::bgv_lift_kernel<2>, dim3(blocks_for(words / 2)), dim3(256), 0, st, hc, words, p, mul, muls,
-                (const ulonglong2*)t->buf[1], nrows, rows, d_coeffs);
-    else
-      HX_LAUNCH(hx::bgv_lift_kernel<1>, dim3(blocks_for(words)), dim3(256), 0, st, hc, words, p, mul, muls,
-                (const ulonglong2*)t->buf[1], nrows, rows, d_coeffs);
-    CK(hipGetLastError());
+  return e.finish(mul % p, coeffs_out);
+}
+
+// ---- diagonals of a device-resident matrix (MatMul1DExec / MatMulFullExec construction, src/matmul.cpp) ----
+static_assert(sizeof(hx::BgvDiag) == sizeof(hx_bgv_diag) && sizeof(hx_bgv_diag) == 40, "hx_bgv_diag layout");
+struct hx_bgv_matrix {
+  const hx_bgv_slots* table = nullptr;
+  int64_t* d = nullptr;     // rows x cols words as given; the gather reduces mod p
+  hx::BgvDiagGeom g{};
+};
+
+extern "C" int hx_bgv_matrix_destroy(hx_bgv_matrix* a)
+{
+  if (!a)
+    return HX_OK;
+  if (a->table)
+    (void)hipSetDevice(a->table->device);
+  hipFree(a->d);
+  delete a;
+  return HX_OK;
+}
+
+extern "C" int hx_bgv_matrix_create(const hx_bgv_slots* t, const int64_t* a_host, int rows, int cols, int dim, hx_bgv_matrix** out)
+{
+  if (!t || !a_host || !out)
+    return err(HX_ERR_INVALID, "null argument");
+  *out = nullptr;
+  const int nd = (int)t->gens.size();
+  if (nd > 8)
+    return err(HX_ERR_UNSUPPORTED, "more than 8 generators");
+  if (dim < -1 || dim >= nd)
+    return err(HX_ERR_INVALID, "dim = %d is neither -1 (a full matrix) nor a dimension of the hypercube (%d)", dim, nd);
+  const uint64_t D = dim < 0 ? t->N : t->ords[dim];
+  if (rows < 1 || (uint64_t)rows != D || (uint64_t)cols != D)
+    return err(HX_ERR_INVALID, "a %d x %d matrix where dim = %d takes %llu x %llu", rows, cols, dim, (unsigned long long)D,
+               (unsigned long long)D);
+  Enter E;
+  RC(E.open(t, "hx_bgv_matrix_create"));
+  hx_bgv_matrix* a = new hx_bgv_matrix();
+  struct Guard {
+    hx_bgv_matrix* a;
+    ~Guard() { hx_bgv_matrix_destroy(a); }
+  } guard{a};
+  a->table = t;
+  a->g.nd = nd;
+  a->g.dim = dim;
+  a->g.cols = (uint32_t)cols;
+  uint64_t stride = 1;
+  for (int i = nd - 1; i >= 0; i--) {
+    a->g.ord[i] = (uint32_t)t->ords[i];
+    a->g.stride[i] = (uint32_t)stride;
+    stride *= t->ords[i];
   }
-  if (nrows > 0)
-    RC(hx_ntt_forward(out));
-  if (coeffs_out)
-    CK(hipMemcpyAsync(coeffs_out, d_coeffs, words * 8, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
+  const size_t bytes = (size_t)rows * (size_t)cols * 8;
+  CK(hipMalloc((void**)&a->d, bytes));
+  CK(hipMemcpyAsync(a->d, a_host, bytes, hipMemcpyHostToDevice, E.v.stream));
+  CK(hipStreamSynchronize(E.v.stream));
+  guard.a = nullptr;
+  *out = a;
+  return HX_OK;
+}
+
+extern "C" int hx_bgv_encode_diagonals(const hx_bgv_slots* tc, const hx_bgv_matrix* a, const hx_bgv_diag* d, int ndiag,
+                                       hx_poly* out, int64_t* coeffs_out, int* nonzero_out)
+{
+  if (!tc || !a || !d || !nonzero_out)
+    return err(HX_ERR_INVALID, "null argument");
+  hx_bgv_slots* t = const_cast<hx_bgv_slots*>(tc);
+  if (a->table != tc)
+    return err(HX_ERR_INVALID, "the matrix belongs to another slot table");
+  if (ndiag < 1)
+    return err(HX_ERR_INVALID, "bad number of diagonals %d", ndiag);
+  if (!out && coeffs_out)
+    return err(HX_ERR_INVALID, "coefficients without an output poly: pass a poly on no primes");
+  const hx::BgvDiagGeom& g = a->g;
+  std::vector<hx::BgvDiag> dd(ndiag);
+  for (int k = 0; k < ndiag; k++) {
+    const int rd = d[k].rot_dim;
+    if (rd < -1 || rd >= g.nd)
+      return err(HX_ERR_INVALID, "diagonal %d: rot_dim = %d is neither -1 nor a dimension of the hypercube (%d)", k, rd, g.nd);
+    for (int i = 0; i < 8; i++) {
+      const int64_t o = i < g.nd ? (int64_t)g.ord[i] : 1;
+      dd[k].off[i] = (int32_t)((((int64_t)d[k].off[i] % o) + o) % o);
+    }
+    const int64_t o = rd >= 0 ? (int64_t)g.ord[rd] : 1;
+    dd[k].rot_dim = rd;
+    dd[k].rot_amt = (int32_t)((((int64_t)d[k].rot_amt % o) + o) % o);
+  }
+  std::vector<uint32_t> nz(ndiag);   // (outlives e, whose destructor waits for the copies)
+  Encode e{t, out, ndiag};
+  RC(e.check());
+  const uint32_t N = t->N;
+  const uint64_t p = t->p, mu = (uint64_t)(((hxh::u128)1 << 64) / p);
+  const size_t dbytes = (sizeof(hx::BgvDiag) * (size_t)ndiag + 15) / 16 * 16, fbytes = sizeof(uint32_t) * (size_t)ndiag;
+  uint64_t* h = nullptr;
+  if (out) {
+    RC(e.open("hx_bgv_encode_diagonals", coeffs_out != nullptr, &h));
+  } else {   // the flags alone: no transform, no scratch rows
+    RC(e.E.open(t, "hx_bgv_encode_diagonals"));
+    e.st = e.E.v.stream;
+    e.words = (size_t)ndiag * N;
+  }
+  const hipStream_t st = e.st;
+  RC(ensure_buf(t, st, 0, dbytes + fbytes));
+  uint32_t* d_nz = (uint32_t*)((char*)t->buf[0] + dbytes);
+  CK(hipMemcpyAsync(t->buf[0], dd.data(), sizeof(hx::BgvDiag) * (size_t)ndiag, hipMemcpyHostToDevice, st));
+  CK(hipMemsetAsync(d_nz, 0, fbytes, st));
+  HX_LAUNCH(hx::bgv_diag_scatter_kernel, dim3(blocks_for(e.words)), dim3(256), 0, st, (const int64_t*)a->d, g,
+            (const hx::BgvDiag*)t->buf[0], t->d_row2slot, N, e.words, p, mu, h, d_nz);
+  CK(hipGetLastError());
+  CK(hipMemcpyAsync(nz.data(), d_nz, fbytes, hipMemcpyDeviceToHost, st));
+  if (out)
+    RC(e.finish(1, coeffs_out));
+  else
+    CK(hipStreamSynchronize(st));
+  for (int k = 0; k < ndiag; k++)
+    nonzero_out[k] = nz[k] ? 1 : 0;
   return HX_OK;
 }
 

@@ -10,7 +10,8 @@ constant` and `+=` (no equalizeRationalFactors multiplier other than 1, no mod-s
 otherwise the run goes term by term.  The class counter MatMul1DExec.fallbacks, and the timing statistic of the same
 name while timing.fhe_stats is set, count the runs that did not fuse.  HX_MATMUL_TERMWISE=1 (or fused=False) forces
 term by term.
-Out of scope: BlockMatMul1D, MatMulFull, non-native dimensions.  Nothing here imports oracle/."""
+The BGV classes (helib_amd.bgv_matmul) run the same mul with multByConstant as the multiply and their own dimension.
+Out of scope: BlockMatMul1D, MatMulFull for CKKS, non-native dimensions.  Nothing here imports oracle/."""
 import os
 import time
 
@@ -90,6 +91,7 @@ def _cleanUp(ct):
 
 class MatMul1DExec:
     fallbacks = 0      # groups that ran term by term although fusing was asked for (all instances)
+    dim = 0            # the dimension the rotations run along: CKKS has one; helib_amd.bgv_matmul sets it
 
     def __init__(self, ea, mat, minimal=False):
         mat = mat if isinstance(mat, MatMul1D_CKKS) else MatMul1D_CKKS(ea, mat)
@@ -205,20 +207,20 @@ class MatMul1DExec:
             for j in need:
                 out[j] = ct0.clone()
                 if j:
-                    out[j].smartAutomorph(z.genToPow(0, j))
+                    out[j].smartAutomorph(z.genToPow(self.dim, j))
                 _cleanUp(out[j])
             return out
         precon = hc.BasicAutomorphPrecon(ct)
         for j in need:
-            out[j] = _cleanUp(precon.automorph(z.genToPow(0, j)))
+            out[j] = _cleanUp(precon.automorph(z.genToPow(self.dim, j)))
         return out
 
     def mul(self, ct, pk=None, strategy=None, fused=None):
-        """MatMul1DExec::mul, native dimension.  The key-switching strategy of dimension 0 is read from the key
+        """MatMul1DExec::mul, native dimension.  The key-switching strategy of the dimension is read from the key
         `pk` (keys.getKSStrategy) unless given."""
         fused = self.fused if fused is None else fused
         if strategy is None:
-            strategy = hk.getKSStrategy(pk, 0) if pk is not None else hk.HELIB_KSS_UNKNOWN
+            strategy = hk.getKSStrategy(pk, self.dim) if pk is not None else hk.HELIB_KSS_UNKNOWN
         z, D, g, M = self.ea.zMStar, self.D, self.g, self.multiplier
         _cleanUp(ct)
         iterative = strategy == hk.HELIB_KSS_MIN
@@ -232,7 +234,7 @@ class MatMul1DExec:
                 for j in range((need[-1] + 1) if need else 0):
                     if j:
                         cur = cur.clone()
-                        cur.smartAutomorph(z.genToPow(0, 1))
+                        cur.smartAutomorph(z.genToPow(self.dim, 1))
                         _cleanUp(cur)
                     baby[j] = cur
                 self._tick("baby", t0)
@@ -240,7 +242,7 @@ class MatMul1DExec:
                 for k in range(h - 1, -1, -1):
                     if k < h - 1 and acc.parts:
                         t0 = time.perf_counter()
-                        acc.smartAutomorph(z.genToPow(0, g))
+                        acc.smartAutomorph(z.genToPow(self.dim, g))
                         _cleanUp(acc)
                         self._tick("giant", t0)
                     self._group(acc, [(M[i], baby[i % g]) for i in range(g * k, min(g * k + g, D)) if M[i]], fused)
@@ -256,7 +258,7 @@ class MatMul1DExec:
                         continue
                     t0 = time.perf_counter()
                     if k > 0:
-                        inner.smartAutomorph(z.genToPow(0, g * k))
+                        inner.smartAutomorph(z.genToPow(self.dim, g * k))
                     acc += inner
                     self._tick("giant", t0)
         elif not iterative:
@@ -265,21 +267,21 @@ class MatMul1DExec:
             terms = []
             if strategy == hk.HELIB_KSS_FULL:
                 precon = hc.BasicAutomorphPrecon(ct)
-                terms = [(M[i], precon.automorph(z.genToPow(0, i))) for i in live]
+                terms = [(M[i], precon.automorph(z.genToPow(self.dim, i))) for i in live]
             elif strategy == hk.HELIB_KSS_BSGS:
                 gg = hk.KSGiantStepSize(D)
                 p0, pre = hc.BasicAutomorphPrecon(ct), {}
                 for i in live:
                     k = i // gg
                     if k not in pre:
-                        pre[k] = hc.BasicAutomorphPrecon(p0.automorph(z.genToPow(0, gg * k)))
-                    terms.append((M[i], pre[k].automorph(z.genToPow(0, i % gg))))
+                        pre[k] = hc.BasicAutomorphPrecon(p0.automorph(z.genToPow(self.dim, gg * k)))
+                    terms.append((M[i], pre[k].automorph(z.genToPow(self.dim, i % gg))))
             else:
                 ct0 = _cleanUp(ct.clone())
                 for i in live:
                     r = ct0.clone()
                     if i:
-                        r.smartAutomorph(z.genToPow(0, i))
+                        r.smartAutomorph(z.genToPow(self.dim, i))
                     terms.append((M[i], r))
             self._tick("baby", t0)
             acc = _empty(ct)
@@ -290,7 +292,7 @@ class MatMul1DExec:
             for i in range((live[-1] + 1) if live else 0):
                 if i > 0:
                     sh = sh.clone()
-                    sh.smartAutomorph(z.genToPow(0, 1))
+                    sh.smartAutomorph(z.genToPow(self.dim, 1))
                     _cleanUp(sh)
                 if M[i]:
                     terms.append((M[i], sh))

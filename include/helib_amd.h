@@ -361,6 +361,34 @@ int hx_bgv_encode(const hx_bgv_slots* t, const int64_t* slots, int batch, int ns
 int hx_bgv_decode(const hx_bgv_slots* t, const hx_poly* acc, uint64_t factor_inv, int64_t* slots_out);
 /* EncryptedArray::decode of `batch` plaintext polynomials (host, [batch][phi(m)], any int64) -> slots_out as above. */
 int hx_bgv_embed(const hx_bgv_slots* t, const int64_t* coeffs, int batch, int64_t* slots_out);
+/* The constants of MatMul1DExec / MatMulFullExec (src/matmul.cpp:604-643, 2035-2075), read out of a matrix that lives
+ * on the device.  hx_bgv_matrix_create uploads a_host ([rows][cols], any int64; entries count mod p) once.  dim = -1:
+ * a full matrix, rows = cols = phi(m), indexed by slot; dim = i: a D x D matrix for dimension i of the hypercube,
+ * D = ords[i], indexed by the coordinate in that dimension.  Any other shape or dim: HX_ERR_INVALID.  Destroy the
+ * matrix before its table. */
+typedef struct hx_bgv_matrix hx_bgv_matrix;
+int hx_bgv_matrix_create(const hx_bgv_slots* t, const int64_t* a_host, int rows, int cols, int dim, hx_bgv_matrix** out);
+int hx_bgv_matrix_destroy(hx_bgv_matrix* a);
+/* One diagonal.  Slot s has the hypercube coordinates c (the last dimension fastest); s0 is s with c[rot_dim] replaced
+ * by c[rot_dim] - rot_amt (plaintextAutomorph at d = 1, build_ConstMultiplier, src/matmul.cpp:375-389; rot_dim = -1:
+ * no rotation).  The slot's value is
+ *   full matrix       A[r, s0], r the slot with the coordinates c_i(s0) - off[i] in every dimension i
+ *                     (MatMulFullHelper::processDiagonal over the accumulated rotate1D of the index vector, :1998-2024,
+ *                     2060-2072)
+ *   dimension dim     A[c_dim(s0) - off[dim], c_dim(s0)]   (processDiagonal1, :449-504)
+ * every difference taken modulo the order of its dimension; off and rot_amt may be any int32. */
+typedef struct hx_bgv_diag {
+  int32_t off[8];
+  int32_t rot_dim, rot_amt;
+} hx_bgv_diag;
+/* out (batch ndiag on its own prime set, as for hx_bgv_encode) receives the balanced encoding, in evaluation form, of
+ * the ndiag diagonals d[] of a; coeffs_out (optional) their zzX as in hx_bgv_encode; nonzero_out[t] = 0 exactly when
+ * every slot of diagonal t is 0 mod p (the reference keeps no multiplier for it, :369-372).  out = NULL (then
+ * coeffs_out = NULL too) computes the flags alone: one pass over the matrix words, no transform.  Preconditions and
+ * errors as for hx_bgv_encode; a matrix of another table and a rot_dim outside [-1, ndims) are HX_ERR_INVALID; a
+ * refused call touches no output.  The scratch grows with ndiag * phi(m): callers pass the diagonals in chunks. */
+int hx_bgv_encode_diagonals(const hx_bgv_slots* t, const hx_bgv_matrix* a, const hx_bgv_diag* d, int ndiag, hx_poly* out,
+                            int64_t* coeffs_out, int* nonzero_out);
 
 /* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
 /* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
