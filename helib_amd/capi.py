@@ -62,6 +62,7 @@ SYMBOLS = [
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
+    "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
 ]
 
 
@@ -162,6 +163,11 @@ def lib():
             "hx_bgv_embed": [vp, vp, ip, vp],
             "hx_bgv_matrix_create": [vp, vp, ip, ip, ip, vp], "hx_bgv_matrix_destroy": [vp],
             "hx_bgv_encode_diagonals": [vp, vp, vp, ip, vp, vp, vp],
+            "hx_bgv_crt_create": [vp, u64, vp], "hx_bgv_crt_destroy": [vp],
+            "hx_bgv_crt_info": [vp, vp, vp, vp, vp, vp, vp, vp],
+            "hx_bgv_crt_encode": [vp, vp, ip, u64, vp, vp],
+            "hx_bgv_crt_decode": [vp, vp, u64, vp],
+            "hx_bgv_crt_embed": [vp, vp, ip, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -730,6 +736,67 @@ def bgvEmbed(table, f):
     assert f.shape[1] == table.context.phim, f.shape
     out = np.zeros_like(f)
     _chk(lib().hx_bgv_embed(table.h, _p(f), f.shape[0], _p(out)))
+    return out
+
+
+class BgvCrt:
+    """The CRT tables of one (Context, p) pair (hx_bgv_crt): the default EncryptedArray for any d = ord_m(p), slots in
+    Z_p.  d, nslots, gens, ords (signed: a non-native dimension's order negated), table_bytes."""
+
+    def __init__(self, context, p):
+        self.context, self.p = context, int(p)
+        self.h = C.c_void_p()
+        _chk(lib().hx_bgv_crt_create(context.h, self.p, C.byref(self.h)))
+        d, ns, nd, tb = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+        g, o = (C.c_uint64 * 8)(), (C.c_int64 * 8)()
+        _chk(lib().hx_bgv_crt_info(self.h, None, C.byref(d), C.byref(ns), C.byref(nd), g, o, C.byref(tb)))
+        self.d, self.nslots, self.table_bytes = int(d.value), int(ns.value), int(tb.value)
+        self.gens, self.ords = [int(x) for x in g[:nd.value]], [int(x) for x in o[:nd.value]]
+
+    def close(self):
+        if self.h:
+            lib().hx_bgv_crt_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bgvCrtEncode(table, slots, idx, mul=1, coeffs=False):
+    """EncryptedArray::encode of slots[B, <= nslots] (integers; missing slots are 0) through the CRT tables: a DoubleCRT
+    over the prime indices `idx` holding balanced(mul * H mod p) in evaluation form (hx_bgv_crt_encode).  coeffs=True
+    also returns the int64 coefficients [B, phi(m)] (the zzX)."""
+    v = _slots_i64(slots)
+    B, ns = v.shape
+    if ns > table.nslots:
+        raise InvalidArgument(HX_ERR_INVALID, "more values than slots")
+    if ns < table.nslots:
+        v = np.ascontiguousarray(np.pad(v, ((0, 0), (0, table.nslots - ns))))
+    ctx = table.context
+    out = DoubleCRT(ctx, list(idx), B, zero=False)
+    cf = np.zeros((B, ctx.phim), dtype=np.int64) if coeffs else None
+    _chk(lib().hx_bgv_crt_encode(table.h, _p(v), B, int(mul) % table.p, out.h, _p(cf) if coeffs else None))
+    return (out, cf) if coeffs else out
+
+
+def bgvCrtDecode(table, poly, factor_inv=1):
+    """SecKey::Decrypt's tail for slots: poly = sum_parts part*s^r in evaluation form -> int64 [B, nslots] in [0, p)
+    (hx_bgv_crt_decode)."""
+    out = np.zeros((poly.batch, table.nslots), dtype=np.int64)
+    _chk(lib().hx_bgv_crt_decode(table.h, poly.h, int(factor_inv) % table.p, _p(out)))
+    return out
+
+
+def bgvCrtEmbed(table, f):
+    """EncryptedArray::decode of plaintext polynomials f[B, phi(m)] (integers) -> int64 slots [B, nslots] in [0, p)
+    (hx_bgv_crt_embed)."""
+    f = _slots_i64(f)
+    assert f.shape[1] == table.context.phim, f.shape
+    out = np.zeros((f.shape[0], table.nslots), dtype=np.int64)
+    _chk(lib().hx_bgv_crt_embed(table.h, _p(f), f.shape[0], _p(out)))
     return out
 
 

@@ -13,7 +13,8 @@
 //   bgv_gather_kernel   row order -> slot order                reads 8 B/word (random inside one row) + 4 B index,
 //                                                              writes 8 B/word coalesced
 // The streaming sides use 16-byte accesses (two words per lane) when the buffers allow it; grids are capped and
-// stride (BGV_MAX_BLOCKS).
+// stride (BGV_MAX_BLOCKS).  Two units include this header (bgv_slots.hip, bgv_crt.hip): the kernels that are no templates
+// have internal linkage.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -45,7 +46,7 @@ __device__ __forceinline__ uint64_t bgv_mul_shoup(uint64_t x, uint64_t w, uint64
 }
 
 // rows[b][j] = slots[b][row2slot[j]] mod p (0 where the row position holds a slot >= nslots): one thread per word
-__global__ void __launch_bounds__(256)
+static __global__ void __launch_bounds__(256)
 bgv_scatter_kernel(const int64_t* __restrict__ slots, uint32_t nslots, const uint32_t* __restrict__ row2slot, uint32_t N,
                    size_t words, uint64_t p, uint64_t mu, uint64_t* __restrict__ rows)
 {
@@ -79,7 +80,7 @@ struct BgvDiag {
 // all mod the orders.  One thread per word; rows = nullptr only raises the flags.  nz[t] |= 1 where a word is non-zero
 // (a vector atomic, skipped once the flag is seen set).  Per word: 4 B index + 8 B matrix word, one per 128 B line in
 // the worst case, + 8 B coalesced store; the descriptors are 40 B per diagonal, cached.
-__global__ void __launch_bounds__(256)
+static __global__ void __launch_bounds__(256)
 bgv_diag_scatter_kernel(const int64_t* __restrict__ A, BgvDiagGeom g, const BgvDiag* __restrict__ diags,
                         const uint32_t* __restrict__ row2slot, uint32_t N, size_t words, uint64_t p, uint64_t mu,
                         uint64_t* __restrict__ rows, uint32_t* nz)
@@ -121,7 +122,7 @@ bgv_diag_scatter_kernel(const int64_t* __restrict__ A, BgvDiagGeom g, const BgvD
 }
 
 // out[b][s] = rows[b][slot2row[s]]
-__global__ void __launch_bounds__(256)
+static __global__ void __launch_bounds__(256)
 bgv_gather_kernel(const uint64_t* __restrict__ rows, const uint32_t* __restrict__ slot2row, uint32_t N, size_t words,
                   int64_t* __restrict__ out)
 {

@@ -390,6 +390,36 @@ typedef struct hx_bgv_diag {
 int hx_bgv_encode_diagonals(const hx_bgv_slots* t, const hx_bgv_matrix* a, const hx_bgv_diag* d, int ndiag, hx_poly* out,
                             int64_t* coeffs_out, int* nonzero_out);
 
+/* ---------------- BGV slots for any d = ord_m(p), r = 1: integer slots mod p (bgv_crt.hip) ----------------
+ * The default-constructed EncryptedArray (G = X, include/helib/EncryptedArray.h): Phi_m mod p has nslots = phi(m) / d
+ * factors of degree d and a slot holds an integer mod p.  Factor 0 is the smallest by poly_comp
+ * (src/PAlgebra.cpp:67-81, 715-721), factor i the minimal polynomial of X^(1/t_i) mod F_0, t_i = ith_rep(i) of
+ * Z_m^* / <p> in hypercube order (:726-733).  The maps are two nslots x phi(m) matrices modulo p, uint32 words on the
+ * device: E, row i the idempotent of factor i (CRT_reconstruct of constants, :1007-1045, crtCoeffs :750-756), and R,
+ * R[i][k] = the constant term of X^k mod F_i (CRT_decompose :885-936, decodePlaintext's degG == 1 branch :1243-1261).
+ * Any ring the context itself supports; all calls synchronise the context's stream and fail with HX_ERR_INVALID
+ * under an open graph capture. */
+typedef struct hx_bgv_crt hx_bgv_crt; /* the tables of one (context, p) pair */
+/* Replaces PAlgebraModDerived's constructor at r = 1 (src/PAlgebra.cpp:680-772).  p not a prime, or p | m:
+ * HX_ERR_INVALID.  A prime p >= 2^31 (the tables hold 32-bit words), a table above 1 GiB, m < 3: HX_ERR_UNSUPPORTED,
+ * the message gives the figure.  Any d is accepted, d = 1 included.  Destroy the table before its context. */
+int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out);
+int hx_bgv_crt_destroy(hx_bgv_crt* t);
+/* p, d, nslots, the hypercube of Z_m^* / <p> -- ndims generators with their orders, a non-native dimension's order
+ * negated as Context::writeTo stores it (src/PAlgebra.cpp:470-507; at most 8 are written) -- and the bytes of E and
+ * R together; any output may be NULL. */
+int hx_bgv_crt_info(const hx_bgv_crt* t, uint64_t* p, int* d, int* nslots, int* ndims, uint64_t* gens, int64_t* ords,
+                    uint64_t* table_bytes);
+/* EncryptedArray::encode (src/EncryptedArray.cpp:438-447) of `batch` vectors of nslots integers ([batch][nslots],
+ * host; any int64 is reduced mod p).  out, mul and coeffs_out as for hx_bgv_encode; for p = 2 a coefficient is 0 or 1
+ * (the reference draws the sign of a 1 at random, src/zzX.cpp:139-154). */
+int hx_bgv_crt_encode(const hx_bgv_crt* t, const int64_t* slots, int batch, uint64_t mul, hx_poly* out, int64_t* coeffs_out);
+/* As hx_bgv_decode (src/keys.cpp:1383-1405, then EncryptedArray::decode): -> slots_out[batch][nslots] in [0, p). */
+int hx_bgv_crt_decode(const hx_bgv_crt* t, const hx_poly* acc, uint64_t factor_inv, int64_t* slots_out);
+/* EncryptedArray::decode (src/EncryptedArray.cpp:461-470) of `batch` plaintext polynomials (host, [batch][phi(m)], any
+ * int64) -> slots_out[batch][nslots] in [0, p). */
+int hx_bgv_crt_embed(const hx_bgv_crt* t, const int64_t* coeffs, int batch, int64_t* slots_out);
+
 /* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
 /* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
  * Replaces n x { tmp = b; tmp *= a; x += tmp }: MulAdd, src/matmul.cpp:391-408, and DoubleCRT::Mul with
