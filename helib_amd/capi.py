@@ -59,7 +59,7 @@ SYMBOLS = [
     "hx_profile_begin", "hx_profile_end", "hx_ctx_arena_stats", "hx_ctx_reserve",
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
-    "hx_mul_add_many", "hx_poly_extract", "hx_mask_split",
+    "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -156,6 +156,7 @@ def lib():
             "hx_mul_add_many": [vp, vp, vp, vp, vp, ip, ip],
             "hx_poly_extract": [vp, vp, ip],
             "hx_mask_split": [vp, vp, vp, vp, vp],
+            "hx_mask_blend": [vp, vp, vp, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -876,6 +877,15 @@ def maskSplit(keep0, keep1, take0, take1, mask):
         raise InvalidArgument(HX_ERR_INVALID, "keep1 and take1 go together (both None for a one-part ciphertext)")
     _chk(lib().hx_mask_split(keep0.h, keep1.h if keep1 is not None else None, take0.h,
                              take1.h if take1 is not None else None, mask.h))
+
+
+def maskBlend(c0, c1, t0, t1, mask):
+    """c = c * mask + t - t * mask on the one or two parts of a ciphertext in one pass (hx_mask_blend): the tail of the
+    non-native rotate1D, ctxt.multByConstant(m1); ctxt += T; T.multByConstant(m1); ctxt -= T
+    (src/EncryptedArray.cpp:120-124).  c1 / t1 = None for a one-part ciphertext; t* are read only."""
+    if (c1 is None) != (t1 is None):
+        raise InvalidArgument(HX_ERR_INVALID, "c1 and t1 go together (both None for a one-part ciphertext)")
+    _chk(lib().hx_mask_blend(c0.h, c1.h if c1 is not None else None, t0.h, t1.h if t1 is not None else None, mask.h))
 
 
 def likeUninit(poly):

@@ -4,7 +4,10 @@
 // being DoubleCRT::Mul with matchIndexSets = false), in one pass over the data; and of the mask split of the
 // linear-array rotate / shift (hx_mask_split):
 //   take = keep * mask,  keep -= take
-// (src/EncryptedArray.cpp:270-274: tmp = ctxt; tmp.multByConstant(mask); ctxt -= tmp), in one pass as well.  The unit
+// (src/EncryptedArray.cpp:270-274: tmp = ctxt; tmp.multByConstant(mask); ctxt -= tmp), in one pass as well; and of the
+// tail of the non-native rotate1D (hx_mask_blend):
+//   c = c * mask + t - t * mask
+// (src/EncryptedArray.cpp:120-124), one pass instead of four.  The unit
 // reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
 #include <hip/hip_runtime.h>
 
@@ -181,6 +184,63 @@ mask_split_kernel(uint64_t* __restrict__ keep0, uint64_t* __restrict__ keep1, ui
       t.y = mul_mod(x1[b].y, c.y, q, mu, k);
       st_stream2(take1 + row_off + boff[b], t);
       st_stream2(keep1 + row_off + boff[b], make_ulonglong2(sub_mod(x1[b].x, t.x, q), sub_mod(x1[b].y, t.y, q)));
+    }
+  }
+}
+
+// c = c * mask + t - t * mask (hx_mask_blend): the words hx_mul(c, mask), hx_add(c, t), hx_mul(t, mask), hx_sub(c, t)
+// leave in c.  Every operand is canonical, so the canonical residue of (c - t) * mask + t is that word: one mul_mod on
+// sub_mod(c, t), then add_mod.  t is read only.  The thread shape is mask_split_kernel's: two adjacent coefficients of
+// one prime row for BP batch elements, the two mask words loaded once when the mask has batch 1, PARTS * BP vectors of
+// c and of t loaded (16 bytes each, non-temporal: every word is read once) and PARTS * BP vectors stored.
+// map.brow[r] is the mask's row for output row r.  No LDS.  All addresses are kernel arguments, so a launch can be
+// captured.
+template <int PARTS, int BP>
+__global__ void __launch_bounds__(256)
+mask_blend_kernel(uint64_t* __restrict__ c0, uint64_t* __restrict__ c1, const uint64_t* __restrict__ t0,
+                  const uint64_t* __restrict__ t1, const uint64_t* __restrict__ mask, int mask_per_elem, int batch,
+                  uint32_t N, RowMap2 map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu;
+  const uint32_t k = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  const uint64_t* mrow = mask + (size_t)map.brow[row] * (mask_per_elem ? batch : 1) * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  ulonglong2 x0[BP], x1[BP], y0[BP], y1[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    x0[b] = ld_stream2(c0 + row_off + boff[b]);
+    y0[b] = ld_stream2(t0 + row_off + boff[b]);
+    if (PARTS == 2) {
+      x1[b] = ld_stream2(c1 + row_off + boff[b]);
+      y1[b] = ld_stream2(t1 + row_off + boff[b]);
+    }
+  }
+  ulonglong2 c = *reinterpret_cast<const ulonglong2*>(mrow + (mask_per_elem ? boff[0] : 2 * (size_t)i));
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    if (b > 0 && mask_per_elem)
+      c = *reinterpret_cast<const ulonglong2*>(mrow + boff[b]);
+    ulonglong2 r;
+    r.x = add_mod(mul_mod(sub_mod(x0[b].x, y0[b].x, q), c.x, q, mu, k), y0[b].x, q);
+    r.y = add_mod(mul_mod(sub_mod(x0[b].y, y0[b].y, q), c.y, q, mu, k), y0[b].y, q);
+    st_stream2(c0 + row_off + boff[b], r);
+    if (PARTS == 2) {
+      r.x = add_mod(mul_mod(sub_mod(x1[b].x, y1[b].x, q), c.x, q, mu, k), y1[b].x, q);
+      r.y = add_mod(mul_mod(sub_mod(x1[b].y, y1[b].y, q), c.y, q, mu, k), y1[b].y, q);
+      st_stream2(c1 + row_off + boff[b], r);
     }
   }
 }
@@ -507,6 +567,99 @@ extern "C" int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_
     launch_split<2>(bp, grid, v.stream, d[0], d[2], d[1], d[3], mp, per_elem, batch, N, map, primes);
   else
     launch_split<1>(bp, grid, v.stream, d[0], nullptr, d[1], nullptr, mp, per_elem, batch, N, map, primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+template <int PARTS>
+static void launch_blend(int bp, dim3 grid, hipStream_t st, uint64_t* c0, uint64_t* c1, const uint64_t* t0,
+                         const uint64_t* t1, const uint64_t* mask, int per_elem, int batch, uint32_t N,
+                         const hx::RowMap2& map, const hx::PrimeDev* primes)
+{
+  if (bp == 1)
+    HX_LAUNCH((hx::mask_blend_kernel<PARTS, 1>), grid, dim3(256), 0, st, c0, c1, t0, t1, mask, per_elem, batch, N, map,
+              primes);
+  else
+    HX_LAUNCH((hx::mask_blend_kernel<PARTS, 4>), grid, dim3(256), 0, st, c0, c1, t0, t1, mask, per_elem, batch, N, map,
+              primes);
+}
+
+extern "C" int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const hx_poly* mask)
+{
+  if (!c0 || !t0 || !mask)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((c1 == nullptr) != (t1 == nullptr))
+    return err(HX_ERR_INVALID, "c1 and t1 go together (both null for a one-part ciphertext)");
+  const int parts = c1 ? 2 : 1;
+  const hx_poly* ops[4] = {c0, t0, c1, t1};
+  for (int a = 0; a < 2 * parts; a++) {
+    if (ops[a] == mask && (a & 1) == 0)
+      return err(HX_ERR_INVALID, "an output is also the mask");
+    for (int b = a + 1; b < 2 * parts; b++)
+      if (ops[a] == ops[b])
+        return err(HX_ERR_INVALID, "c0, c1, t0 and t1 must be different polys");
+  }
+  hx_ctx* ctx = hxi::poly_ctx(c0);
+  for (int a = 1; a < 2 * parts; a++)
+    if (hxi::poly_ctx(ops[a]) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  if (hxi::poly_ctx(mask) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  int batch = 0, b2 = 0;
+  std::vector<int> idx, other;
+  RC(shape_of(c0, &batch, &idx));
+  const int rows = (int)idx.size();
+  if (rows > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  static const char* const name[4] = {"c0", "t0", "c1", "t1"};
+  for (int a = 1; a < 2 * parts; a++) {
+    RC(shape_of(ops[a], &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "%s differs from c0 in batch or prime set", name[a]);
+  }
+  RC(shape_of(mask, &b2, &other));
+  if (b2 != batch && b2 != 1)
+    return err(HX_ERR_INVALID, "mask: batch %d is neither 1 nor %d", b2, batch);
+  const int per_elem = b2 == batch && batch > 1;
+  hx::RowMap2 map;
+  for (int r = 0; r < rows; r++) {
+    int at = -1;
+    for (size_t j = 0; j < other.size(); j++)
+      if (other[j] == idx[r]) {
+        at = (int)j;
+        break;
+      }
+    if (at < 0)
+      return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the mask has no row for prime %d)", idx[r]);
+    map.p[r] = (uint16_t)idx[r];
+    map.brow[r] = (uint16_t)at;
+  }
+  const uint32_t N = v.phim;
+  if (N < 2 || (N & 1))
+    return err(HX_ERR_UNSUPPORTED, "hx_mask_blend needs an even number of coefficients");
+  if (rows == 0)
+    return HX_OK;
+  // c first: one that still shares t's rows (a lazy hx_poly_copy) takes its own copy, and t's rows stay where they are
+  uint64_t* d[2] = {nullptr, nullptr};
+  RC(hxi::poly_rows_update(c0, &d[0]));
+  if (c1)
+    RC(hxi::poly_rows_update(c1, &d[1]));
+  const uint64_t* s0 = hxi::poly_rows_read(t0);
+  const uint64_t* s1 = t1 ? hxi::poly_rows_read(t1) : nullptr;
+  const uint64_t* mp = hxi::poly_rows_read(mask);
+  if (((uint64_t)(uintptr_t)d[0] | (uint64_t)(uintptr_t)d[1] | (uint64_t)(uintptr_t)s0 | (uint64_t)(uintptr_t)s1 |
+       (uint64_t)(uintptr_t)mp) & 15)
+    return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
+  const int bp = batch == 1 ? 1 : 4;
+  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  if (parts == 2)
+    launch_blend<2>(bp, grid, v.stream, d[0], d[1], s0, s1, mp, per_elem, batch, N, map, primes);
+  else
+    launch_blend<1>(bp, grid, v.stream, d[0], nullptr, s0, nullptr, mp, per_elem, batch, N, map, primes);
   CK(hipGetLastError());
   return HX_OK;
 }

@@ -450,6 +450,21 @@ int hx_poly_extract(hx_poly* dst, const hx_poly* src, int b);
  * kernel argument: the call is asynchronous on the context's stream and may be recorded in a graph capture.
  * HX_NO_MASK_SPLIT=1 runs the three calls per part instead. */
 int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_poly* take1, const hx_poly* mask);
+/* The tail of the non-native rotate1D (src/EncryptedArray.cpp:120-124:
+ *   ctxt.multByConstant(m1);  ctxt += T;  T.multByConstant(m1);  ctxt -= T;)
+ * on the parts of one ciphertext, in one pass:  c = c * mask + t - t * mask,  row by row modulo each prime, every word
+ * canonical in [0, q) and equal to what hx_mul(c, mask), hx_add(c, t), hx_mul(t, mask), hx_sub(c, t) leave in c.  t is
+ * read, not written: the four-call form ends with t = t * mask, a value every caller drops.  c1 and t1 are both null
+ * for a one-part operand.  t0 / t1 have the batch and the prime set (same order) of c0 / c1; all are in evaluation form
+ * (a poly does not record its form: that is the caller's to keep).  mask has batch 1 (broadcast over the batch) or the
+ * batch of c, and may live on more primes than c: its rows are matched by prime index, a missing prime is
+ * HX_ERR_PRIMESET (as hx_mul's).  Null arguments, c0 / c1 being the mask, c and t (or the two parts) being one poly, a
+ * poly of another context and mismatched shapes are HX_ERR_INVALID; an odd phi(m) is HX_ERR_UNSUPPORTED; a refused
+ * call touches no operand.  A c that still shares its rows with t (a lazy hx_poly_copy) takes its own copy first, and
+ * the result is then c unchanged.  Every pointer travels as a kernel argument: the call is asynchronous on the
+ * context's stream and may be recorded in a graph capture.  Per part, in passes over the part, the four calls read 6
+ * and write 4 (and read the mask twice); this call reads 2 and writes 1 (and reads the mask once). */
+int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const hx_poly* mask);
 
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
