@@ -15,7 +15,7 @@ below derive from them and restate the reference's masked paths.
                       native `dim` is the base class's
 
 Out of scope, refused with a message that says so: MatMulFullExec over a hypercube with a non-native dimension
-(src/matmul.cpp:2157-2250), BlockMatMul*, slots in GF(p^d), p^r with r > 1.  Nothing here imports oracle/."""
+(src/matmul.cpp:2157-2250), BlockMatMul*, p^r with r > 1.  Nothing here imports oracle/."""
 import contextlib
 import os
 import time

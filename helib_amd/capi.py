@@ -63,6 +63,7 @@ SYMBOLS = [
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
+    "hx_bgv_gf_create", "hx_bgv_gf_destroy", "hx_bgv_gf_info", "hx_bgv_gf_encode", "hx_bgv_gf_decode", "hx_bgv_gf_embed",
 ]
 
 
@@ -169,6 +170,11 @@ def lib():
             "hx_bgv_crt_encode": [vp, vp, ip, u64, vp, vp],
             "hx_bgv_crt_decode": [vp, vp, u64, vp],
             "hx_bgv_crt_embed": [vp, vp, ip, vp],
+            "hx_bgv_gf_create": [vp, u64, vp], "hx_bgv_gf_destroy": [vp],
+            "hx_bgv_gf_info": [vp, vp, vp, vp, vp, vp, vp, vp, vp],
+            "hx_bgv_gf_encode": [vp, vp, ip, u64, vp, vp],
+            "hx_bgv_gf_decode": [vp, vp, u64, vp],
+            "hx_bgv_gf_embed": [vp, vp, ip, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -798,6 +804,80 @@ def bgvCrtEmbed(table, f):
     assert f.shape[1] == table.context.phim, f.shape
     out = np.zeros((f.shape[0], table.nslots), dtype=np.int64)
     _chk(lib().hx_bgv_crt_embed(table.h, _p(f), f.shape[0], _p(out)))
+    return out
+
+
+class BgvGf:
+    """The tables of one (Context, p) pair for slots in GF(p^d) = Z_p[X] / G, G = F_0 (hx_bgv_gf): EncryptedArray(context,
+    G).  d, nslots, gens, ords (signed), table_bytes, G (d + 1 integers, the constant coefficient first)."""
+
+    def __init__(self, context, p):
+        self.context, self.p = context, int(p)
+        self.h = C.c_void_p()
+        _chk(lib().hx_bgv_gf_create(context.h, self.p, C.byref(self.h)))
+        d, ns, nd, tb = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
+        g, o = (C.c_uint64 * 8)(), (C.c_int64 * 8)()
+        _chk(lib().hx_bgv_gf_info(self.h, None, C.byref(d), C.byref(ns), C.byref(nd), g, o, C.byref(tb), None))
+        self.d, self.nslots, self.table_bytes = int(d.value), int(ns.value), int(tb.value)
+        self.gens, self.ords = [int(x) for x in g[:nd.value]], [int(x) for x in o[:nd.value]]
+        G = (C.c_uint64 * (self.d + 1))()
+        _chk(lib().hx_bgv_gf_info(self.h, None, None, None, None, None, None, None, G))
+        self.G = [int(x) for x in G]
+
+    def close(self):
+        if self.h:
+            lib().hx_bgv_gf_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def _gf_slots(table, slots):
+    """int64 [B, nslots, d] from [B, <= nslots] (constants in the slots) or [B, <= nslots, <= d]"""
+    v = np.asarray(slots, dtype=np.int64)
+    if v.ndim == 1:
+        v = v[None, :]
+    if v.ndim == 2:
+        v = v[:, :, None]
+    if v.ndim != 3 or v.shape[1] > table.nslots or v.shape[2] > table.d:
+        raise InvalidArgument(HX_ERR_INVALID, "more values than slots, or more coefficients than d")
+    out = np.zeros((v.shape[0], table.nslots, table.d), dtype=np.int64)
+    out[:, :v.shape[1], :v.shape[2]] = v
+    return out
+
+
+def bgvGfEncode(table, slots, idx, mul=1, coeffs=False):
+    """EncryptedArray::encode of GF(p^d) slots (see _gf_slots for the shapes) through the tables: a DoubleCRT over the
+    prime indices `idx` holding balanced(mul * H mod p) in evaluation form (hx_bgv_gf_encode).  coeffs=True also returns
+    the int64 coefficients [B, phi(m)] (the zzX)."""
+    v = _gf_slots(table, slots)
+    B = v.shape[0]
+    ctx = table.context
+    out = DoubleCRT(ctx, list(idx), B, zero=False)
+    cf = np.zeros((B, ctx.phim), dtype=np.int64) if coeffs else None
+    _chk(lib().hx_bgv_gf_encode(table.h, _p(v), B, int(mul) % table.p, out.h, _p(cf) if coeffs else None))
+    return (out, cf) if coeffs else out
+
+
+def bgvGfDecode(table, poly, factor_inv=1):
+    """SecKey::Decrypt's tail for GF(p^d) slots: poly = sum_parts part*s^r in evaluation form -> int64
+    [B, nslots, d] in [0, p) (hx_bgv_gf_decode)."""
+    out = np.zeros((poly.batch, table.nslots, table.d), dtype=np.int64)
+    _chk(lib().hx_bgv_gf_decode(table.h, poly.h, int(factor_inv) % table.p, _p(out)))
+    return out
+
+
+def bgvGfEmbed(table, f):
+    """EncryptedArray::decode of plaintext polynomials f[B, phi(m)] (integers) -> int64 slots [B, nslots, d] in [0, p)
+    (hx_bgv_gf_embed)."""
+    f = _slots_i64(f)
+    assert f.shape[1] == table.context.phim, f.shape
+    out = np.zeros((f.shape[0], table.nslots, table.d), dtype=np.int64)
+    _chk(lib().hx_bgv_gf_embed(table.h, _p(f), f.shape[0], _p(out)))
     return out
 
 

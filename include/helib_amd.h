@@ -420,6 +420,35 @@ int hx_bgv_crt_decode(const hx_bgv_crt* t, const hx_poly* acc, uint64_t factor_i
  * int64) -> slots_out[batch][nslots] in [0, p). */
 int hx_bgv_crt_embed(const hx_bgv_crt* t, const int64_t* coeffs, int batch, int64_t* slots_out);
 
+/* ---------------- BGV slots in GF(p^d) = Z_p[X] / G, G = F_0, d = ord_m(p), r = 1 (bgv_gf.hip) ----------------
+ * EncryptedArray(context, G) with G the first factor of Phi_m mod p (the one hx_bgv_crt numbers 0): slot i holds a
+ * polynomial alpha_i of degree < d over Z_p, d int64 words lowest coefficient first, read modulo G.  The plaintext is
+ * H = sum_i alpha_i(X^(t_i)) E_i mod (Phi_m, p) (PAlgebraModDerived::embedInSlots and CRT_reconstruct with the
+ * G = F_0 special case, src/PAlgebra.cpp:1064-1067, 1096-1100, 1168-1186, and matrix_maps), and slot i of a
+ * plaintext w is (w mod F_i)(X^(1/t_i)) mod G (decodePlaintext, :1243-1278).  A slot (a, 0, ..., 0) is the integer a
+ * of hx_bgv_crt, word for word; d = 1 is hx_bgv_crt.  The tables stay nslots x phi(m): E, the decode rows run d - 1
+ * words further, two d x d maps per slot and d - 1 rows X^(phi(m) + u) mod Phi_m.  Calls synchronise the context's
+ * stream and fail with HX_ERR_INVALID under an open graph capture. */
+typedef struct hx_bgv_gf hx_bgv_gf; /* the tables of one (context, p) pair */
+/* Replaces PAlgebraModDerived's constructor and mapToSlots at G = F_0 (src/PAlgebra.cpp:680-772, 1116-1186).  The
+ * refusals of hx_bgv_crt_create, and d > 64: HX_ERR_UNSUPPORTED with the figures. */
+int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out);
+int hx_bgv_gf_destroy(hx_bgv_gf* t);
+/* As hx_bgv_crt_info; table_bytes counts every device table; G receives d + 1 words, the constant coefficient first
+ * (PAlgebraMod::getFactors()[0], src/PAlgebra.cpp:715-721).  Any output may be NULL. */
+int hx_bgv_gf_info(const hx_bgv_gf* t, uint64_t* p, int* d, int* nslots, int* ndims, uint64_t* gens, int64_t* ords,
+                   uint64_t* table_bytes, uint64_t* G);
+/* EncryptedArray::encode (src/EncryptedArray.cpp:438-447 over src/PAlgebra.cpp:1064-1100, 1007-1045) of `batch`
+ * vectors of nslots slots ([batch][nslots][d], host; any int64 is reduced mod p).  out, mul and coeffs_out as for
+ * hx_bgv_crt_encode. */
+int hx_bgv_gf_encode(const hx_bgv_gf* t, const int64_t* slots, int batch, uint64_t mul, hx_poly* out, int64_t* coeffs_out);
+/* As hx_bgv_crt_decode (src/keys.cpp:1383-1405, then EncryptedArray::decode over src/PAlgebra.cpp:1243-1278):
+ * -> slots_out[batch][nslots][d] in [0, p). */
+int hx_bgv_gf_decode(const hx_bgv_gf* t, const hx_poly* acc, uint64_t factor_inv, int64_t* slots_out);
+/* EncryptedArray::decode (src/EncryptedArray.cpp:461-470 over src/PAlgebra.cpp:1243-1278) of `batch` plaintext
+ * polynomials (host, [batch][phi(m)], any int64) -> slots_out[batch][nslots][d] in [0, p). */
+int hx_bgv_gf_embed(const hx_bgv_gf* t, const int64_t* coeffs, int batch, int64_t* slots_out);
+
 /* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
 /* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
  * Replaces n x { tmp = b; tmp *= a; x += tmp }: MulAdd, src/matmul.cpp:391-408, and DoubleCRT::Mul with
