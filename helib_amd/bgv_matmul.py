@@ -224,7 +224,7 @@ def _generalAutomorphPrecon(ea, ct, dim, strategy):
         precon = hc.BasicAutomorphPrecon(ct)
         return lambda i: precon.automorph(z.genToPow(dim, i))
     if strategy == hk.HELIB_KSS_BSGS:
-        g = hk.KSGiantStepSize(z.OrderOf(dim))
+        g = hk.KSGiantStepSize(z.ordP if dim == -1 else z.OrderOf(dim))     # dim = -1: the Frobenius (:211)
         p0, pre = hc.BasicAutomorphPrecon(ct), {}
 
         def bsgs(i):

@@ -64,6 +64,7 @@ SYMBOLS = [
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
     "hx_bgv_gf_create", "hx_bgv_gf_destroy", "hx_bgv_gf_info", "hx_bgv_gf_encode", "hx_bgv_gf_decode", "hx_bgv_gf_embed",
+    "hx_bgv_gf_linalg_tables", "hx_bgv_gf_matrix_create", "hx_bgv_gf_matrix_destroy", "hx_bgv_gf_matrix_coeffs", "hx_bgv_gf_gather",
 ]
 
 
@@ -175,6 +176,10 @@ def lib():
             "hx_bgv_gf_encode": [vp, vp, ip, u64, vp, vp],
             "hx_bgv_gf_decode": [vp, vp, u64, vp],
             "hx_bgv_gf_embed": [vp, vp, ip, vp],
+            "hx_bgv_gf_linalg_tables": [u64, ip, vp, vp, vp, vp],
+            "hx_bgv_gf_matrix_create": [vp, vp, ip, ip, ip, vp, vp, vp, vp], "hx_bgv_gf_matrix_destroy": [vp],
+            "hx_bgv_gf_matrix_coeffs": [vp, vp],
+            "hx_bgv_gf_gather": [vp, vp, ip, vp, ip, vp, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -879,6 +884,69 @@ def bgvGfEmbed(table, f):
     out = np.zeros((f.shape[0], table.nslots, table.d), dtype=np.int64)
     _chk(lib().hx_bgv_gf_embed(table.h, _p(f), f.shape[0], _p(out)))
     return out
+
+
+def bgvGfLinalgTables(p, d, G):
+    """The host tables of linear maps on GF(p^d) slots (hx_bgv_gf_linalg_tables): frob [d, d, d] with frob[e][l] =
+    X^(l p^e) mod G, K [d, d, d] with K[j][k] the entries of the inverse of M[i][j] = (X^j)^(p^i), and the flat table
+    T [d^2, d^2] of buildLinPolyCoeffs; uint32."""
+    d = int(d)
+    g = (C.c_uint64 * (d + 1))(*[int(x) for x in G])
+    frob, K, T = (np.zeros(max(d, 1) ** e, dtype=np.uint32) for e in (3, 3, 4))
+    _chk(lib().hx_bgv_gf_linalg_tables(int(p), d, g, _p(frob), _p(K), _p(T)))
+    return frob.reshape(d, d, d), K.reshape(d, d, d), T.reshape(d * d, d * d)
+
+
+class BgvGfMatrix:
+    """A matrix over GF(p^d) slots on the device (hx_bgv_gf_matrix): GF entries words[nb, D, D, d] or blocks
+    words[nb, D, D, d, d] (integers in [0, p)); blk / col [nslots]: the transform and the column every slot reads.  For
+    blocks the linearized-polynomial coefficients of every entry are formed on the device at creation."""
+
+    def __init__(self, table, words, blk, col):
+        w = np.ascontiguousarray(np.asarray(words), dtype=np.uint32)
+        if w.ndim not in (4, 5) or w.shape[1] != w.shape[2] or any(x != table.d for x in w.shape[3:]):
+            raise InvalidArgument(HX_ERR_INVALID, "a GF matrix is [nb, D, D, d] or [nb, D, D, d, d]")
+        self.table, self.block, self.nb, self.D = table, w.ndim == 5, w.shape[0], w.shape[1]
+        blk, col = (np.ascontiguousarray(np.asarray(x), dtype=np.int32) for x in (blk, col))
+        if blk.shape != (table.nslots,) or col.shape != (table.nslots,):
+            raise InvalidArgument(HX_ERR_INVALID, "blk and col name one transform and one column per slot")
+        self.h = C.c_void_p()
+        _chk(lib().hx_bgv_gf_matrix_create(table.context.h, table.h, 1 if self.block else 0, self.nb, self.D, _p(w), _p(blk),
+                                           _p(col), C.byref(self.h)))
+
+    def coeffs(self):
+        """the words the gather reads: uint32 [nb, D, D, d, d] (row k = C[k] of the entry) or the entries [nb, D, D, d]"""
+        d = self.table.d
+        out = np.zeros((self.nb, self.D, self.D) + ((d, d) if self.block else (d,)), dtype=np.uint32)
+        _chk(lib().hx_bgv_gf_matrix_coeffs(self.h, _p(out)))
+        return out
+
+    def close(self):
+        if self.h:
+            lib().hx_bgv_gf_matrix_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def bgvGfGather(matrix, descs, maps):
+    """descs int32 [n, 3] = (diagonal, coefficient index, map), maps int32 [nmaps, nslots, 2] = (source slot or -1,
+    Frobenius exponent) -> (int64 slots [n, nslots, d] as bgvGfEncode reads them, bool non-zero flags [n])
+    (hx_bgv_gf_gather)."""
+    t = matrix.table
+    ds = np.ascontiguousarray(descs, dtype=np.int32).reshape(-1, 3)
+    mp = np.ascontiguousarray(maps, dtype=np.int32)
+    if mp.ndim != 3 or mp.shape[1:] != (t.nslots, 2):
+        raise InvalidArgument(HX_ERR_INVALID, "maps is [nmaps, nslots, 2]")
+    n = ds.shape[0]
+    out = np.zeros((n, t.nslots, t.d), dtype=np.int64)
+    nz = np.zeros(max(n, 1), dtype=np.int32)
+    _chk(lib().hx_bgv_gf_gather(matrix.h, _p(ds), n, _p(mp), mp.shape[0], _p(out), _p(nz)))
+    return out, nz[:n] != 0
 
 
 class BgvMatrix:

@@ -449,6 +449,40 @@ int hx_bgv_gf_decode(const hx_bgv_gf* t, const hx_poly* acc, uint64_t factor_inv
  * polynomials (host, [batch][phi(m)], any int64) -> slots_out[batch][nslots][d] in [0, p). */
 int hx_bgv_gf_embed(const hx_bgv_gf* t, const int64_t* coeffs, int batch, int64_t* slots_out);
 
+/* ---------------- linear maps on GF(p^d) slots: the constants of linearized polynomials (bgv_gf_linalg.hip) ------------
+ * A Z_p-linear map of a slot is sum_k C[k] alpha^(p^k) (EncryptedArrayDerived::buildLinPolyCoeffs,
+ * src/EncryptedArray.cpp:760-798).  The host tables: frob[e][l] = X^(l p^e) mod G ([d][d][d] words), K = the inverse of
+ * M[i][j] = (X^j)^(p^i) over the field ([d][d] elements of d words: buildLinPolyMatrix + ppInvert,
+ * src/NumbTh.cpp:1099-1111, src/EncryptedArray.cpp:783-787) and the flat table T[(j,b)][(k,c)] = [X^c](X^b K[j][k] mod G)
+ * ([d^2][d^2] words) with C = E T for the map sending X^j to sum_b E[j][b] X^b.  Host only; any output may be NULL.
+ * G: d + 1 words, monic.  d > 64 or p >= 2^31: HX_ERR_UNSUPPORTED. */
+int hx_bgv_gf_linalg_tables(uint64_t p, int d, const uint64_t* G, uint32_t* frob_out, uint32_t* K_out, uint32_t* T_out);
+typedef struct hx_bgv_gf_matrix hx_bgv_gf_matrix; /* a matrix of GF(p^d) entries or d x d blocks on the device */
+/* The matrix of a MatMul1D with entries in GF(p^d) (block = 0: words[nb][D][D][d]) or of a BlockMatMul1D (block = 1:
+ * words[nb][D][D][d][d], entry row j = the image of X^j), uint32 words below p on the host.  blk[s], col[s] (nslots
+ * each) name the transform and the column slot s reads (PAlgebra::breakIndexByDim; the size-1 dimension of
+ * BlockMatMul1DExec has blk[s] = s, col[s] = 0, D = 1).  For blocks every entry's linearized-polynomial coefficients
+ * [d][d] are formed here, once, by one product [nb D D, d^2] x [d^2, d^2] modulo p on the device (replaces
+ * buildLinPolyCoeffs per entry in processDiagonal1/2, src/matmul.cpp:1369-1373, 1452-1457).  Words not below p, blk or
+ * col out of range: HX_ERR_INVALID.  Synchronises the context's stream.  Destroy the matrix before its context. */
+int hx_bgv_gf_matrix_create(hx_ctx* ctx, const hx_bgv_gf* t, int block, int nb, int D, const uint32_t* words, const int32_t* blk,
+                            const int32_t* col, hx_bgv_gf_matrix** out);
+int hx_bgv_gf_matrix_destroy(hx_bgv_gf_matrix* a);
+/* The words the gather reads: [nb D D][d][d] coefficients (row k = C[k]) for blocks, the entries themselves otherwise. */
+int hx_bgv_gf_matrix_coeffs(const hx_bgv_gf_matrix* a, uint32_t* out);
+/* One constant: slot s, with (src, e) = maps[map][s] (two int32 per slot), holds zero when src = -1 and otherwise
+ * Frob^e of coefficient k (0 for GF entries) of the entry [(col[src] - diag) mod D, col[src]] of transform blk[src]. */
+typedef struct hx_bgv_gf_desc {
+  int32_t diag, k, map;
+} hx_bgv_gf_desc;
+/* slots_out[ndesc][nslots][d] (host, the layout hx_bgv_gf_encode reads) and nonzero_out[ndesc] (0 exactly when every
+ * word of the constant is 0).  Replaces the slot-by-slot transposition and the poly-space plaintextAutomorph / mask
+ * products of build_ConstMultiplier(poly, -1, -j), (poly, dim, -i), the masked halves and (poly1, dim, D)
+ * (src/matmul.cpp:375-389, 1392-1400, 1467-1475, 1560-1651): a plaintext automorphism permutes slots and applies a
+ * power of the Frobenius to each.  Anything out of range: HX_ERR_INVALID before the device is touched. */
+int hx_bgv_gf_gather(const hx_bgv_gf_matrix* a, const hx_bgv_gf_desc* descs, int ndesc, const int32_t* maps, int nmaps,
+                     int64_t* slots_out, int* nonzero_out);
+
 /* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
 /* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
  * Replaces n x { tmp = b; tmp *= a; x += tmp }: MulAdd, src/matmul.cpp:391-408, and DoubleCRT::Mul with
