@@ -26,8 +26,8 @@ ciphertexts and come back out.
   matrix products     helib_amd.bgv_matmul: MatMul1DExec / MatMulFullExec over rotate1D, with the diagonals read out of a
                       device-resident matrix (DeviceEncoder.matrix / encodeDiagonals: hx_bgv_encode_diagonals)
 
-Out of scope: d > 1 (helib_amd.bgv_crt, bgv_hypercube and bgv_gf cover it) and p^r with r > 1 -- refused with
-HX_ERR_UNSUPPORTED.  Nothing here imports
+Out of scope: d > 1 (helib_amd.bgv_crt, bgv_hypercube and bgv_gf cover it) and p^r with r > 1 (helib_amd.bgv_pr) --
+refused with HX_ERR_UNSUPPORTED.  Nothing here imports
 oracle/."""
 import collections
 import math

@@ -11,7 +11,8 @@ of the reference's rings work.
   rotate / shift / totalSums / runningSums, and helib_amd.bgv_matmul, over a hypercube with a non-native dimension
                       raise LogicError: their masked loops (src/EncryptedArray.cpp:221-264) are not built
 
-Out of scope: p^r with r > 1 (slots in GF(p^d), G = F_0: helib_amd.bgv_gf).  Nothing here imports oracle/."""
+Out of scope: p^r with r > 1 (refused here; integer slots mod p^r: helib_amd.bgv_pr.  Slots in GF(p^d), G = F_0:
+helib_amd.bgv_gf).  Nothing here imports oracle/."""
 import numpy as np
 
 from . import bgv, capi, hostnt

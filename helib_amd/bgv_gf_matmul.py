@@ -108,6 +108,8 @@ def _tables(ea):
 
 
 def _check(ea):
+    if getattr(ea, "r", 1) != 1:
+        raise LogicError("linear maps on GF(p^d) slots at p^r with r > 1 (helib_amd.bgv_pr holds integers) are not built")
     if not isinstance(ea, bgv_gf.EncryptedArray):
         raise LogicError("linear maps on GF(p^d) slots take helib_amd.bgv_gf.EncryptedArray")
 

@@ -15,7 +15,8 @@ below derive from them and restate the reference's masked paths.
                       native `dim` is the base class's
 
 Out of scope, refused with a message that says so: MatMulFullExec over a hypercube with a non-native dimension
-(src/matmul.cpp:2157-2250), BlockMatMul*, p^r with r > 1.  Nothing here imports oracle/."""
+(src/matmul.cpp:2157-2250), BlockMatMul*, p^r with r > 1 (integer slots mod p^r: helib_amd.bgv_pr, which derives from
+the class below).  Nothing here imports oracle/."""
 import contextlib
 import os
 import time
@@ -195,6 +196,7 @@ class MatMul1DExec(bgv_matmul.MatMul1DExec):
     >= i / < i of a non-native dimension (vec / vec1 of MatMul1DExec_construct)"""
 
     def __init__(self, ea, mat, minimal=False, dim=None, device_diagonals=None):
+        bgv_matmul._modPOnly(ea, "MatMul1DExec")
         if not isinstance(mat, (bgv_matmul.MatMul1D, bgv_matmul._FullHelper)):
             if dim is None:
                 raise LogicError("MatMul1DExec: a bare matrix needs its dimension (or pass a MatMul1D)")
@@ -347,6 +349,7 @@ class MatMulFullExec(bgv_matmul.MatMulFullExec):
     the masked rotations (src/matmul.cpp:2157-2250) is not built"""
 
     def __init__(self, ea, mat, minimal=False, device_diagonals=None):
+        bgv_matmul._modPOnly(ea, "MatMulFullExec")
         if not all(ea.nativeDimension(i) for i in range(ea.dimension())):
             raise LogicError("MatMulFullExec over a hypercube with a non-native dimension is out of scope "
                              "(src/matmul.cpp:2157-2250 is not built); MatMul1DExec works along one dimension")

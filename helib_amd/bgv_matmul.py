@@ -59,10 +59,18 @@ def diagonalSlots(ea, a, dim, off, rot_dim=-1, rot_amt=0):
     return a[r, s0] % ea.p
 
 
+def _modPOnly(ea, what):
+    """the matrix products are built for slots mod p: over helib_amd.bgv_pr.EncryptedArray at r > 1 the diagonals
+    would have to be reduced, gathered and encoded mod p^r"""
+    if getattr(ea, "r", 1) != 1:
+        raise LogicError("%s over slots mod p^r with r > 1 (helib_amd.bgv_pr) is not built" % what)
+
+
 class _Matrix:
     """a plaintext matrix of one of the two shapes: dense integers, or a callable get(i, j) read out once"""
 
     def __init__(self, ea, mat, dim, side):
+        _modPOnly(ea, type(self).__name__)
         self.ea, self.dim = ea, dim
         self.callable = callable(mat)
         if self.callable:
@@ -153,6 +161,7 @@ class MatMul1DExec(linalg.MatMul1DExec):
     FLAG_CHUNK = 4096          # descriptors per flags-only call (40 B each; no scratch rows)
 
     def __init__(self, ea, mat, minimal=False, dim=None, device_diagonals=None):
+        _modPOnly(ea, "MatMul1DExec")
         if not isinstance(mat, (MatMul1D, _FullHelper)):
             if dim is None:
                 raise LogicError("MatMul1DExec: a bare matrix needs its dimension (or pass a MatMul1D)")
@@ -248,6 +257,7 @@ class MatMulFullExec:
     the offsets in the dimensions before it"""
 
     def __init__(self, ea, mat, minimal=False, device_diagonals=None):
+        _modPOnly(ea, "MatMulFullExec")
         mat = mat if isinstance(mat, MatMulFull) else MatMulFull(ea, mat)
         self.ea, self.mat, self.minimal = ea, mat, minimal
         nd = ea.dimension()

@@ -59,10 +59,11 @@ SYMBOLS = [
     "hx_profile_begin", "hx_profile_end", "hx_ctx_arena_stats", "hx_ctx_reserve",
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
-    "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend",
+    "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
+    "hx_bgv_crt_create_pr", "hx_bgv_crt_space",
     "hx_bgv_gf_create", "hx_bgv_gf_destroy", "hx_bgv_gf_info", "hx_bgv_gf_encode", "hx_bgv_gf_decode", "hx_bgv_gf_embed",
     "hx_bgv_gf_linalg_tables", "hx_bgv_gf_matrix_create", "hx_bgv_gf_matrix_destroy", "hx_bgv_gf_matrix_coeffs", "hx_bgv_gf_gather",
 ]
@@ -159,6 +160,7 @@ def lib():
             "hx_poly_extract": [vp, vp, ip],
             "hx_mask_split": [vp, vp, vp, vp, vp],
             "hx_mask_blend": [vp, vp, vp, vp, vp],
+            "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -167,6 +169,7 @@ def lib():
             "hx_bgv_matrix_create": [vp, vp, ip, ip, ip, vp], "hx_bgv_matrix_destroy": [vp],
             "hx_bgv_encode_diagonals": [vp, vp, vp, ip, vp, vp, vp],
             "hx_bgv_crt_create": [vp, u64, vp], "hx_bgv_crt_destroy": [vp],
+            "hx_bgv_crt_create_pr": [vp, u64, ip, vp], "hx_bgv_crt_space": [vp, vp, vp],
             "hx_bgv_crt_info": [vp, vp, vp, vp, vp, vp, vp, vp],
             "hx_bgv_crt_encode": [vp, vp, ip, u64, vp, vp],
             "hx_bgv_crt_decode": [vp, vp, u64, vp],
@@ -752,13 +755,22 @@ def bgvEmbed(table, f):
 
 
 class BgvCrt:
-    """The CRT tables of one (Context, p) pair (hx_bgv_crt): the default EncryptedArray for any d = ord_m(p), slots in
-    Z_p.  d, nslots, gens, ords (signed: a non-native dimension's order negated), table_bytes."""
+    """The CRT tables of one (Context, p, r) triple (hx_bgv_crt): the default EncryptedArray for any d = ord_m(p), slots
+    in Z_p or, with r > 1, Hensel-lifted in Z_(p^r) (hx_bgv_crt_create_pr).  d, nslots, gens, ords (signed: a non-native
+    dimension's order negated), table_bytes; prime, r; p is the modulus p^r the maps work in."""
 
-    def __init__(self, context, p):
-        self.context, self.p = context, int(p)
+    def __init__(self, context, p, r=1):
+        self.context, self.prime, self.r = context, int(p), int(r)
         self.h = C.c_void_p()
-        _chk(lib().hx_bgv_crt_create(context.h, self.p, C.byref(self.h)))
+        if self.r == 1:
+            _chk(lib().hx_bgv_crt_create(context.h, self.prime, C.byref(self.h)))
+            self.p = self.prime
+        else:
+            _chk(lib().hx_bgv_crt_create_pr(context.h, self.prime, self.r, C.byref(self.h)))
+            rr, mod = C.c_int(), C.c_uint64()
+            _chk(lib().hx_bgv_crt_space(self.h, C.byref(rr), C.byref(mod)))
+            assert rr.value == self.r and mod.value == self.prime ** self.r
+            self.p = int(mod.value)
         d, ns, nd, tb = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
         g, o = (C.c_uint64 * 8)(), (C.c_int64 * 8)()
         _chk(lib().hx_bgv_crt_info(self.h, None, C.byref(d), C.byref(ns), C.byref(nd), g, o, C.byref(tb)))
@@ -1034,6 +1046,22 @@ def maskBlend(c0, c1, t0, t1, mask):
     if (c1 is None) != (t1 is None):
         raise InvalidArgument(HX_ERR_INVALID, "c1 and t1 go together (both None for a one-part ciphertext)")
     _chk(lib().hx_mask_blend(c0.h, c1.h if c1 is not None else None, t0.h, t1.h if t1 is not None else None, mask.h))
+
+
+def scaledSub(c0, c1, t0, t1, u, v):
+    """c = c * u[row] - t * v[row] on the one or two parts of a ciphertext in one pass (hx_scaled_sub): tmp -= digit;
+    tmp.divideByP() (src/extractDigits.cpp:106-107) with u = e1 / p and v = e2 / p modulo each prime of c0, in the order
+    of its rows (integers in [0, q)).  c1 / t1 = None for a one-part ciphertext; t* are read only."""
+    if (c1 is None) != (t1 is None):
+        raise InvalidArgument(HX_ERR_INVALID, "c1 and t1 go together (both None for a one-part ciphertext)")
+    u = np.array([int(x) for x in u], dtype=np.uint64)
+    v = np.array([int(x) for x in v], dtype=np.uint64)
+    n = len(c0.getIndexSet())
+    if len(u) != n or len(v) != n:
+        raise InvalidArgument(HX_ERR_INVALID, "scaledSub takes one u and one v per prime row of c0")
+    if n == 0:
+        return
+    _chk(lib().hx_scaled_sub(c0.h, c1.h if c1 is not None else None, t0.h, t1.h if t1 is not None else None, _p(u), _p(v)))
 
 
 def likeUninit(poly):

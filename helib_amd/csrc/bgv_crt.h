@@ -1,4 +1,4 @@
-// bgv_crt.h -- host tables of BGV slot encoding and decoding for any d = ord_m(p), r = 1, slots in Z_p: the
+// bgv_crt.h -- host tables of BGV slot encoding and decoding for any d = ord_m(p), slots in Z_p (r = 1) or Z_(p^r): the
 // default-constructed EncryptedArray (G = X, include/helib/EncryptedArray.h) over PAlgebraModDerived's constructor
 // (src/PAlgebra.cpp:680-772), restated without factoring polynomials.  Plain C++ (no device code): product code, unit
 // tested on the CPU like hostmath.h.
@@ -17,6 +17,15 @@
 //              branch :1243-1261): the sequence satisfies the recurrence whose characteristic polynomial is F_i
 // so  encode: H[k] = sum_i a_i E[i][k] mod p   and   decode: slot i = sum_k w[k] R[i][k] mod p.
 // Rows are ld = phi(m) rounded up to 4 words apart (zero filled), so that a row starts on a 16-byte boundary.
+//
+// r > 1 (slots in Z_(p^r)): the r > 1 branch of the same constructor (src/PAlgebra.cpp:757-763), where the factors
+// found and ordered modulo p (:705-733) are Hensel-lifted by PAlgebraLift (:840-881).  No polynomial is lifted by hand
+// here: the work moves to the Galois ring GR(p^r, d) = Z_(p^r)[y] / g with the same monic g (any lift of an
+// irreducible serves), and zeta is replaced by its Teichmueller lift  zeta~ = a^(p^(d (r - 1))),  a any lift of zeta:
+// it reduces to zeta (zeta^(p^d) = zeta) and has zeta~^m = 1 (a^m = 1 + p u, and (1 + p u)^(p^(r-1)) = 1 mod p^r).
+// The Frobenius lift maps zeta~ to zeta~^p, so prod_k (X - zeta~^(j p^k)) over a coset has coefficients in Z_(p^r),
+// divides X^m - 1 and reduces to F_i: it is the Hensel lift of F_i (which is unique).  E and R are the same formulas
+// modulo p^r; poly_comp still compares residues modulo p.  At r = 1 every step is the one above, word for word.
 #pragma once
 #include <stdint.h>
 
@@ -28,13 +37,15 @@
 
 namespace hxc {
 
-constexpr uint64_t CRT_MAX_P = 1ull << 31;            // table words are uint32 and a product of two fits 62 bits
+constexpr uint64_t CRT_MAX_P = 1ull << 31;            // table words are uint32 and a product of two fits 62 bits (bounds p^r)
 constexpr uint64_t CRT_MAX_TABLE_BYTES = 1ull << 30;  // each of E and R
 
 struct CrtTables {
   uint64_t m = 0, p = 0;
+  uint32_t r = 1;
+  uint64_t modulus = 0;                 // p^r: what the words of E, R and the factors are residues of
   uint32_t d = 0, nslots = 0, phim = 0, ld = 0;
-  uint64_t limit = 0;                   // terms a 64-bit accumulator takes between reductions: floor(2^64 / p^2)
+  uint64_t limit = 0;                   // terms a 64-bit accumulator takes between reductions: floor(2^64 / p^(2r))
   std::vector<uint64_t> gens;
   std::vector<int64_t> ords;            // signed: a non-native dimension's order negated
   std::vector<uint32_t> factors;        // [nslots][d + 1], constant coefficient first
@@ -113,7 +124,7 @@ inline void find_generators(uint64_t m, uint64_t p, std::vector<uint64_t>& gens,
   }
 }
 
-// ---- polynomials over Z_p, coefficients lowest first, p < 2^31 ----
+// ---- polynomials over Z_p, coefficients lowest first, p < 2^31 (Field::mul and poly_rem take any modulus) ----
 typedef std::vector<uint64_t> Poly;
 
 inline void trim(Poly& a)
@@ -149,7 +160,8 @@ inline Poly poly_gcd(Poly a, Poly b, uint64_t p)
   return a;
 }
 
-// GF(p^d) = Z_p[y] / g: elements are d words
+// GF(p^d) = Z_p[y] / g: elements are d words.  With p a prime power and g irreducible modulo the prime the same code
+// is the Galois ring GR(p, d) (mul, one, pow, is_one; is_irreducible and poly_gcd are for a prime only)
 struct Field {
   uint64_t p = 0;
   uint32_t d = 0;
@@ -316,15 +328,36 @@ inline void rem_phi(std::vector<uint32_t>& X, uint64_t m, uint32_t n, uint32_t p
     X[i] = X[i] >= W[i] ? X[i] - W[i] : X[i] + p - W[i];
 }
 
+// p^r, or 0 when it is not below CRT_MAX_P (or r < 1)
+inline uint64_t crt_modulus(uint64_t p, uint32_t r)
+{
+  uint64_t P = 1;
+  for (uint32_t i = 0; i < r; i++) {
+    if (p < 2 || P > (CRT_MAX_P - 1) / p)
+      return 0;
+    P *= p;
+  }
+  return r < 1 ? 0 : P;
+}
+
 // 0, or the reason the tables cannot be built.  tables = false: the geometry alone (m, p, d, nslots, gens, ords).
-inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables = true)
+// r: the tables are modulo p^r (the top of this file).
+inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables = true, uint32_t r = 1)
 {
   char msg[200];
   if (p < 2 || !hxh::is_prime(p))
     return "the plaintext modulus is not a prime";
+  if (r < 1)
+    return "the exponent r of the plaintext space p^r is less than 1";
   if (p >= CRT_MAX_P) {
     snprintf(msg, sizeof msg, "p = %llu: the CRT tables hold 32-bit words and take p < 2^31 = %llu", (unsigned long long)p,
              (unsigned long long)CRT_MAX_P);
+    return msg;
+  }
+  const uint64_t P = crt_modulus(p, r);
+  if (!P) {
+    snprintf(msg, sizeof msg, "p^r = %llu^%u: the CRT tables hold 32-bit words and take p^r < 2^31 = %llu",
+             (unsigned long long)p, r, (unsigned long long)CRT_MAX_P);
     return msg;
   }
   if (m < 2 || m >= (1ull << 24) || hxh::gcd(m, p) != 1)
@@ -332,7 +365,9 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
   t = CrtTables();
   t.m = m;
   t.p = p;
-  t.limit = lazy_limit(p);
+  t.r = r;
+  t.modulus = P;
+  t.limit = lazy_limit(P);
   uint32_t phim = 0;
   for (uint64_t j = 0; j < m; j++)
     phim += hxh::gcd(j, m) == 1;
@@ -381,21 +416,33 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
     if (ok)
       break;
   }
+  // from here on modulo P = p^r in G = Z_P[y] / g (r = 1: G is F and nothing changes); zeta becomes its Teichmueller
+  // lift a^(p^(d (r - 1))), a = zeta's own words
+  Field G = F;
+  G.p = P;
+  if (r > 1) {
+    hxh::BigU te(1);
+    for (uint32_t i = 0; i < d * (r - 1); i++)
+      te.mul_word(p);
+    zeta = G.pow(zeta, te.d);
+    if (!G.is_one(G.pow(zeta, m)))
+      return "internal: the lifted root of unity does not have order m";
+  }
   std::vector<uint64_t> zp((size_t)m * d);   // zeta^j
   {
-    Poly cur = F.one();
+    Poly cur = G.one();
     for (uint64_t j = 0; j < m; j++) {
       std::copy(cur.begin(), cur.end(), zp.begin() + j * d);
-      cur = F.mul(cur, zeta);
+      cur = G.mul(cur, zeta);
     }
   }
-  // traces: Tr(zeta^j) = sum_k zeta^(j p^k), an element of Z_p (its constant coordinate; the others cancel)
+  // traces: Tr(zeta^j) = sum_k zeta^(j p^k), an element of Z_P (its constant coordinate; the others cancel)
   std::vector<uint32_t> tr(m);
   for (uint64_t j = 0; j < m; j++) {
     uint64_t s = 0, x = j;
     for (uint32_t k = 0; k < d; k++, x = x * (p % m) % m)
       s += zp[x * d];
-    tr[j] = (uint32_t)(s % p);
+    tr[j] = (uint32_t)(s % P);
   }
   // the factor of every coset j<p> of Z_m^*, kept under its smallest element
   std::vector<uint32_t> coset(m, 0xffffffffu);
@@ -404,16 +451,16 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
   for (uint64_t j = 1; j < m; j++) {
     if (hxh::gcd(j, m) != 1 || coset[j] != 0xffffffffu)
       continue;
-    std::vector<Poly> f(1, F.one());   // the running product, coefficients in the field
+    std::vector<Poly> f(1, G.one());   // the running product, coefficients in the field
     uint64_t x = j;
     for (uint32_t k = 0; k < d; k++, x = x * (p % m) % m) {
       coset[x] = (uint32_t)j;
       const Poly root(zp.begin() + x * d, zp.begin() + (x + 1) * d);
-      f.push_back(F.one());   // times (X - root): f[i] = f[i - 1] - root f[i]
+      f.push_back(G.one());   // times (X - root): f[i] = f[i - 1] - root f[i]
       for (size_t i = f.size() - 1; i-- > 0;) {
-        Poly pr = F.mul(f[i], root);
+        Poly pr = G.mul(f[i], root);
         for (uint32_t c = 0; c < d; c++)
-          pr[c] = ((i > 0 ? f[i - 1][c] : 0) + p - pr[c]) % p;
+          pr[c] = ((i > 0 ? f[i - 1][c] : 0) + P - pr[c]) % P;
         f[i] = pr;
       }
     }
@@ -425,8 +472,11 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
           return "internal: a factor of Phi_m has a coefficient outside Z_p";
       out[i] = (uint32_t)f[i][0];
     }
-    if (!c0 || std::lexicographical_compare(out.begin(), out.end(), fac[c0].begin(), fac[c0].end()))
-      c0 = j;   // poly_comp: equal degrees, so the first differing coefficient from the constant one up decides
+    // poly_comp: equal degrees, so the first differing coefficient from the constant one up decides -- of the factors
+    // modulo p, which is where the reference orders them (:715-721) before it lifts
+    if (!c0 || std::lexicographical_compare(out.begin(), out.end(), fac[c0].begin(), fac[c0].end(),
+                                            [p](uint32_t a, uint32_t b) { return a % p < b % p; }))
+      c0 = j;
   }
   // slot i: the coset of c0 / t_i, t_i = ith_rep(i) (the last generator's exponent fastest)
   const size_t ng = t.gens.size();
@@ -436,7 +486,7 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
   t.factors.assign((size_t)n * (d + 1), 0);
   t.E.assign((size_t)n * t.ld, 0);
   t.R.assign((size_t)n * t.ld, 0);
-  const uint64_t minv = hxh::invmod(m % p, p);
+  const uint64_t minv = hxh::invmod(m % P, P);
   const PhiBinomials pb(m);
   std::vector<uint32_t> X(m), scratch;
   std::vector<uint8_t> seen(m, 0);
@@ -454,20 +504,20 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
     // E_i mod X^m - 1: (1/m) Tr(zeta^(-k u)), then mod Phi_m
     uint64_t at = 0;   // -k u mod m
     for (uint64_t k = 0; k < m; k++) {
-      X[k] = (uint32_t)(tr[at] * minv % p);
+      X[k] = (uint32_t)(tr[at] * minv % P);
       at = at >= u ? at - u : at + m - u;
     }
-    rem_phi(X, m, phim, (uint32_t)p, pb, scratch);
+    rem_phi(X, m, phim, (uint32_t)P, pb, scratch);
     std::copy(X.begin(), X.begin() + phim, t.E.begin() + (size_t)i * t.ld);
     // R_i[k] = [X^0] (X^k mod F_i): R[k + d] = -sum_j f_j R[k + j], from 1, 0, ..., 0
-    uint32_t* r = t.R.data() + (size_t)i * t.ld;
-    r[0] = 1 % p;
+    uint32_t* rw = t.R.data() + (size_t)i * t.ld;
+    rw[0] = 1 % P;
     for (uint32_t k = d; k < phim; k++) {
       hxh::u128 s = 0;
       for (uint32_t j = 0; j < d; j++)
-        s += (uint64_t)f[j] * r[k - d + j];
-      const uint64_t v = (uint64_t)(s % p);
-      r[k] = (uint32_t)(v ? p - v : 0);
+        s += (uint64_t)f[j] * rw[k - d + j];
+      const uint64_t v = (uint64_t)(s % P);
+      rw[k] = (uint32_t)(v ? P - v : 0);
     }
     // the next exponent vector
     for (size_t g = ng; g-- > 0;) {

@@ -1,5 +1,6 @@
-// bgv_crt.hip -- C ABI of BGV slot encoding and decoding for any d = ord_m(p) at r = 1, slots in Z_p (include/helib_amd.h:
-// hx_bgv_crt_create, hx_bgv_crt_encode, hx_bgv_crt_decode, hx_bgv_crt_embed): the default-constructed EncryptedArray
+// bgv_crt.hip -- C ABI of BGV slot encoding and decoding for any d = ord_m(p), slots in Z_p or, Hensel-lifted, in
+// Z_(p^r) (include/helib_amd.h: hx_bgv_crt_create, hx_bgv_crt_create_pr, hx_bgv_crt_encode, hx_bgv_crt_decode,
+// hx_bgv_crt_embed): the default-constructed EncryptedArray
 // (G = X) over PAlgebraMod (src/EncryptedArray.cpp, src/PAlgebra.cpp:680-772, 885-936, 1007-1045, 1243-1261).  For
 // d > 1 the plaintext prime is no transform prime of the ring, so there is no transform to borrow as bgv_slots.hip
 // does: the maps are two matrices modulo p built on the host (bgv_crt.h),
@@ -9,6 +10,10 @@
 // terms (floor(2^64 / p^2), per table), operand tiles staged through the LDS, 16-byte accesses along the rows of E, R
 // and the coefficients.  Around them the d = 1 path's own pieces (bgv_encode.h): bgv_lift_kernel and the engine's
 // forward transforms behind an encode, hxi::poly_rem_device and bgv_redmul_kernel in front of a decode.
+// At r > 1 the modulus of all of these is p^r < 2^31 (in the kernels' `p`; the table keeps the prime beside it).  None
+// of them needs a prime: bgv_red's quotient estimate floor(x mu / 2^64), mu = floor(2^64 / q), is short by at most 1
+// for any q >= 2, Shoup's product x w - floor(x ws / 2^64) q lies in [0, 2q) for any q and w < q, and the accumulators
+// are bounded by `limit` = floor(2^64 / p^(2r)).  The one place that knows the parity is the lift's balancing, below.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -167,7 +172,9 @@ bgv_crt_decode_kernel(const uint64_t* __restrict__ w, const uint32_t* __restrict
 
 }  // namespace hx
 
-struct hx_bgv_crt : hxb::SlotBase {
+struct hx_bgv_crt : hxb::SlotBase {   // SlotBase::p is the modulus p^r of the maps
+  uint64_t prime = 0;
+  uint32_t r = 1;
   uint32_t d = 0, nslots = 0, ld = 0, limit = 0;
   std::vector<uint64_t> gens;
   std::vector<int64_t> ords;   // signed
@@ -215,7 +222,7 @@ extern "C" int hx_bgv_crt_destroy(hx_bgv_crt* t)
   return HX_OK;
 }
 
-extern "C" int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out)
+extern "C" int hx_bgv_crt_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_crt** out)
 {
   if (!ctx || !out)
     return err(HX_ERR_INVALID, "null argument");
@@ -228,15 +235,21 @@ extern "C" int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out)
   const uint64_t m = v.m;
   if (p < 2 || !hxh::is_prime(p))
     return err(HX_ERR_INVALID, "the plaintext modulus p = %llu is not a prime", (unsigned long long)p);
+  if (r < 1)
+    return err(HX_ERR_INVALID, "the exponent r = %d of the plaintext space p^r is less than 1", r);
   if (p >= hxc::CRT_MAX_P)
     return err(HX_ERR_UNSUPPORTED, "p = %llu: the CRT tables hold 32-bit words and take p < 2^31 = %llu", (unsigned long long)p,
                (unsigned long long)hxc::CRT_MAX_P);
+  const uint64_t P = hxc::crt_modulus(p, (uint32_t)r);
+  if (!P)
+    return err(HX_ERR_UNSUPPORTED, "p^r = %llu^%d: the CRT tables hold 32-bit words and take p^r < 2^31 = %llu",
+               (unsigned long long)p, r, (unsigned long long)hxc::CRT_MAX_P);
   if (m % p == 0)
     return err(HX_ERR_INVALID, "p = %llu divides m = %llu", (unsigned long long)p, (unsigned long long)m);
   if (m < 3 || v.phim % 2 != 0)
     return err(HX_ERR_UNSUPPORTED, "BGV slots need m >= 3 (m = %llu)", (unsigned long long)m);
   hxc::CrtTables tab;
-  const std::string why = hxc::build_crt(m, p, tab);
+  const std::string why = hxc::build_crt(m, p, tab, true, (uint32_t)r);
   if (!why.empty())
     return err(why.rfind("internal", 0) == 0 ? HX_ERR_DEVICE : HX_ERR_UNSUPPORTED, "%s", why.c_str());
   if (tab.phim != v.phim)
@@ -248,7 +261,9 @@ extern "C" int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out)
   } guard{t};
   t->ctx = ctx;
   t->m = m;
-  t->p = p;
+  t->p = P;
+  t->prime = p;
+  t->r = (uint32_t)r;
   t->N = v.phim;
   t->device = v.device;
   t->d = tab.d;
@@ -267,13 +282,26 @@ extern "C" int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out)
   return HX_OK;
 }
 
+extern "C" int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out) { return hx_bgv_crt_create_pr(ctx, p, 1, out); }
+
+extern "C" int hx_bgv_crt_space(const hx_bgv_crt* t, int* r, uint64_t* modulus)
+{
+  if (!t)
+    return err(HX_ERR_INVALID, "null argument");
+  if (r)
+    *r = (int)t->r;
+  if (modulus)
+    *modulus = t->p;
+  return HX_OK;
+}
+
 extern "C" int hx_bgv_crt_info(const hx_bgv_crt* t, uint64_t* p, int* d, int* nslots, int* ndims, uint64_t* gens, int64_t* ords,
                                uint64_t* table_bytes)
 {
   if (!t)
     return err(HX_ERR_INVALID, "null argument");
   if (p)
-    *p = t->p;
+    *p = t->prime;
   if (d)
     *d = (int)t->d;
   if (nslots)

@@ -25,7 +25,8 @@ constexpr int BGV_MAXPRIMES = 512;       // rows of an encode's output (the chai
 constexpr unsigned BGV_MAX_BLOCKS = 2048;
 constexpr uint32_t BGV_NO_SLOT = 0xffffffffu;
 
-// x mod q for any x < 2^64, mu = floor(2^64 / q): the quotient estimate is short by at most 1 (q >= 3)
+// x mod q for any x < 2^64 and any modulus q >= 2 (prime or not), mu = floor(2^64 / q): the quotient estimate is short
+// by at most 1
 __device__ __forceinline__ uint64_t bgv_red(uint64_t x, uint64_t q, uint64_t mu)
 {
   uint64_t r = x - __umul64hi(x, mu) * q;
@@ -153,8 +154,12 @@ bgv_redmul_kernel(const int64_t* __restrict__ in, size_t words, uint64_t p, uint
   }
 }
 
-// The lift: c = balanced(mul * h[i] mod p) in (-p/2, p/2) (p odd: no tie), rows[r][i] = c mod q_r for the L primes
-// qm[r] = (q_r, floor(2^64 / q_r)); coeffs (optional) receives c itself.  One read, L coalesced writes.
+// The lift: c = balanced(mul * h[i] mod p) in (-p/2, p/2], rows[r][i] = c mod q_r for the L primes
+// qm[r] = (q_r, floor(2^64 / q_r)); coeffs (optional) receives c itself.  One read, L coalesced writes.  p is any
+// modulus below 2^63 (a prime, or p^r for Hensel-lifted slots).  An odd p has no tie.  At an even p a word equal to
+// p/2 stays +p/2: the reference's balanced_zzX and balanced_MulMod draw that sign at random (src/zzX.cpp:122-137,
+// 156-170; for p = 2, where every 1 is such a word, :139-154), both signs being the same residue; the project takes
+// the positive one always, so that an encoding is a function of its input.
 template <int V>
 __global__ void __launch_bounds__(256)
 bgv_lift_kernel(const uint64_t* __restrict__ h, size_t words, uint64_t p, uint64_t mul, uint64_t muls,

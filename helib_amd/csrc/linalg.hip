@@ -7,10 +7,14 @@
 // (src/EncryptedArray.cpp:270-274: tmp = ctxt; tmp.multByConstant(mask); ctxt -= tmp), in one pass as well; and of the
 // tail of the non-native rotate1D (hx_mask_blend):
 //   c = c * mask + t - t * mask
-// (src/EncryptedArray.cpp:120-124), one pass instead of four.  The unit
+// (src/EncryptedArray.cpp:120-124), one pass instead of four; and of the inner step of digit extraction
+// (hx_scaled_sub):
+//   c = c * u - t * v,  u and v one scalar per prime row
+// (src/extractDigits.cpp:106-107: tmp -= digits[j]; tmp.divideByP()), one pass instead of four.  The unit
 // reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdio>
 #include <mutex>
@@ -19,6 +23,7 @@
 #include "../../include/helib_amd.h"
 #include "ckks_bridge.h"
 #include "dev_common.h"
+#include "hostmath.h"
 #include "prof.h"
 
 namespace hx {
@@ -240,6 +245,68 @@ mask_blend_kernel(uint64_t* __restrict__ c0, uint64_t* __restrict__ c1, const ui
     if (PARTS == 2) {
       r.x = add_mod(mul_mod(sub_mod(x1[b].x, y1[b].x, q), c.x, q, mu, k), y1[b].x, q);
       r.y = add_mod(mul_mod(sub_mod(x1[b].y, y1[b].y, q), c.y, q, mu, k), y1[b].y, q);
+      st_stream2(c1 + row_off + boff[b], r);
+    }
+  }
+}
+
+// Per-row scalars of one scaled_sub_kernel launch, by value (the kernel-argument segment holds 4 KiB, so a launch takes
+// SS_ROWS rows and the host issues one per SS_ROWS rows of the operand)
+constexpr int SS_ROWS = 48;
+struct ScaledSubRows {
+  uint16_t p[SS_ROWS];                              // prime index of row row_base + r
+  uint64_t u[SS_ROWS], up[SS_ROWS];                 // u in [0, q) and its Shoup companion floor(u 2^64 / q)
+  uint64_t v[SS_ROWS], vp[SS_ROWS];
+};
+static_assert(sizeof(ScaledSubRows) + 64 <= 4096, "the scalars travel as kernel arguments");
+
+// c = c * u[row] - t * v[row] (hx_scaled_sub): the words hx_mul_scalar(c, u), hx_poly_copy(t', t), hx_mul_scalar(t', v),
+// hx_sub(c, t') leave in c.  Every operand is canonical and mul_shoup returns the canonical product, so sub_mod of the
+// two products is that word.  t is read only.  The thread shape is mask_blend_kernel's: two adjacent coefficients of
+// one prime row for BP batch elements, PARTS * BP vectors of c and of t loaded (16 bytes each, non-temporal: every word
+// is read once) and PARTS * BP vectors stored; the four scalars of the row are wave-uniform reads of the kernel
+// arguments.  HBM bound: per part 16 B read and 8 B written per coefficient, against 40 B read and 32 B written by the
+// four calls.  No LDS.  All addresses and scalars are kernel arguments, so a launch can be captured.
+template <int PARTS, int BP>
+__global__ void __launch_bounds__(256)
+scaled_sub_kernel(uint64_t* __restrict__ c0, uint64_t* __restrict__ c1, const uint64_t* __restrict__ t0,
+                  const uint64_t* __restrict__ t1, int batch, uint32_t N, int row_base, ScaledSubRows rows,
+                  const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const uint64_t q = primes[rows.p[row]].q;
+  const uint64_t u = rows.u[row], up = rows.up[row], v = rows.v[row], vp = rows.vp[row];
+  const size_t row_off = (size_t)(row_base + row) * batch * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  ulonglong2 x0[BP], x1[BP], y0[BP], y1[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    x0[b] = ld_stream2(c0 + row_off + boff[b]);
+    y0[b] = ld_stream2(t0 + row_off + boff[b]);
+    if (PARTS == 2) {
+      x1[b] = ld_stream2(c1 + row_off + boff[b]);
+      y1[b] = ld_stream2(t1 + row_off + boff[b]);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    ulonglong2 r;
+    r.x = sub_mod(mul_shoup(x0[b].x, u, up, q), mul_shoup(y0[b].x, v, vp, q), q);
+    r.y = sub_mod(mul_shoup(x0[b].y, u, up, q), mul_shoup(y0[b].y, v, vp, q), q);
+    st_stream2(c0 + row_off + boff[b], r);
+    if (PARTS == 2) {
+      r.x = sub_mod(mul_shoup(x1[b].x, u, up, q), mul_shoup(y1[b].x, v, vp, q), q);
+      r.y = sub_mod(mul_shoup(x1[b].y, u, up, q), mul_shoup(y1[b].y, v, vp, q), q);
       st_stream2(c1 + row_off + boff[b], r);
     }
   }
@@ -661,6 +728,93 @@ extern "C" int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const 
   else
     launch_blend<1>(bp, grid, v.stream, d[0], nullptr, s0, nullptr, mp, per_elem, batch, N, map, primes);
   CK(hipGetLastError());
+  return HX_OK;
+}
+
+template <int PARTS>
+static void launch_scaled_sub(int bp, dim3 grid, hipStream_t st, uint64_t* c0, uint64_t* c1, const uint64_t* t0,
+                              const uint64_t* t1, int batch, uint32_t N, int row_base, const hx::ScaledSubRows& rows,
+                              const hx::PrimeDev* primes)
+{
+  if (bp == 1)
+    HX_LAUNCH((hx::scaled_sub_kernel<PARTS, 1>), grid, dim3(256), 0, st, c0, c1, t0, t1, batch, N, row_base, rows, primes);
+  else
+    HX_LAUNCH((hx::scaled_sub_kernel<PARTS, 4>), grid, dim3(256), 0, st, c0, c1, t0, t1, batch, N, row_base, rows, primes);
+}
+
+extern "C" int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const uint64_t* u_per_row,
+                             const uint64_t* v_per_row)
+{
+  if (!c0 || !t0 || !u_per_row || !v_per_row)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((c1 == nullptr) != (t1 == nullptr))
+    return err(HX_ERR_INVALID, "c1 and t1 go together (both null for a one-part ciphertext)");
+  const int parts = c1 ? 2 : 1;
+  const hx_poly* ops[4] = {c0, t0, c1, t1};
+  for (int a = 0; a < 2 * parts; a++)
+    for (int b = a + 1; b < 2 * parts; b++)
+      if (ops[a] == ops[b])
+        return err(HX_ERR_INVALID, "c0, c1, t0 and t1 must be different polys");
+  hx_ctx* ctx = hxi::poly_ctx(c0);
+  for (int a = 1; a < 2 * parts; a++)
+    if (hxi::poly_ctx(ops[a]) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  int batch = 0, b2 = 0;
+  std::vector<int> idx, other;
+  RC(shape_of(c0, &batch, &idx));
+  const int rows = (int)idx.size();
+  if (rows > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  static const char* const name[4] = {"c0", "t0", "c1", "t1"};
+  for (int a = 1; a < 2 * parts; a++) {
+    RC(shape_of(ops[a], &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "%s differs from c0 in batch or prime set", name[a]);
+  }
+  const uint32_t N = v.phim;
+  if (N < 2 || (N & 1))
+    return err(HX_ERR_UNSUPPORTED, "hx_scaled_sub needs an even number of coefficients");
+  std::vector<uint64_t> qs(rows);
+  for (int r = 0; r < rows; r++) {
+    RC(hx_ctx_prime(ctx, idx[r], &qs[r], nullptr));
+    if (u_per_row[r] >= qs[r] || v_per_row[r] >= qs[r])
+      return err(HX_ERR_INVALID, "row %d: the scalars are not reduced modulo the row's prime %llu", r,
+                 (unsigned long long)qs[r]);
+  }
+  if (rows == 0)
+    return HX_OK;
+  // c first: one that still shares t's rows (a lazy hx_poly_copy) takes its own copy, and t's rows stay where they are
+  uint64_t* d[2] = {nullptr, nullptr};
+  RC(hxi::poly_rows_update(c0, &d[0]));
+  if (c1)
+    RC(hxi::poly_rows_update(c1, &d[1]));
+  const uint64_t* s0 = hxi::poly_rows_read(t0);
+  const uint64_t* s1 = t1 ? hxi::poly_rows_read(t1) : nullptr;
+  if (((uint64_t)(uintptr_t)d[0] | (uint64_t)(uintptr_t)d[1] | (uint64_t)(uintptr_t)s0 | (uint64_t)(uintptr_t)s1) & 15)
+    return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
+  const int bp = batch == 1 ? 1 : 4;
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  for (int base = 0; base < rows; base += hx::SS_ROWS) {
+    const int nr = std::min(rows - base, (int)hx::SS_ROWS);
+    hx::ScaledSubRows sr{};
+    for (int r = 0; r < nr; r++) {
+      const uint64_t q = qs[base + r];
+      sr.p[r] = (uint16_t)idx[base + r];
+      sr.u[r] = u_per_row[base + r];
+      sr.up[r] = hxh::shoup(sr.u[r], q);
+      sr.v[r] = v_per_row[base + r];
+      sr.vp[r] = hxh::shoup(sr.v[r], q);
+    }
+    const dim3 grid((N / 2 + 255) / 256, (unsigned)nr, (unsigned)((batch + bp - 1) / bp));
+    if (parts == 2)
+      launch_scaled_sub<2>(bp, grid, v.stream, d[0], d[1], s0, s1, batch, N, base, sr, primes);
+    else
+      launch_scaled_sub<1>(bp, grid, v.stream, d[0], nullptr, s0, nullptr, batch, N, base, sr, primes);
+    CK(hipGetLastError());
+  }
   return HX_OK;
 }
 

@@ -740,6 +740,98 @@ class Ctxt:
             p.mulConstant(bal)
         self.lnNoise = self.lnNoise + math.log(abs(bal))
 
+    def effectiveR(self):
+        """Ctxt::effectiveR (src/Ctxt.cpp:103-114): the r with ptxtSpace = p^r"""
+        p = self.context.p
+        r, p2r = 1, p
+        while r < HELIB_SP_NBITS:
+            if p2r == self.ptxtSpace:
+                return r
+            if p2r > self.ptxtSpace:
+                break
+            r, p2r = r + 1, p2r * p
+        raise RuntimeError("ctxt.ptxtSpace is not of the form p^r")
+
+    def divideByP(self):
+        """Ctxt::divideByP (src/Ctxt.cpp:2415-2435): for a ciphertext whose plaintext is 0 mod p -- every part times
+        p^-1 mod Q (Q the product of the prime set), the noise and the plaintext space divided by p, intFactor reduced
+        to the new space.  The reference's two asserts are errors here."""
+        if not self.parts:
+            return self
+        p = self.context.p
+        if self.ptxtSpace % p != 0:
+            raise RuntimeError("p must divide ptxtSpace")
+        if self.ptxtSpace <= p:
+            raise RuntimeError("ptxtSpace must be strictly greater than p")
+        self._materializeTensor()
+        pInverse = pow(p, -1, self.context.productOfPrimes(self.primeSet))
+        for part in self.parts.values():
+            part.mulConstant(pInverse)
+        self.lnNoise = self.lnNoise - math.log(p)
+        self.ptxtSpace //= p
+        self.intFactor %= self.ptxtSpace
+        return self
+
+    def multByP(self, e=1):
+        """Ctxt::multByP (include/helib/Ctxt.h:1216-1221): the plaintext space grows to p^(r+e), then
+        multByConstant(p^e)"""
+        p2e = self.context.p ** e
+        self.ptxtSpace *= p2e
+        return self.multByScalar(p2e)
+
+    fuseScaledSub = False  # fused=None: the two calls until hx_scaled_sub has been measured as the faster form (DESIGN 3.9j)
+
+    def subDivideByP(self, other, fused=None):
+        """*this -= other; this->divideByP() -- the inner step of extractDigits (src/extractDigits.cpp:106-107).
+        Fused: addCtxt's own preparation (_alignForAdd: the plaintext spaces' gcd, the union of the prime sets, the
+        intFactor pair e1, e2), then one ops.scaledSub (hx_scaled_sub) with u = balanced(e1) / p and
+        v = balanced(e2) / p modulo every prime in place of mulIntFactor on both sides, the subtraction and the
+        product by p^-1 mod Q; the bookkeeping of the two calls is done here, float operation for float operation.  It
+        applies when both sides hold the canonical parts {1, s} or the same single part and divideByP's conditions
+        hold; otherwise, and with fused=False, the two calls run as they are.  fused=True insists on a backend with
+        scaledSub; fused=None follows Ctxt.fuseScaledSub.  The words, lnNoise, primeSet, ptxtSpace and intFactor are
+        the same either way; `other` is left as it was either way."""
+        has = hasattr(self.ops, "scaledSub")
+        if fused and not has:
+            raise RuntimeError("Ctxt::subDivideByP: fused=True, but this backend has no scaledSub")
+        want = (Ctxt.fuseScaledSub if fused is None else fused) and has
+        ctx = self.context
+        p = ctx.p
+        g = math.gcd(self.ptxtSpace, other.ptxtSpace)
+        can = (want and not ctx.ckks and other is not self and self.parts and other.parts
+               and g % p == 0 and g > p)
+        if can:
+            self._materializeTensor()
+            other._materializeTensor()
+            hs = list(self.parts)
+            can = sorted(hs) == sorted(other.parts) and (len(hs) == 1 or sorted(hs) == ["1", "s"])
+        if not can:
+            self -= other
+            return self.divideByP()
+        o, _, e1, e2 = self._alignForAdd(other)
+        P = self.ptxtSpace
+        bal = lambda e: e - P if e > P // 2 else e                     # noqa: E731  (mulIntFactor's)
+        idx = self.parts[hs[0]].getIndexSet()
+        pInverse = pow(p, -1, ctx.productOfPrimes(self.primeSet))
+        u = [bal(e1) * pInverse % ctx.primes[i] for i in idx]
+        v = [bal(e2) * pInverse % ctx.primes[i] for i in idx]
+        if len(hs) == 2:
+            self.ops.scaledSub(self.parts["1"], self.parts["s"], o.parts["1"], o.parts["s"], u, v)
+        else:
+            self.ops.scaledSub(self.parts[hs[0]], None, o.parts[hs[0]], None, u, v)
+        oln = o.lnNoise
+        if e2 != 1:                                                    # o.mulIntFactor(e2): the bound alone
+            oln = oln + math.log(abs(bal(e2)))
+        if e1 != 1:                                                    # self.mulIntFactor(e1)
+            self.intFactor = self.intFactor * e1 % P
+            self.lnNoise = self.lnNoise + math.log(abs(bal(e1)))
+        self.ptxtMag += o.ptxtMag                                      # the subtraction
+        self.lnNoise = logaddexp(self.lnNoise, oln)
+        self.lnNoise = self.lnNoise - math.log(p)                      # divideByP
+        self.ptxtSpace //= p
+        self.intFactor %= self.ptxtSpace
+        return self
+
     def negate(self):
         for p in self.parts.values():
             p.Negate()
@@ -800,7 +892,6 @@ class Ctxt:
         both operands mod-switched UP to the union of their prime sets, CKKS factors equalised,
         BGV intFactors harmonised by the (e1, e2) of least noise along the extended Euclidean
         sequence, then the parts added handle by handle."""
-        ctx = self.context
         if not other.parts:
             return
         if not self.parts:
@@ -809,6 +900,31 @@ class Ctxt:
             if negative:
                 self.negate()
             return
+        o, owned, e1, e2 = self._alignForAdd(other)
+        if e2 != 1:
+            if not owned:
+                o = other.clone()
+            o.mulIntFactor(e2)
+        if e1 != 1:
+            self.mulIntFactor(e1)
+        for h, p in o.parts.items():
+            if h in self.parts:
+                if negative:
+                    self.parts[h] -= p
+                else:
+                    self.parts[h] += p
+            else:
+                self.parts[h] = p.copy()
+                if negative:
+                    self.parts[h].Negate()
+        self.ptxtMag += o.ptxtMag
+        self.lnNoise = logaddexp(self.lnNoise, o.lnNoise)
+
+    def _alignForAdd(self, other):
+        """addCtxt up to the sum itself (src/Ctxt.cpp:1428-1526), both sides with parts: the plaintext spaces' gcd,
+        the union of the prime sets, the CKKS factors, and the (e1, e2) that harmonise the BGV intFactors, not yet
+        applied.  -> (o, owned, e1, e2): o is `other`, or (owned) a clone where it had to change."""
+        ctx = self.context
         o = other
         owned = False
 
@@ -854,22 +970,7 @@ class Ctxt:
                         e1, e2, best = a, b, cand
             assert e1 * self.intFactor % P == e2 * o.intFactor % P
             assert math.gcd(e1, P) == 1 and math.gcd(e2, P) == 1
-        if e2 != 1:
-            own().mulIntFactor(e2)
-        if e1 != 1:
-            self.mulIntFactor(e1)
-        for h, p in o.parts.items():
-            if h in self.parts:
-                if negative:
-                    self.parts[h] -= p
-                else:
-                    self.parts[h] += p
-            else:
-                self.parts[h] = p.copy()
-                if negative:
-                    self.parts[h].Negate()
-        self.ptxtMag += o.ptxtMag
-        self.lnNoise = logaddexp(self.lnNoise, o.lnNoise)
+        return o, owned, e1, e2
 
     @staticmethod
     def computeIntervalForMul(c1, c2):

@@ -390,7 +390,7 @@ typedef struct hx_bgv_diag {
 int hx_bgv_encode_diagonals(const hx_bgv_slots* t, const hx_bgv_matrix* a, const hx_bgv_diag* d, int ndiag, hx_poly* out,
                             int64_t* coeffs_out, int* nonzero_out);
 
-/* ---------------- BGV slots for any d = ord_m(p), r = 1: integer slots mod p (bgv_crt.hip) ----------------
+/* ---------------- BGV slots for any d = ord_m(p): integer slots mod p, or mod p^r (bgv_crt.hip) ----------------
  * The default-constructed EncryptedArray (G = X, include/helib/EncryptedArray.h): Phi_m mod p has nslots = phi(m) / d
  * factors of degree d and a slot holds an integer mod p.  Factor 0 is the smallest by poly_comp
  * (src/PAlgebra.cpp:67-81, 715-721), factor i the minimal polynomial of X^(1/t_i) mod F_0, t_i = ith_rep(i) of
@@ -400,11 +400,21 @@ int hx_bgv_encode_diagonals(const hx_bgv_slots* t, const hx_bgv_matrix* a, const
  * Any ring the context itself supports; all calls synchronise the context's stream and fail with HX_ERR_INVALID
  * under an open graph capture. */
 typedef struct hx_bgv_crt hx_bgv_crt; /* the tables of one (context, p) pair */
-/* Replaces PAlgebraModDerived's constructor at r = 1 (src/PAlgebra.cpp:680-772).  p not a prime, or p | m:
+/* Replaces PAlgebraModDerived's constructor at r = 1 (src/PAlgebra.cpp:680-772; hx_bgv_crt_create_pr takes any r).  p not a prime, or p | m:
  * HX_ERR_INVALID.  A prime p >= 2^31 (the tables hold 32-bit words), a table above 1 GiB, m < 3: HX_ERR_UNSUPPORTED,
  * the message gives the figure.  Any d is accepted, d = 1 included.  Destroy the table before its context. */
 int hx_bgv_crt_create(hx_ctx* ctx, uint64_t p, hx_bgv_crt** out);
+/* The same constructor for the plaintext space p^r, r >= 1 (its r > 1 branch, src/PAlgebra.cpp:757-763 over
+ * PAlgebraLift, :840-881): the factors are found and ordered modulo p as above and Hensel-lifted, E and R are the
+ * same two matrices modulo p^r, and a slot holds an integer mod p^r.  hx_bgv_crt_encode, _decode and _embed then work
+ * modulo p^r wherever their descriptions say p (mul and factor_inv are reduced mod p^r); at an even p^r a coefficient
+ * equal to p^r / 2 is encoded as +p^r / 2 (the reference draws its sign at random, src/zzX.cpp:122-137).  The tables
+ * reduced mod p^k, k < r, are the tables of p^k.  r = 1 is hx_bgv_crt_create, table for table.  r < 1: HX_ERR_INVALID;
+ * p^r >= 2^31: HX_ERR_UNSUPPORTED with the figure; otherwise the errors of hx_bgv_crt_create. */
+int hx_bgv_crt_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_crt** out);
 int hx_bgv_crt_destroy(hx_bgv_crt* t);
+/* The exponent r and the modulus p^r of the table's maps (hx_bgv_crt_info gives p); either output may be NULL. */
+int hx_bgv_crt_space(const hx_bgv_crt* t, int* r, uint64_t* modulus);
 /* p, d, nslots, the hypercube of Z_m^* / <p> -- ndims generators with their orders, a non-native dimension's order
  * negated as Context::writeTo stores it (src/PAlgebra.cpp:470-507; at most 8 are written) -- and the bytes of E and
  * R together; any output may be NULL. */
@@ -528,6 +538,22 @@ int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_poly* take1
  * context's stream and may be recorded in a graph capture.  Per part, in passes over the part, the four calls read 6
  * and write 4 (and read the mask twice); this call reads 2 and writes 1 (and reads the mask once). */
 int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const hx_poly* mask);
+/* The inner step of digit extraction (src/extractDigits.cpp:106-107:
+ *   tmp -= digits[j];  tmp.divideByP();)
+ * on the parts of one ciphertext, in one pass:  c = c * u[row] - t * v[row],  row by row modulo each prime.  After
+ * Ctxt::addCtxt's intFactor harmonisation (src/Ctxt.cpp:1474-1536) the subtraction is e1 * tmp - e2 * digit and
+ * Ctxt::divideByP (:2415-2435) multiplies by p^-1 mod Q, so the caller passes u = e1 * p^-1 and v = e2 * p^-1 modulo
+ * each prime of c0, in the order of its rows.  Every word is canonical in [0, q) and equal to what
+ * hx_mul_scalar(c, u), hx_poly_copy(t', t), hx_mul_scalar(t', v), hx_sub(c, t') leave in c.  t is read, not written.
+ * c1 and t1 are both null for a one-part operand.  t0 / t1 have the batch and the prime set (same order) of c0 / c1.
+ * Null arguments, c and t (or the two parts) being one poly, a poly of another context, mismatched shapes and a scalar
+ * that is not below its row's prime are HX_ERR_INVALID; an odd phi(m) is HX_ERR_UNSUPPORTED; a refused call touches no
+ * operand.  A c that still shares its rows with t (a lazy hx_poly_copy) takes its own copy first.  Pointers and
+ * scalars travel as kernel arguments (one launch per 48 rows): the call is asynchronous on the context's stream and
+ * may be recorded in a graph capture.  Per part, in passes over the part, the four calls read 5 and write 4; this call
+ * reads 2 and writes 1. */
+int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const uint64_t* u_per_row,
+                  const uint64_t* v_per_row);
 
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
