@@ -11,7 +11,10 @@ helib_amd/csrc/bgv_crt.h: no Galois ring, no roots of unity, no traces.
   encode        sum_i a_i E_i mod p^r, times mul, balanced into (-p^r/2, p^r/2]: at an even modulus the reference draws
                 the sign of a coefficient equal to p^r/2 at random (src/zzX.cpp:122-137); the project keeps +p^r/2
   decode        slot i = sum_k h_k R[i][k] mod p^r, reduced mod p^k for a ciphertext whose space is p^k
-Coefficients are lowest first."""
+Coefficients are lowest first.
+
+Beside the tables, the two references the host and the device tests share: scaled_sub (hx_scaled_sub's words) and replay
+(the digit extraction loop on plain integers)."""
 import functools
 
 import numpy as np
@@ -114,7 +117,69 @@ class Tables:
         h = np.array([[int(v) % self.P for v in row] for row in h], dtype=object)
         return np.array(h.dot(self._R.T) % Pk, dtype=np.int64)
 
+    def worst_sums(self):
+        """(encode, decode): the largest sums a kernel that never reduced would have to hold when every input word is
+        p^r - 1 -- max over the coefficients k of sum_i (p^r - 1) E[i][k], max over the slots i of
+        sum_k (p^r - 1) R[i][k].  Above 2^64 a dropped or late reduction of the 64-bit accumulator wraps."""
+        top = self.P - 1
+        return top * int(max(self._E.sum(axis=0))), top * int(max(self._R.sum(axis=1)))
+
+    def kernel_replay(self, kind, x, drop=False, late=0):
+        """What a 64-bit accumulator gives for x = slots ("encode": [B, nslots] -> [B, phim]) or coefficients ("decode":
+        [B, phim] -> [B, nslots]) when it counts as bgv_crt_encode_kernel / bgv_crt_decode_kernel do: terms four at a
+        time in steps of 16 slots / 32 coefficients (the padding of the last step counts down as well), left = limit at
+        the start, left -= 4 after every four terms and, once left < 4, a reduction mod p^r and left = limit + late.
+        drop: the reduction inside the loop never happens.  The sums wrap modulo 2^64; the result is reduced once at the
+        end, so with drop = False and late = 0 it is the residue encode / decode start from.  A modulus that divides
+        2^64 keeps its residue through a wrap: there no miscount can show."""
+        P, M = self.P, (1 << 64) - 1
+        limit = min((1 << 64) // (P * P), 0xffffffff)
+        T, step = (self._E, 16) if kind == "encode" else (self._R.T, 32)      # [terms, outputs]
+        x = np.array([[int(v) % P for v in row] for row in np.atleast_2d(np.asarray(x, dtype=object))], dtype=object)
+        acc = np.zeros((x.shape[0], T.shape[1]), dtype=object)
+        left = limit
+        for g in range(0, (T.shape[0] + step - 1) // step * step, 4):
+            if g < T.shape[0]:
+                acc = (acc + x[:, g:g + 4].dot(T[g:g + 4])) & M
+            left -= 4
+            if left < 4:
+                if not drop:
+                    acc = acc % P
+                left = limit + late
+        return np.array(acc % P, dtype=np.int64)
+
 
 @functools.lru_cache(maxsize=None)
 def tables(m, p, r):
     return Tables(m, p, r)
+
+
+def scaled_sub(c_rows, t_rows, u, v, qs):
+    """hx_scaled_sub in python integers: row i of the result is (c_rows[i] * u[i] - t_rows[i] * v[i]) mod qs[i], word for
+    word, as an object array of the shape of c_rows (row i may have any shape)"""
+    c = np.asarray(c_rows).astype(object)
+    t = np.asarray(t_rows).astype(object)
+    assert c.shape == t.shape and len(c) == len(u) == len(v) == len(qs)
+    out = np.empty_like(c)
+    for i, q in enumerate(qs):
+        out[i] = (c[i] * int(u[i]) - t[i] * int(v[i])) % int(q)
+    return out
+
+
+def replay(a, p, r):
+    """the loop of src/extractDigits.cpp:90-124 on plain integers: [(values, modulus)]"""
+    P = p ** r
+    dig = []
+    for i in range(r):
+        tmp, M = np.array([int(x) % P for x in a], dtype=object), P
+        for j in range(i):
+            v, Mj = dig[j]
+            v = v ** p % Mj
+            dig[j] = (v, Mj)
+            assert Mj == M
+            tmp = tmp - v
+            assert not any(int(x) % p for x in tmp)
+            M //= p
+            tmp = np.array([int(x) // p % M for x in tmp], dtype=object)
+        dig.append((tmp, M))
+    return dig

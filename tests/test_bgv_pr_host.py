@@ -324,23 +324,46 @@ def test_sub_divide_by_p_equals_the_two_calls(which, request):
     _same(_state(c), _state(two))
 
 
-def _replay(a, p, r):
-    """the loop of src/extractDigits.cpp:90-124 on plain integers: [(values, modulus)]"""
-    P = p ** r
-    dig = []
-    for i in range(r):
-        tmp, M = np.array([int(x) % P for x in a], dtype=object), P
-        for j in range(i):
-            v, Mj = dig[j]
-            v = v ** p % Mj
-            dig[j] = (v, Mj)
-            assert Mj == M
-            tmp = tmp - v
-            assert not any(int(x) % p for x in tmp)
-            M //= p
-            tmp = np.array([int(x) // p % M for x in tmp], dtype=object)
-        dig.append((tmp, M))
-    return dig
+_replay = R.replay       # the loop of src/extractDigits.cpp:90-124 on plain integers (shared with the device tests)
+
+
+def test_the_scaled_sub_reference_is_the_stand_in_of_the_oracle_backend(s3):
+    """tests/bgv_pr_ref.scaled_sub (what the device tests hold hx_scaled_sub against) and Ops.scaledSub above (what the
+    host tests run subDivideByP over) are one function: two parts and one, five of the chain's primes in another order
+    than the context's, u and v with 0, 1 and q - 1 among them"""
+    from oracle.backend import OPoly
+    o, ops = s3.be.o, s3.be.ops
+    idx = list(range(len(o.primes)))[::-1][:5]
+    idx[1], idx[3] = idx[3], idx[1]
+    qs = [o.primes[i] for i in idx]
+    rng = np.random.default_rng(21)
+    n = 32
+
+    def rnd():
+        x = np.stack([rng.integers(0, q, size=n, dtype=np.uint64) for q in qs])
+        x[0, :3] = [0, 1, qs[0] - 1]
+        x[-1, -1] = qs[-1] - 1
+        return x
+    c0, c1, t0, t1 = rnd(), rnd(), rnd(), rnd()
+    u = [0, 1, qs[2] - 1] + [int(rng.integers(0, q)) for q in qs[3:]]
+    v = [int(rng.integers(0, q)) for q in qs[:2]] + [qs[2] - 1, 0, 1]
+    want = [R.scaled_sub(c, t, u, v, qs) for c, t in ((c0, t0), (c1, t1))]
+    assert all(0 <= int(x) < q for w in want for row, q in zip(w, qs) for x in row)
+    # one row by hand
+    assert int(want[0][2][5]) == (int(c0[2][5]) * (qs[2] - 1) - int(t0[2][5]) * (qs[2] - 1)) % qs[2]
+    pc = [OPoly(o, idx, c0.copy()), OPoly(o, idx, c1.copy())]
+    pt = [OPoly(o, idx, t0.copy()), OPoly(o, idx, t1.copy())]
+    n_calls = len(s3.calls)
+    ops.scaledSub(pc[0], pc[1], pt[0], pt[1], u, v)
+    assert s3.calls[n_calls:] == [(u, v)]
+    del s3.calls[n_calls:]
+    for got, w in zip(pc, want):
+        assert np.array_equal(got.rows, w.astype(np.uint64))
+    assert np.array_equal(pt[0].rows, t0) and np.array_equal(pt[1].rows, t1)
+    one = OPoly(o, idx, c0.copy())
+    ops.scaledSub(one, None, pt[1], None, v, u)
+    del s3.calls[n_calls:]
+    assert np.array_equal(one.rows, R.scaled_sub(c0, t1, v, u, qs).astype(np.uint64))
 
 
 @pytest.mark.parametrize("which,fused", [("s2", False), ("s3", False), ("s2", True), ("s3", True)])
