@@ -15,8 +15,8 @@ the kernels are those of r = 1, and at r = 1 the class is helib_amd.bgv_hypercub
                       Ctxt.subDivideByP, one hx_scaled_sub with fused=True
 
 Out of scope, refused with LogicError and a message: helib_amd.bgv_matmul and bgv_gf_matmul over this class at r > 1,
-GF(p^d) slots at r > 1 (helib_amd.bgv_gf refuses), p > 3 in extractDigits (polyEval and buildDigitPolynomial,
-src/extractDigits.cpp:28-56, are not built), extendExtractDigits.  Nothing here imports oracle/."""
+GF(p^d) slots at r > 1 (helib_amd.bgv_gf refuses), p > 3 in this module's extractDigits (helib_amd.polyeval has polyEval,
+buildDigitPolynomial, an extractDigits for any p and extendExtractDigits).  Nothing here imports oracle/."""
 import numpy as np
 
 from . import bgv, bgv_crt, bgv_hypercube, capi, hostnt
@@ -132,7 +132,8 @@ def extractDigits(ea, ct, r=0, fused=None):
     rr = ct.effectiveR(); -> digits, a list of r ciphertexts (r <= 0 or r > rr: rr), digits[j] with plaintext space
     p^(rr - j) and, in every slot, a value congruent mod p to digit j of the slot's expansion in base p (digits in
     [0, p) for p = 2, balanced for p = 3).  Round i starts from ct and, for j < i, raises digits[j] to the p-th power in
-    place (square / cube) and does tmp -= digits[j]; tmp.divideByP() -- Ctxt.subDivideByP(digits[j], fused)."""
+    place (square / cube) and does tmp -= digits[j]; tmp.divideByP() -- Ctxt.subDivideByP(digits[j], fused).  p > 3 is
+    refused here: helib_amd.polyeval.extractDigits takes any p."""
     if ct.context is not ea.cc:
         raise LogicError("extractDigits: the ciphertext belongs to another context than the EncryptedArray")
     p = ea.p

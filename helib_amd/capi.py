@@ -60,6 +60,7 @@ SYMBOLS = [
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
+    "hx_lin_comb",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -161,6 +162,7 @@ def lib():
             "hx_mask_split": [vp, vp, vp, vp, vp],
             "hx_mask_blend": [vp, vp, vp, vp, vp],
             "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
+            "hx_lin_comb": [vp, vp, vp, vp, ip, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -1062,6 +1064,40 @@ def scaledSub(c0, c1, t0, t1, u, v):
     if n == 0:
         return
     _chk(lib().hx_scaled_sub(c0.h, c1.h if c1 is not None else None, t0.h, t1.h if t1 is not None else None, _p(u), _p(v)))
+
+
+def linComb(in0, in1, idx, w, addend=None):
+    """out = sum_t w[t][row] * in[t] + addend[row] on the one or two parts of n ciphertexts in one pass (hx_lin_comb):
+    the loop of simplePolyEval (src/polyEval.cpp:240-253) with the integers of multByConstant, the mod-ups and the
+    intFactor pairs folded into w.  in0 / in1: the n parts pointing at 1 and at s (in1 = None for one-part operands),
+    each term on a subset of idx in its own order; idx: the prime indices of the output rows; w: n lists of one integer
+    in [0, q) per output row; addend: one integer in [0, q) per output row, added to the first part, or None.
+    -> (out0, out1), new DoubleCRTs (out1 = None with in1)."""
+    if in0 is None or w is None or idx is None:
+        raise InvalidArgument(HX_ERR_INVALID, "linComb: in0, idx and w are required")
+    n, idx = len(in0), [int(i) for i in idx]
+    if n < 1:
+        raise InvalidArgument(HX_ERR_INVALID, "linComb needs at least one term")
+    if in1 is not None and len(in1) != n:
+        raise InvalidArgument(HX_ERR_INVALID, "linComb: in0 and in1 go together, term by term")
+    if len(w) != n or any(len(row) != len(idx) for row in w) or (addend is not None and len(addend) != len(idx)):
+        raise InvalidArgument(HX_ERR_INVALID, "linComb takes one weight per term and output row, and one addend per output row")
+    wa = np.array([[int(x) for x in row] for row in w], dtype=np.uint64).reshape(n, len(idx))
+    aa = np.array([int(x) for x in addend], dtype=np.uint64) if addend is not None else None
+    ctx, batch = in0[0].context, in0[0].batch
+    out0 = DoubleCRT(ctx, idx, batch, zero=False)
+    out1 = DoubleCRT(ctx, idx, batch, zero=False) if in1 is not None else None
+
+    def arr(ps):
+        return (C.c_void_p * n)(*[p.h for p in ps])
+    _chk(lib().hx_lin_comb(out0.h, out1.h if out1 is not None else None, arr(in0), arr(in1) if in1 is not None else None,
+                           n, _p(wa), _p(aa) if aa is not None else None))
+    return out0, out1
+
+
+def constantLike(poly, idx, num):
+    """DoubleCRT(num, context, primeSet): the constant polynomial num on the prime indices idx, with poly's batch"""
+    return DoubleCRT(poly.context, list(idx), poly.batch, zero=False).setConstant(num)
 
 
 def likeUninit(poly):

@@ -10,7 +10,11 @@
 // (src/EncryptedArray.cpp:120-124), one pass instead of four; and of the inner step of digit extraction
 // (hx_scaled_sub):
 //   c = c * u - t * v,  u and v one scalar per prime row
-// (src/extractDigits.cpp:106-107: tmp -= digits[j]; tmp.divideByP()), one pass instead of four.  The unit
+// (src/extractDigits.cpp:106-107: tmp -= digits[j]; tmp.divideByP()), one pass instead of four; and of the leaf of
+// polyEval (hx_lin_comb):
+//   out = sum_t w[t] * in[t] + addend,  the terms on prime sets of their own, w and the addend one scalar per prime row
+// (src/polyEval.cpp:240-253: tmp = X^i; tmp.multByConstant(f_i); ret += tmp; then ret.addConstant), one read of every
+// term and one write of the sum.  The unit
 // reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
 #include <hip/hip_runtime.h>
 
@@ -312,11 +316,79 @@ scaled_sub_kernel(uint64_t* __restrict__ c0, uint64_t* __restrict__ c1, const ui
   }
 }
 
+// out0 = sum_t w[t][row] * in0[t] + addend[row], out1 = sum_t w[t][row] * in1[t] (hx_lin_comb): the words that the
+// loop of simplePolyEval (src/polyEval.cpp:240-253) leaves -- per term a copy, addPrimesAndScale, one or two
+// hx_mul_scalar and hx_add, then hx_add_scalar -- since every one of those steps is exact arithmetic modulo the row's
+// prime and the caller has folded the integers they multiply by into w.  Table (device, uint64 words): per output row r
+// and term t three words at 3 (r n + t): the address of the term's row for the prime of r in in0[t] and in in1[t]
+// (0: the term has no such row and adds nothing), and the weight in [0, q); behind them, at 3 rows n + r, the addend of
+// row r in [0, q).  It is read through the constant address space: the entries are wave-uniform, so they are scalar
+// loads, and the branch on an absent row is uniform.  The thread shape is mul_add_many_kernel's: two adjacent
+// coefficients of one prime row for BP batch elements, PARTS * BP operand vectors per term (16 bytes each,
+// non-temporal: every operand word is read once), 128-bit accumulators that start from the addend and take n <=
+// MAD_CHUNK products, one reduction, PARTS * BP vectors stored.  No LDS: nothing is shared between threads.
+template <int PARTS, int BP>
+__global__ void __launch_bounds__(256)
+lin_comb_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, ro_u64 tab, int n, int rows, int batch,
+                uint32_t N, MadRows map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t k = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  const uint64_t addend = tab[3 * (size_t)rows * n + row];
+  u128 a0[BP][2], a1[BP][2];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    a0[b][0] = a0[b][1] = addend;
+    a1[b][0] = a1[b][1] = 0;
+  }
+  ro_u64 e = tab + 3 * (size_t)row * n;
+  for (int t = 0; t < n; t++) {
+    const uint64_t* p0 = reinterpret_cast<const uint64_t*>(e[3 * t]);
+    if (!p0)
+      continue;
+    const uint64_t* p1 = PARTS == 2 ? reinterpret_cast<const uint64_t*>(e[3 * t + 1]) : nullptr;
+    const uint64_t w = e[3 * t + 2];
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      const ulonglong2 x = ld_stream2(p0 + boff[b]);
+      a0[b][0] += (u128)w * x.x;
+      a0[b][1] += (u128)w * x.y;
+      if (PARTS == 2) {
+        const ulonglong2 y = ld_stream2(p1 + boff[b]);
+        a1[b][0] += (u128)w * y.x;
+        a1[b][1] += (u128)w * y.y;
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    st_stream2(out0 + row_off + boff[b], make_ulonglong2(mad_reduce(a0[b][0], q, mu, mu64, k),
+                                                         mad_reduce(a0[b][1], q, mu, mu64, k)));
+    if (PARTS == 2)
+      st_stream2(out1 + row_off + boff[b], make_ulonglong2(mad_reduce(a1[b][0], q, mu, mu64, k),
+                                                           mad_reduce(a1[b][1], q, mu, mu64, k)));
+  }
+}
+
 }  // namespace hx
 
 namespace {
 
-constexpr int RING = 4;   // calls whose table copy may still be in flight
+constexpr int RING = 4;  // calls whose table copy may still be in flight
 
 // per-context state: pinned staging buffers for the pointer table (one per call in flight) and its device copy
 struct LinState {
@@ -367,6 +439,38 @@ int err(int code, const char* fmt, ...)
     if (_rc != HX_OK)   \
       return _rc;       \
   } while (0)
+
+// the next staging buffer of the ring and the device table, both of at least `bytes`: waits for the copy that last read
+// the staging buffer, and for the stream before a smaller device table is replaced
+int stage_table(LinState* s, hipStream_t st, size_t bytes, int* slot_out)
+{
+  const int slot = s->next;
+  s->next = (slot + 1) % RING;
+  if (s->pending[slot]) {   // the copy that last read this staging buffer
+    CK(hipEventSynchronize(s->copied[slot]));
+    s->pending[slot] = false;
+  }
+  if (s->h_cap[slot] < bytes) {
+    if (s->h_tab[slot])
+      CK(hipHostFree(s->h_tab[slot]));
+    s->h_tab[slot] = nullptr;
+    s->h_cap[slot] = 0;
+    CK(hipHostMalloc((void**)&s->h_tab[slot], bytes, hipHostMallocDefault));
+    s->h_cap[slot] = bytes;
+  }
+  if (!s->copied[slot])
+    CK(hipEventCreateWithFlags(&s->copied[slot], hipEventDisableTiming));
+  if (s->d_cap < bytes) {
+    CK(hipStreamSynchronize(st));   // an earlier launch may still read the old table
+    hipFree(s->d_tab);
+    s->d_tab = nullptr;
+    s->d_cap = 0;
+    CK(hipMalloc((void**)&s->d_tab, bytes));
+    s->d_cap = bytes;
+  }
+  *slot_out = slot;
+  return HX_OK;
+}
 
 int shape_of(const hx_poly* p, int* batch, std::vector<int>* idx)
 {
@@ -471,30 +575,8 @@ extern "C" int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* cons
   LinState* s = static_cast<LinState*>(*v.linalg);
   const hipStream_t st = v.stream;
   const size_t words = (size_t)n * (2 + rows), bytes = words * 8;
-  const int slot = s->next;
-  s->next = (slot + 1) % RING;
-  if (s->pending[slot]) {   // the copy that last read this staging buffer
-    CK(hipEventSynchronize(s->copied[slot]));
-    s->pending[slot] = false;
-  }
-  if (s->h_cap[slot] < bytes) {
-    if (s->h_tab[slot])
-      CK(hipHostFree(s->h_tab[slot]));
-    s->h_tab[slot] = nullptr;
-    s->h_cap[slot] = 0;
-    CK(hipHostMalloc((void**)&s->h_tab[slot], bytes, hipHostMallocDefault));
-    s->h_cap[slot] = bytes;
-  }
-  if (!s->copied[slot])
-    CK(hipEventCreateWithFlags(&s->copied[slot], hipEventDisableTiming));
-  if (s->d_cap < bytes) {
-    CK(hipStreamSynchronize(st));   // an earlier launch may still read the old table
-    hipFree(s->d_tab);
-    s->d_tab = nullptr;
-    s->d_cap = 0;
-    CK(hipMalloc((void**)&s->d_tab, bytes));
-    s->d_cap = bytes;
-  }
+  int slot = 0;
+  RC(stage_table(s, st, bytes, &slot));
   uint64_t *o0 = nullptr, *o1 = nullptr;
   if (accumulate) {
     RC(hxi::poly_rows_update(out0, &o0));
@@ -815,6 +897,151 @@ extern "C" int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const 
       launch_scaled_sub<1>(bp, grid, v.stream, d[0], nullptr, s0, nullptr, batch, N, base, sr, primes);
     CK(hipGetLastError());
   }
+  return HX_OK;
+}
+
+template <int PARTS>
+static void launch_lin_comb(int bp, dim3 grid, hipStream_t st, uint64_t* o0, uint64_t* o1, const uint64_t* tab, int n,
+                            int rows, int batch, uint32_t N, const hx::MadRows& map, const hx::PrimeDev* primes)
+{
+  if (bp == 1)
+    HX_LAUNCH((hx::lin_comb_kernel<PARTS, 1>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, rows, batch, N, map,
+              primes);
+  else
+    HX_LAUNCH((hx::lin_comb_kernel<PARTS, 4>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, rows, batch, N, map,
+              primes);
+}
+
+extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* in0, const hx_poly* const* in1, int n,
+                           const uint64_t* w, const uint64_t* addend)
+{
+  if (!out0 || !in0 || !w)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((out1 == nullptr) != (in1 == nullptr))
+    return err(HX_ERR_INVALID, "out1 and in1 go together (both null for a one-part ciphertext)");
+  if (n < 1)
+    return err(HX_ERR_INVALID, "hx_lin_comb needs at least one term (n = %d)", n);
+  if (n > hx::MAD_CHUNK)
+    return err(HX_ERR_UNSUPPORTED, "hx_lin_comb takes at most %d terms (n = %d)", hx::MAD_CHUNK, n);
+  if (out0 == out1)
+    return err(HX_ERR_INVALID, "out0 and out1 are the same poly");
+  const int parts = out1 ? 2 : 1;
+  hx_ctx* ctx = hxi::poly_ctx(out0);
+  for (int t = 0; t < n; t++) {
+    if (!in0[t] || (in1 && !in1[t]))
+      return err(HX_ERR_INVALID, "null poly (term %d)", t);
+    if (hxi::poly_ctx(in0[t]) != ctx || (in1 && hxi::poly_ctx(in1[t]) != ctx))
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects (term %d)", t);
+    if (in0[t] == out0 || in0[t] == out1 || (in1 && (in1[t] == out0 || in1[t] == out1)))
+      return err(HX_ERR_INVALID, "an output is also an input (term %d)", t);
+  }
+  if (out1 && hxi::poly_ctx(out1) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  if (v.capturing)
+    return err(HX_ERR_UNSUPPORTED, "hx_lin_comb uploads a table of pointers and weights and cannot be captured in a graph");
+  int batch = 0, b2 = 0;
+  std::vector<int> idx, other, other1;
+  RC(shape_of(out0, &batch, &idx));
+  const int rows = (int)idx.size();
+  if (rows > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  if (out1) {
+    RC(shape_of(out1, &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "out0 and out1 differ in batch or prime set");
+  }
+  const uint32_t N = v.phim;
+  if (N < 2 || (N & 1))
+    return err(HX_ERR_UNSUPPORTED, "hx_lin_comb needs an even number of coefficients");
+  std::vector<uint64_t> qs(rows);
+  for (int r = 0; r < rows; r++) {
+    RC(hx_ctx_prime(ctx, idx[r], &qs[r], nullptr));
+    if (addend && addend[r] >= qs[r])
+      return err(HX_ERR_INVALID, "row %d: the addend is not reduced modulo the row's prime %llu", r,
+                 (unsigned long long)qs[r]);
+    for (int t = 0; t < n; t++)
+      if (w[(size_t)t * rows + r] >= qs[r])
+        return err(HX_ERR_INVALID, "term %d, row %d: the weight is not reduced modulo the row's prime %llu", t, r,
+                   (unsigned long long)qs[r]);
+  }
+  // trow[r n + t]: the row of term t that holds the prime of output row r, or -1
+  std::vector<int> trow((size_t)rows * n, -1);
+  for (int t = 0; t < n; t++) {
+    RC(shape_of(in0[t], &b2, &other));
+    if (b2 != batch)
+      return err(HX_ERR_INVALID, "in0[%d]: batch %d, the output has %d", t, b2, batch);
+    if (in1) {
+      RC(shape_of(in1[t], &b2, &other1));
+      if (b2 != batch || other1 != other)
+        return err(HX_ERR_INVALID, "in1[%d] differs from in0[%d] in batch or prime set", t, t);
+    }
+    for (size_t j = 0; j < other.size(); j++) {
+      int at = -1;
+      for (int r = 0; r < rows; r++)
+        if (idx[r] == other[j]) {
+          at = r;
+          break;
+        }
+      if (at < 0)
+        return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the output has no row for prime %d of term %d)",
+                   other[j], t);
+      if (trow[(size_t)at * n + t] >= 0)
+        return err(HX_ERR_INVALID, "term %d lists prime %d twice", t, other[j]);
+      trow[(size_t)at * n + t] = (int)j;
+    }
+    if (((uint64_t)(uintptr_t)hxi::poly_rows_read(in0[t]) | (in1 ? (uint64_t)(uintptr_t)hxi::poly_rows_read(in1[t]) : 0)) & 15)
+      return err(HX_ERR_INVALID, "term %d: rows are not 16-byte aligned", t);
+  }
+  if (rows == 0)
+    return HX_OK;
+  if (!*v.linalg) {
+    *v.linalg = new LinState();
+    *v.linalg_free = state_free;
+  }
+  LinState* s = static_cast<LinState*>(*v.linalg);
+  const hipStream_t st = v.stream;
+  const size_t words = (size_t)rows * (3 * (size_t)n + 1), bytes = words * 8;
+  int slot = 0;
+  RC(stage_table(s, st, bytes, &slot));
+  // the outputs first: one that still shares an input's rows (a lazy hx_poly_copy) lets go of them
+  uint64_t *o0 = nullptr, *o1 = nullptr;
+  RC(hxi::poly_rows_write(out0, &o0));
+  if (out1)
+    RC(hxi::poly_rows_write(out1, &o1));
+  if (((uint64_t)(uintptr_t)o0 | (uint64_t)(uintptr_t)o1) & 15)
+    return err(HX_ERR_INVALID, "output rows are not 16-byte aligned");
+  uint64_t* h = s->h_tab[slot];
+  const size_t rw = (size_t)batch * N;
+  for (int t = 0; t < n; t++) {
+    const uint64_t* p0 = hxi::poly_rows_read(in0[t]);
+    const uint64_t* p1 = in1 ? hxi::poly_rows_read(in1[t]) : nullptr;
+    for (int r = 0; r < rows; r++) {
+      const int at = trow[(size_t)r * n + t];
+      uint64_t* e = h + 3 * ((size_t)r * n + t);
+      e[0] = at < 0 ? 0 : (uint64_t)(uintptr_t)(p0 + (size_t)at * rw);
+      e[1] = at < 0 || !p1 ? 0 : (uint64_t)(uintptr_t)(p1 + (size_t)at * rw);
+      e[2] = w[(size_t)t * rows + r];
+    }
+  }
+  for (int r = 0; r < rows; r++)
+    h[3 * (size_t)rows * n + r] = addend ? addend[r] : 0;
+  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
+  CK(hipEventRecord(s->copied[slot], st));
+  s->pending[slot] = true;
+  hx::MadRows map;
+  for (int r = 0; r < rows; r++)
+    map.p[r] = (uint16_t)idx[r];
+  const int bp = batch == 1 ? 1 : 4;
+  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  if (parts == 2)
+    launch_lin_comb<2>(bp, grid, st, o0, o1, s->d_tab, n, rows, batch, N, map, primes);
+  else
+    launch_lin_comb<1>(bp, grid, st, o0, nullptr, s->d_tab, n, rows, batch, N, map, primes);
+  CK(hipGetLastError());
   return HX_OK;
 }
 

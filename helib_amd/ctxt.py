@@ -456,6 +456,7 @@ class Ctxt:
         # storage; the mod-switch or the key switch that follows forms the product inside its own kernels
         # (ops.tensorBringToSet / ops.mulRelin), anything else calls _materializeTensor() first
         self._pendT = None
+        self._like = None      # a part this ciphertext once held: the shape (batch, device) of a part it is yet to gain
         self.primeSet = frozenset()
         self.ptxtSpace = context.ptxtSpace
         self.intFactor = 1
@@ -475,6 +476,9 @@ class Ctxt:
 
     def clear(self):
         """Ctxt::clear (include/helib/Ctxt.h:1347-1354): an empty ciphertext on the ctxt primes"""
+        like = self._pendT[0] if self._pendT is not None else next(iter(self.parts.values()), None)
+        if like is not None:
+            self._like = like
         self._pending, self._pendT = [], None
         self.parts = {}
         self.primeSet = frozenset(self.context.ctxtPrimes)
@@ -492,6 +496,16 @@ class Ctxt:
         c.ksw_auto = self.ksw_auto
         c.ksw_pow = self.ksw_pow
         c.ksw_map = self.ksw_map
+        c._like = self._like
+        return c
+
+    def _emptyLike(self):
+        """Ctxt tmp(pubKey, ptxtSpace): an empty ciphertext under this one's keys, in its plaintext space"""
+        c = Ctxt(self.context, self.ops, self.ksw, self.ksw_ptxtSpace, self.ksw_lnNoise)
+        c.ptxtSpace = self.ptxtSpace
+        c.ksw_auto, c.ksw_pow, c.ksw_map = self.ksw_auto, self.ksw_pow, self.ksw_map
+        c._like = self._pendT[0] if self._pendT is not None else next(iter(self.parts.values()), self._like)
+        c.primeSet = frozenset(self.context.ctxtPrimes)
         return c
 
     # ---- noise estimate: ln(noiseBound) ----
@@ -809,9 +823,14 @@ class Ctxt:
             self -= other
             return self.divideByP()
         o, _, e1, e2 = self._alignForAdd(other)
+        idx = self.parts[hs[0]].getIndexSet()
+        if any(self.parts[h].getIndexSet() != idx or o.parts[h].getIndexSet() != idx for h in hs):
+            # the kernel pairs rows by position: two sides whose rows stand in different orders (a digit that came out
+            # of polyEval) take the two calls, which find nothing left to align
+            self -= other
+            return self.divideByP()
         P = self.ptxtSpace
         bal = lambda e: e - P if e > P // 2 else e                     # noqa: E731  (mulIntFactor's)
-        idx = self.parts[hs[0]].getIndexSet()
         pInverse = pow(p, -1, ctx.productOfPrimes(self.primeSet))
         u = [bal(e1) * pInverse % ctx.primes[i] for i in idx]
         v = [bal(e2) * pInverse % ctx.primes[i] for i in idx]
@@ -953,24 +972,30 @@ class Ctxt:
             Ctxt.equalizeRationalFactors(self, own())
         e1 = e2 = 1
         if not ctx.ckks and self.intFactor != o.intFactor:
-            P = self.ptxtSpace
-            ratio = o.intFactor * pow(self.intFactor, -1, P) % P
-            bal = lambda e: abs(e - P if e > P // 2 else e)                 # noqa: E731
-            norm = lambda a, b: logaddexp(self.lnNoise + _ln(bal(a)), o.lnNoise + _ln(bal(b)))  # noqa: E731
-            r0, t0, r1, t1 = P, 0, ratio, 1
-            e1, e2 = r1, t1
-            best = norm(e1, e2)
-            while r1 != 0:
-                q = r0 // r1
-                r0, r1, t0, t1 = r1, r0 % r1, t1, t0 - t1 * q
-                a, b = r1 % P, t1 % P
-                if a % ctx.p != 0:
-                    cand = norm(a, b)
-                    if cand < best:
-                        e1, e2, best = a, b, cand
-            assert e1 * self.intFactor % P == e2 * o.intFactor % P
-            assert math.gcd(e1, P) == 1 and math.gcd(e2, P) == 1
+            e1, e2 = Ctxt._intFactorPair(ctx.p, self.ptxtSpace, self.intFactor, self.lnNoise, o.intFactor, o.lnNoise)
         return o, owned, e1, e2
+
+    @staticmethod
+    def _intFactorPair(p, P, f1, ln1, f2, ln2):
+        """the (e1, e2) with e1 f1 = e2 f2 mod P of least noise along the extended Euclidean sequence of P and f2 / f1
+        (src/Ctxt.cpp:1474-1526); ln1, ln2 the two sides' ln(noiseBound)"""
+        ratio = f2 * pow(f1, -1, P) % P
+        bal = lambda e: abs(e - P if e > P // 2 else e)                 # noqa: E731
+        norm = lambda a, b: logaddexp(ln1 + _ln(bal(a)), ln2 + _ln(bal(b)))  # noqa: E731
+        r0, t0, r1, t1 = P, 0, ratio, 1
+        e1, e2 = r1, t1
+        best = norm(e1, e2)
+        while r1 != 0:
+            q = r0 // r1
+            r0, r1, t0, t1 = r1, r0 % r1, t1, t0 - t1 * q
+            a, b = r1 % P, t1 % P
+            if a % p != 0:
+                cand = norm(a, b)
+                if cand < best:
+                    e1, e2, best = a, b, cand
+        assert e1 * f1 % P == e2 * f2 % P
+        assert math.gcd(e1, P) == 1 and math.gcd(e2, P) == 1
+        return e1, e2
 
     @staticmethod
     def computeIntervalForMul(c1, c2):
@@ -1202,16 +1227,7 @@ class Ctxt:
             for _ in range(e.bit_length() - 1):
                 self.square()
             return self
-        powers = {1: self.clone()}
-
-        def get(n):
-            if n not in powers:
-                k = 1 << ((n - 1).bit_length() - 1)      # NextPowerOfTwo(n) - 1
-                c = get(n - k).clone()
-                c.multiplyBy(get(k))
-                powers[n] = c
-            return powers[n]
-        r = get(e)
+        r = DynamicCtxtPowers(self, e).getPower(e)
         self.__dict__.update(r.__dict__)
         return self
 
@@ -1431,6 +1447,181 @@ class Ctxt:
             self.parts["1"] += tmp
         return self
 
+    def _constFactor(self):
+        """f = balRem(intFactor * Q mod ptxtSpace): what a constant is scaled by before it is added (src/Ctxt.cpp:2163-2168)"""
+        f = 1
+        if self.ptxtSpace > 2:
+            p = self.ptxtSpace
+            f = self.context.productOfPrimes(self.primeSet) % p * self.intFactor % p
+            if f > p // 2:
+                f -= p
+        return f
+
+    def addScalar(self, c, neg=False):
+        """Ctxt::addConstant(const ZZ&, bool neg) (src/Ctxt.cpp:2264-2282), BGV: c reduced to its balanced residue cc
+        (0: nothing to do), then addConstant of the constant polynomial cc on the prime set with size |cc|: the noise
+        bound grows by |cc f| and cc f goes to the part pointing at 1, f as in addConstant.  A ciphertext without that
+        part -- an empty one after clear() -- gains it, as Ctxt::addSignedPart does."""
+        if self.context.ckks:
+            raise TypeError("addScalar is the BGV branch of Ctxt::addConstant(ZZ)")
+        P = self.ptxtSpace
+        cc = int(c) % P
+        if cc > P // 2:
+            cc -= P
+        if cc == 0:
+            return self
+        self._materializeTensor()
+        f = self._constFactor()
+        self.lnNoise = logaddexp(self.lnNoise, _ln(float(abs(cc)) * abs(f)))
+        v = -cc * f if neg else cc * f
+        part = self.parts.get("1")
+        if part is not None and hasattr(part, "addConstant"):
+            part.addConstant(v)
+            return self
+        like = part if part is not None else next(iter(self.parts.values()), self._like)
+        if like is None or not hasattr(self.ops, "constantLike"):
+            raise RuntimeError("Ctxt::addPart: no part pointing at 1, and nothing to shape one after")
+        idx = like.getIndexSet() if self.parts else sorted(self.primeSet)
+        cst = self.ops.constantLike(like, idx, v)
+        if part is not None:
+            part += cst
+        else:
+            self.parts["1"] = cst
+        return self
+
+    fuseLinComb = False  # fused=None: the call sequence until hx_lin_comb has been measured as the faster form (DESIGN 3.9k)
+
+    @staticmethod
+    def linearCombination(terms, free=0, fused=None):
+        """sum_t c_t * ct_t + free for terms = [(ct, integer)]: the loop of simplePolyEval (src/polyEval.cpp:227-253) --
+        ret.clear(); per term tmp = ct; tmp.multByConstant(c); ret += tmp; then ret.addConstant(free) -- as a new
+        ciphertext.  Fused: the same steps on the bookkeeping alone (the plaintext spaces' gcd, the union of the prime
+        sets, _alignForAdd's (e1, e2), lnNoise, ptxtMag and intFactor, float operation for float operation), collecting
+        per term the integers the steps would have multiplied into its words -- the balanced gcd of multByScalar, the
+        product of the added primes whenever a side is modded up, bal(e2) on the new term and bal(e1) on everything
+        before it -- then one ops.linComb (hx_lin_comb) with those products reduced modulo every output prime.  It
+        applies to a BGV context when every surviving term holds the canonical parts {1, s}, or all hold the same single
+        part, at most 256 of them, on a backend with linComb; otherwise, and with fused=False, the sequence runs as it
+        is.  fused=True insists on a backend with linComb; fused=None follows Ctxt.fuseLinComb.  Words, lnNoise,
+        primeSet, ptxtSpace, intFactor and ptxtMag are the same either way; the terms are left as they were."""
+        if not terms:
+            raise ValueError("linearCombination of no terms")
+        first = terms[0][0]
+        has = hasattr(first.ops, "linComb")
+        if fused and not has:
+            raise RuntimeError("Ctxt::linearCombination: fused=True, but this backend has no linComb")
+        want = (Ctxt.fuseLinComb if fused is None else fused) and has
+        if want:
+            ret = Ctxt._linCombFused(terms, free)
+            if ret is not None:
+                return ret
+        ret = first._emptyLike()
+        for ct, c in terms:
+            tmp = ct.clone()
+            tmp.multByScalar(c)
+            ret += tmp
+        ret.addScalar(free)
+        return ret
+
+    @staticmethod
+    def _linCombFused(terms, free):
+        """linearCombination's fused form, or None where it does not apply (nothing has been touched then)"""
+        first = terms[0][0]
+        ctx = first.context
+        if ctx.ckks:
+            return None
+        live = []                                        # (ct, c mod its space), the terms multByScalar leaves with parts
+        for ct, c in terms:
+            if isinstance(c, float):
+                raise TypeError("multByConstant(double) not supported for BGV")
+            ct._materializeTensor()
+            if ct.parts and int(c) % ct.ptxtSpace != 0:
+                live.append((ct, int(c) % ct.ptxtSpace))
+        if not live or len(live) > 256:
+            return None
+        hs = sorted(live[0][0].parts, key=str)
+        if not (hs == ["1", "s"] or len(hs) == 1):
+            return None
+        for ct, _ in live:
+            if sorted(ct.parts, key=str) != hs:
+                return None
+            ix = ct.parts[hs[0]].getIndexSet()
+            if any(ct.parts[h].getIndexSet() != ix for h in hs[1:]):
+                return None
+        # the running sum's bookkeeping, and per term the integer its words are multiplied by
+        mult = []
+        P = ps = fac = ln = mag = idx = None
+        for ct, c0 in live:
+            tP, tf, tln, tmag, tps, m = ct.ptxtSpace, ct.intFactor, ct.lnNoise, ct.ptxtMag, ct.primeSet, 1
+            if c0 != 1:                                                   # multByScalar
+                d = math.gcd(c0, tP)
+                tf = tf * pow(c0 // d, -1, tP) % tP
+                if d != 1:
+                    cc = d - tP if d > tP // 2 else d
+                    tln = tln + math.log(abs(cc))
+                    m *= cc
+            if P is None:                                                 # ret += tmp into the empty ret
+                P, ps, fac, ln, mag = tP, tps, tf, tln, tmag
+                idx = ct.parts[hs[0]].getIndexSet()
+                mult.append(m)
+                continue
+            g = math.gcd(P, tP)                                           # _alignForAdd
+            if g <= 1:
+                raise ValueError("New and old plaintext spaces are coprime")
+            P, fac = g, fac % g
+            if tP != g:
+                tf %= g
+            up = sorted(tps - ps)
+            if up:                                                        # the sum is modded up
+                ln = ln + ctx.logOfProduct(up)
+                ps = ps | frozenset(up)
+                idx = idx + up
+                prod = ctx.productOfPrimes(up)
+                mult = [x * prod for x in mult]
+            up = sorted(ps - tps)
+            if up:                                                        # the term is modded up
+                tln = tln + ctx.logOfProduct(up)
+                m *= ctx.productOfPrimes(up)
+            e1 = e2 = 1
+            if fac != tf:
+                e1, e2 = Ctxt._intFactorPair(ctx.p, P, fac, ln, tf, tln)
+            bal = lambda e: e - P if e > P // 2 else e                    # noqa: E731  (mulIntFactor's)
+            if e2 != 1:                                                   # o.mulIntFactor(e2)
+                m *= bal(e2)
+                tln = tln + math.log(abs(bal(e2)))
+            if e1 != 1:                                                   # self.mulIntFactor(e1)
+                fac = fac * e1 % P
+                mult = [x * bal(e1) for x in mult]
+                ln = ln + math.log(abs(bal(e1)))
+            mag += tmag                                                   # the sum
+            ln = logaddexp(ln, tln)
+            mult.append(m)
+        cc = int(free) % P                                                # addScalar
+        if cc > P // 2:
+            cc -= P
+        addend = None
+        if cc != 0:
+            if hs != ["1", "s"] and hs != ["1"]:
+                return None
+            f = 1
+            if P > 2:
+                f = ctx.productOfPrimes(ps) % P * fac % P
+                if f > P // 2:
+                    f -= P
+            ln = logaddexp(ln, _ln(float(abs(cc)) * abs(f)))
+            addend = [cc * f % ctx.primes[i] for i in idx]
+        w = [[x % ctx.primes[i] for i in idx] for x in mult]
+        in0 = [ct.parts[hs[0]] for ct, _ in live]
+        in1 = [ct.parts[hs[1]] for ct, _ in live] if len(hs) == 2 else None
+        out0, out1 = first.ops.linComb(in0, in1, idx, w, addend)
+        ret = live[0][0]._emptyLike()
+        ret.parts = {hs[0]: out0}
+        if len(hs) == 2:
+            ret.parts[hs[1]] = out1
+        ret.ptxtSpace, ret.primeSet, ret.intFactor, ret.ptxtMag = P, ps, fac, mag
+        ret.lnNoise = ln
+        return ret
+
     def cleanUp(self):
         """Ctxt::cleanUp (src/Ctxt.cpp:788-797)"""
         self.reLinearize()
@@ -1438,6 +1629,39 @@ class Ctxt:
         if self.primeSet & (frozenset(ctx.specialPrimes) | frozenset(ctx.smallPrimes)):
             self.dropSmallAndSpecialPrimes()
         return self
+
+
+class DynamicCtxtPowers:
+    """DynamicCtxtPowers (include/helib/polyEval.h:59-130, src/polyEval.cpp:18-29): the powers of one ciphertext,
+    computed when first asked for -- X^e = X^(e-k) * X^k with k the largest power of two below e -- so every power is
+    formed once and X^e sits at depth ceil(log2 e).  stats, if given, counts the products in stats["mults"] and
+    records (name, e) in stats["powers"]."""
+
+    def __init__(self, x, nPowers, stats=None, name=""):
+        if nPowers < 1:
+            raise ValueError("Zero or negative nPowers")
+        self.v = [None] * nPowers
+        self.v[0] = x.clone()
+        self.stats, self.name = stats, name
+
+    def size(self):
+        return len(self.v)
+
+    def wasComputed(self, e):
+        return 1 <= e <= len(self.v) and self.v[e - 1] is not None
+
+    def getPower(self, e):
+        if e < 1 or e > len(self.v):
+            raise IndexError("DynamicCtxtPowers: power %d of %d" % (e, len(self.v)))
+        if self.v[e - 1] is None:
+            k = 1 << ((e - 1).bit_length() - 1)      # NextPowerOfTwo(e) - 1
+            c = self.getPower(e - k).clone()
+            c.multiplyBy(self.getPower(k))
+            self.v[e - 1] = c
+            if self.stats is not None:
+                self.stats["mults"] += 1
+                self.stats["powers"].add((self.name, e))
+        return self.v[e - 1]
 
 
 class BasicAutomorphPrecon:

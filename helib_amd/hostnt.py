@@ -266,3 +266,53 @@ class ZmStar:
             raise ValueError("PAlgebra::genToPow: bad dim")
         base = self.p % self.m if i == -1 else self.gens[i]
         return pow(base, j, self.m)
+
+
+def _interpolate_mod_p(x, y, p):
+    """the polynomial of degree < len(x) over F_p through (x[j], y[j]), x distinct mod p; coefficients in [0, p),
+    lowest first (NTL's interpolate, by Newton's divided differences)"""
+    n = len(x)
+    coef = [v % p for v in y]
+    for k in range(1, n):                       # divided differences in place
+        for j in range(n - 1, k - 1, -1):
+            coef[j] = (coef[j] - coef[j - 1]) * pow((x[j] - x[j - k]) % p, -1, p) % p
+    poly = [0] * n                              # Horner over the Newton basis
+    for k in range(n - 1, -1, -1):
+        nxt = [0] * n
+        for i in range(n - 1):
+            nxt[i + 1] = poly[i]
+        for i in range(n):
+            nxt[i] = (nxt[i] - x[k] * poly[i]) % p
+        nxt[0] = (nxt[0] + coef[k]) % p
+        poly = nxt
+    return poly
+
+
+def interpolateMod(x, y, p, e):
+    """interpolateMod (src/NumbTh.cpp:998-1069): the integer polynomial with poly(x[j]) = y[j] mod p^e, the points
+    distinct modulo the prime p; coefficients lowest first, trailing zeros dropped.  One digit in base p at a time:
+    interpolate modulo p, subtract what that polynomial gives modulo p^e, divide by p, recurse modulo p^(e-1);
+    poly = p * poly' + that polynomial."""
+    x = [int(v) for v in x]
+    if len({v % p for v in x}) != len(x):
+        raise ValueError("interpolateMod: the points are not distinct modulo p")
+    p2e = p ** e
+    y = [int(v) % p2e for v in y]
+
+    def ev(poly, v, mod):
+        r = 0
+        for c in reversed(poly):
+            r = (r * v + c) % mod
+        return r
+
+    def rec(y, p2e):
+        if p2e <= 1:
+            return []
+        low = _interpolate_mod_p(x, y, p)
+        y = [(yj - ev(low, xj, p2e)) % p2e // p for xj, yj in zip(x, y)]
+        high = rec(y, p2e // p)
+        return [low[i] + p * (high[i] if i < len(high) else 0) for i in range(len(low))]
+    poly = rec(y, p2e)
+    while poly and poly[-1] == 0:
+        poly.pop()
+    return poly

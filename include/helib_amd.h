@@ -554,6 +554,26 @@ int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1
  * reads 2 and writes 1. */
 int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const uint64_t* u_per_row,
                   const uint64_t* v_per_row);
+/* The leaf of polyEval (src/polyEval.cpp:240-253:
+ *   for each baby step  tmp = X^i;  tmp.multByConstant(f_i);  ret += tmp;   then  ret.addConstant(f_0);)
+ * on the parts of n ciphertexts, in one pass:  for output row r (prime idx[r] of out0) and every word
+ *   out0 = (sum_t w[t][r] * in0[t] + addend[r]) mod q,   out1 = (sum_t w[t][r] * in1[t]) mod q,
+ * the sums over the terms t that have a row for that prime.  The powers of X sit on different prime sets: ret += tmp
+ * mod-switches one side up (DoubleCRT::addPrimesAndScale, src/DoubleCRT.cpp:603-647: the old rows times the product of
+ * the added primes, the new rows zero) and harmonises the intFactors (two products by a scalar), all of it exact
+ * arithmetic modulo the row's prime.  The caller folds those integers into w, so a term's rows may be a subset of the
+ * output's, in any order of its own, and a term without a row for a prime contributes nothing there; an output row that
+ * no term covers is addend[r], or 0.  w is [n][rows(out0)], addend [rows(out0)] or null (zero); every entry is in
+ * [0, q) of its row.  in1[t] has the batch and the prime set (same order) of in0[t]; out1 and in1 are both null for
+ * one-part operands.  The outputs are overwritten, not read, and must not be among the inputs; every word written is
+ * canonical in [0, q).  Null arguments, n < 1, a poly of another context, mismatched batches, an output among the
+ * inputs and an entry of w or addend that is not below its row's prime are HX_ERR_INVALID; a term's prime that the
+ * output lacks is HX_ERR_PRIMESET; n > 256 (the 128-bit accumulators take 256 products before they must be reduced),
+ * more than 160 rows and an odd phi(m) are HX_ERR_UNSUPPORTED; a refused call touches no output.  The call uploads a
+ * table of row addresses and weights, so it cannot be recorded: under an open graph capture it returns
+ * HX_ERR_UNSUPPORTED before touching the device.  Asynchronous on the context's stream. */
+int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* in0, const hx_poly* const* in1, int n,
+                const uint64_t* w, const uint64_t* addend);
 
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
