@@ -14,7 +14,8 @@ element of GF(p^d) = Z_p[X] / G, d = ord_m(p), r = 1.  helib_amd.bgv_crt / bgv_h
   mulPlain / frobeniusPlain     the plain-side truths: the slot-wise product mod (G, p) and alpha -> alpha^(p^j)
 
 Out of scope, refused with a message: a G other than F_0 (a root of G in Z_p[X] / F_0 would have to be found: the
-reference's FindRoots branch of mapToSlots, src/PAlgebra.cpp:1116-1186), deg G < d, p^r with r > 1, d > 64.  Linearized
+reference's FindRoots branch of mapToSlots, src/PAlgebra.cpp:1116-1186), deg G < d, d > 64, and p^r with r > 1, which is
+helib_amd.bgv_gr (slots in the Galois ring Z_(p^r)[X] / G; unpack / repack over either class: helib_amd.intraslot).  Linearized
 polynomials, MatMul1D with GF entries and BlockMatMul1D over these slots are helib_amd.bgv_gf_matmul (helib_amd.bgv_matmul
 takes integer matrices of two axes).  Nothing here imports oracle/."""
 import numpy as np

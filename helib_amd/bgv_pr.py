@@ -15,8 +15,10 @@ the kernels are those of r = 1, and at r = 1 the class is helib_amd.bgv_hypercub
                       Ctxt.subDivideByP, one hx_scaled_sub with fused=True
 
 Out of scope, refused with LogicError and a message: helib_amd.bgv_matmul and bgv_gf_matmul over this class at r > 1,
-GF(p^d) slots at r > 1 (helib_amd.bgv_gf refuses), p > 3 in this module's extractDigits (helib_amd.polyeval has polyEval,
-buildDigitPolynomial, an extractDigits for any p and extendExtractDigits).  Nothing here imports oracle/."""
+p > 3 in this module's extractDigits (helib_amd.polyeval has polyEval,
+buildDigitPolynomial, an extractDigits for any p and extendExtractDigits).  Slots with d > 1 coefficients at r > 1 --
+the Galois ring Z_(p^r)[X] / G -- are helib_amd.bgv_gr (helib_amd.bgv_gf stays at r = 1 and refuses).  Nothing here
+imports oracle/."""
 import numpy as np
 
 from . import bgv, bgv_crt, bgv_hypercube, capi, hostnt

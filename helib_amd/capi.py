@@ -60,12 +60,13 @@ SYMBOLS = [
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
-    "hx_lin_comb",
+    "hx_lin_comb", "hx_mul_add_circulant",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
     "hx_bgv_crt_create_pr", "hx_bgv_crt_space",
     "hx_bgv_gf_create", "hx_bgv_gf_destroy", "hx_bgv_gf_info", "hx_bgv_gf_encode", "hx_bgv_gf_decode", "hx_bgv_gf_embed",
+    "hx_bgv_gf_create_pr", "hx_bgv_gf_space",
     "hx_bgv_gf_linalg_tables", "hx_bgv_gf_matrix_create", "hx_bgv_gf_matrix_destroy", "hx_bgv_gf_matrix_coeffs", "hx_bgv_gf_gather",
 ]
 
@@ -163,6 +164,7 @@ def lib():
             "hx_mask_blend": [vp, vp, vp, vp, vp],
             "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
             "hx_lin_comb": [vp, vp, vp, vp, ip, vp, vp],
+            "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -177,6 +179,7 @@ def lib():
             "hx_bgv_crt_decode": [vp, vp, u64, vp],
             "hx_bgv_crt_embed": [vp, vp, ip, vp],
             "hx_bgv_gf_create": [vp, u64, vp], "hx_bgv_gf_destroy": [vp],
+            "hx_bgv_gf_create_pr": [vp, u64, ip, vp], "hx_bgv_gf_space": [vp, vp, vp],
             "hx_bgv_gf_info": [vp, vp, vp, vp, vp, vp, vp, vp, vp],
             "hx_bgv_gf_encode": [vp, vp, ip, u64, vp, vp],
             "hx_bgv_gf_decode": [vp, vp, u64, vp],
@@ -827,13 +830,23 @@ def bgvCrtEmbed(table, f):
 
 
 class BgvGf:
-    """The tables of one (Context, p) pair for slots in GF(p^d) = Z_p[X] / G, G = F_0 (hx_bgv_gf): EncryptedArray(context,
-    G).  d, nslots, gens, ords (signed), table_bytes, G (d + 1 integers, the constant coefficient first)."""
+    """The tables of one (Context, p, r) triple for slots in GF(p^d) = Z_p[X] / G, G = F_0 (hx_bgv_gf): EncryptedArray(context,
+    G); with r > 1 slots in the Galois ring Z_(p^r)[X] / G, G the Hensel lift of F_0 (hx_bgv_gf_create_pr).  d, nslots,
+    gens, ords (signed), table_bytes, G (d + 1 integers, the constant coefficient first); prime, r; p is the modulus p^r
+    the maps work in."""
 
-    def __init__(self, context, p):
-        self.context, self.p = context, int(p)
+    def __init__(self, context, p, r=1):
+        self.context, self.prime, self.r = context, int(p), int(r)
         self.h = C.c_void_p()
-        _chk(lib().hx_bgv_gf_create(context.h, self.p, C.byref(self.h)))
+        if self.r == 1:
+            _chk(lib().hx_bgv_gf_create(context.h, self.prime, C.byref(self.h)))
+            self.p = self.prime
+        else:
+            _chk(lib().hx_bgv_gf_create_pr(context.h, self.prime, self.r, C.byref(self.h)))
+            rr, mod = C.c_int(), C.c_uint64()
+            _chk(lib().hx_bgv_gf_space(self.h, C.byref(rr), C.byref(mod)))
+            assert rr.value == self.r and mod.value == self.prime ** self.r
+            self.p = int(mod.value)
         d, ns, nd, tb = C.c_int(), C.c_int(), C.c_int(), C.c_uint64()
         g, o = (C.c_uint64 * 8)(), (C.c_int64 * 8)()
         _chk(lib().hx_bgv_gf_info(self.h, None, C.byref(d), C.byref(ns), C.byref(nd), g, o, C.byref(tb), None))
@@ -1028,6 +1041,21 @@ def mulAddMany(out0, out1, consts, in0, in1, accumulate=True):
         return (C.c_void_p * max(n, 1))(*[p.h for p in ps])
     _chk(lib().hx_mul_add_many(out0.h, out1.h if out1 is not None else None, arr(consts), arr(in0),
                                arr(in1) if in1 is not None else None, n, 1 if accumulate else 0))
+
+
+def mulAddCirculant(out0, out1, consts, in0, in1):
+    """out0[i] = sum_j consts[(i + j) mod d] * in0[j], out1[i] likewise, for i < len(out0) <= d = len(consts) <= 64, in one
+    pass (hx_mul_add_circulant): the inner loop of unpack (src/intraSlot.cpp:108-115).  out1 / in1 = None for one-part
+    operands; the outputs are overwritten (make them with likeUninit) and must not be among the inputs."""
+    d, nout = len(consts), len(out0)
+    if len(in0) != d or (in1 is not None and len(in1) != d) or (out1 is None) != (in1 is None) or \
+            (out1 is not None and len(out1) != nout):
+        raise InvalidArgument(HX_ERR_INVALID, "mulAddCirculant: d constants, d inputs per part and as many outputs per part")
+
+    def arr(ps):
+        return (C.c_void_p * max(len(ps), 1))(*[p.h for p in ps])
+    _chk(lib().hx_mul_add_circulant(arr(out0), arr(out1) if out1 is not None else None, nout, arr(consts), arr(in0),
+                                    arr(in1) if in1 is not None else None, d))
 
 
 def maskSplit(keep0, keep1, take0, take1, mask):

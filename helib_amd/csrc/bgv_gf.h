@@ -18,6 +18,13 @@
 // d = 1: G is linear, A_i = M_i = [1], there is no fold: the integer path of bgv_crt.h, word for word.
 // No phi(m) x phi(m) table is built: E stays nslots x ld, Rx is nslots x ldr (ldr = phi(m) + d - 1 rounded up to 4
 // words, zero filled, so that a row starts on a 16-byte boundary), A and M nslots d^2 words each, T (d - 1) x ld.
+//
+// r > 1 (build_gf's last argument): slots in the Galois ring Z_(p^r)[X] / G, G the Hensel lift of F_0.  Every table above
+// is the same formula modulo P = p^r over the lifted factors bgv_crt.h computes: the lift of a factorisation is unique,
+// so X -> X^(t_i) carries the lifted F_0 to the lifted F_i exactly as it does modulo p, and A_i, T, Rx need no change
+// but the modulus.  alpha -> u is invertible modulo P because it is modulo p; only the elimination knows about the
+// prime: gf_invert picks a pivot that is a unit, i.e. non-zero modulo p (one exists in every column, the matrix being
+// invertible modulo p).  At r = 1 every word is the one built above.
 #pragma once
 #include "bgv_crt.h"
 
@@ -52,15 +59,18 @@ inline void gf_mulmod(const uint32_t* a, const uint32_t* b, const uint32_t* f, u
     out[i] = (uint32_t)r[i];
 }
 
-// the inverse of the d x d matrix a modulo p (row major) into inv; false: singular
-inline bool gf_invert(std::vector<uint64_t> a, uint32_t d, uint64_t p, uint32_t* inv)
+// the inverse of the d x d matrix a modulo p (row major) into inv; false: singular.  prime: p is a power of it (0: p
+// itself is the prime) and a pivot has to be a unit, non-zero modulo the prime
+inline bool gf_invert(std::vector<uint64_t> a, uint32_t d, uint64_t p, uint32_t* inv, uint64_t prime = 0)
 {
+  if (!prime)
+    prime = p;
   std::vector<uint64_t> b((size_t)d * d, 0);
   for (uint32_t i = 0; i < d; i++)
     b[(size_t)i * d + i] = 1 % p;
   for (uint32_t c = 0; c < d; c++) {
     uint32_t piv = c;
-    while (piv < d && a[(size_t)piv * d + c] == 0)
+    while (piv < d && a[(size_t)piv * d + c] % prime == 0)
       piv++;
     if (piv == d)
       return false;
@@ -88,23 +98,24 @@ inline bool gf_invert(std::vector<uint64_t> a, uint32_t d, uint64_t p, uint32_t*
   return true;
 }
 
-// "", or the reason the tables cannot be built
-inline std::string build_gf(uint64_t m, uint64_t p, GfTables& t)
+// "", or the reason the tables cannot be built.  r: the tables are modulo p^r (the top of this file)
+inline std::string build_gf(uint64_t m, uint64_t prime, GfTables& t, uint32_t r = 1)
 {
   char msg[200];
   t = GfTables();
-  std::string why = build_crt(m, p, t.crt, false);   // the geometry first: d decides
+  std::string why = build_crt(m, prime, t.crt, false, r);   // the geometry first: d decides
   if (!why.empty())
     return why;
   if (t.crt.d > GF_MAX_D) {
     snprintf(msg, sizeof msg, "d = ord_m(p) = %u for m = %llu, p = %llu: slots in GF(p^d) are built for d <= %u", t.crt.d,
-             (unsigned long long)m, (unsigned long long)p, GF_MAX_D);
+             (unsigned long long)m, (unsigned long long)prime, GF_MAX_D);
     return msg;
   }
-  why = build_crt(m, p, t.crt);
+  why = build_crt(m, prime, t.crt, true, r);
   if (!why.empty())
     return why;
   const CrtTables& c = t.crt;
+  const uint64_t p = c.modulus;   // p^r: what every table below is a residue of
   const uint32_t d = c.d, n = c.nslots, phim = c.phim, ld = c.ld;
   t.ldr = (phim + d - 1 + 3) / 4 * 4;
   t.G.assign(c.factors.begin(), c.factors.begin() + d + 1);
@@ -192,7 +203,7 @@ inline std::string build_gf(uint64_t m, uint64_t p, GfTables& t)
             s = (s + (uint64_t)A[(size_t)l * d + k] * r[k + j]) % p;
           U[(size_t)j * d + l] = s;   // transposed
         }
-      if (!gf_invert(U, d, p, t.M.data() + (size_t)i * d * d))
+      if (!gf_invert(U, d, p, t.M.data() + (size_t)i * d * d, prime))
         return "internal: the map from a slot to its d constant terms is singular";
     }
     for (size_t g = ng; g-- > 0;) {

@@ -1,5 +1,6 @@
 // bgv_gf.hip -- C ABI of BGV slot encoding and decoding with slots in GF(p^d) = Z_p[X] / G, G = F_0, d = ord_m(p), r = 1
-// (include/helib_amd.h: hx_bgv_gf_create, hx_bgv_gf_info, hx_bgv_gf_encode, hx_bgv_gf_decode, hx_bgv_gf_embed):
+// (include/helib_amd.h: hx_bgv_gf_create, hx_bgv_gf_create_pr, hx_bgv_gf_space, hx_bgv_gf_info, hx_bgv_gf_encode,
+// hx_bgv_gf_decode, hx_bgv_gf_embed):
 // EncryptedArray(context, G) over the G = F_0 branches of PAlgebraModDerived (src/PAlgebra.cpp:1064-1067, 1096-1100,
 // 1168-1186, 1243-1278).  The tables are bgv_gf.h's; with B elements, n slots, N = phi(m):
 //   encode   c[b][i] = alpha[b][i] A_i                                   (bgv_gf_map_kernel: B n d^2 multiply-adds)
@@ -12,6 +13,11 @@
 // kernel of its own ahead of the encode: formed while staging it would be redone for each of the N / 256 coefficient
 // tiles.  The fold is a launch of its own: the top words of W belong to the last coefficient tile, another workgroup.
 // Around them the pieces every BGV slot path shares (bgv_encode.h).
+// At r > 1 (hx_bgv_gf_create_pr: slots in the Galois ring Z_(p^r)[X] / G, G the Hensel lift of F_0) the modulus of all of
+// these is p^r < 2^31 (in the kernels' `p`; the table keeps the prime beside it) and the kernels are the same code: as
+// in bgv_crt.hip none of them needs a prime -- bgv_red's quotient estimate is short by at most 1 for any q >= 2, Shoup's
+// product lies in [0, 2q) for any q and w < q -- and every accumulator is bounded by `limit` = floor(2^64 / p^(2r)),
+// which build_crt computes from p^r (lazy_limit) and which is >= 4 because p^r < 2^31.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -260,6 +266,8 @@ bgv_gf_decode_kernel(const uint64_t* __restrict__ w, const uint32_t* __restrict_
 }  // namespace hx
 
 struct hx_bgv_gf : hxb::SlotBase {
+  uint64_t prime = 0;          // p; SlotBase's p is the modulus p^r the maps work in
+  uint32_t r = 1;
   uint32_t d = 0, nslots = 0, ld = 0, ldr = 0, limit = 0;
   std::vector<uint64_t> gens;
   std::vector<int64_t> ords;   // signed
@@ -344,7 +352,7 @@ extern "C" int hx_bgv_gf_destroy(hx_bgv_gf* t)
   return HX_OK;
 }
 
-extern "C" int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out)
+extern "C" int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** out)
 {
   if (!ctx || !out)
     return err(HX_ERR_INVALID, "null argument");
@@ -357,15 +365,21 @@ extern "C" int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out)
   const uint64_t m = v.m;
   if (p < 2 || !hxh::is_prime(p))
     return err(HX_ERR_INVALID, "the plaintext modulus p = %llu is not a prime", (unsigned long long)p);
+  if (r < 1)
+    return err(HX_ERR_INVALID, "the exponent r = %d of the plaintext space p^r is less than 1", r);
   if (p >= hxc::CRT_MAX_P)
     return err(HX_ERR_UNSUPPORTED, "p = %llu: the CRT tables hold 32-bit words and take p < 2^31 = %llu", (unsigned long long)p,
                (unsigned long long)hxc::CRT_MAX_P);
+  const uint64_t P = hxc::crt_modulus(p, (uint32_t)r);
+  if (!P)
+    return err(HX_ERR_UNSUPPORTED, "p^r = %llu^%d: the CRT tables hold 32-bit words and take p^r < 2^31 = %llu",
+               (unsigned long long)p, r, (unsigned long long)hxc::CRT_MAX_P);
   if (m % p == 0)
     return err(HX_ERR_INVALID, "p = %llu divides m = %llu", (unsigned long long)p, (unsigned long long)m);
   if (m < 3 || v.phim % 2 != 0)
     return err(HX_ERR_UNSUPPORTED, "BGV slots need m >= 3 (m = %llu)", (unsigned long long)m);
   hxc::GfTables tab;
-  const std::string why = hxc::build_gf(m, p, tab);
+  const std::string why = hxc::build_gf(m, p, tab, (uint32_t)r);
   if (!why.empty())
     return err(why.rfind("internal", 0) == 0 ? HX_ERR_DEVICE : HX_ERR_UNSUPPORTED, "%s", why.c_str());
   const hxc::CrtTables& c = tab.crt;
@@ -378,10 +392,14 @@ extern "C" int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out)
   } guard{t};
   t->ctx = ctx;
   t->m = m;
-  t->p = p;
+  t->p = P;
+  t->prime = p;
+  t->r = (uint32_t)r;
   t->N = v.phim;
   t->device = v.device;
   t->d = c.d;
+  if (c.limit < 1)
+    return err(HX_ERR_DEVICE, "internal: no multiply-add fits a 64-bit accumulator modulo %llu", (unsigned long long)P);
   t->nslots = c.nslots;
   t->ld = c.ld;
   t->ldr = tab.ldr;
@@ -413,13 +431,26 @@ extern "C" int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out)
   return HX_OK;
 }
 
+extern "C" int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out) { return hx_bgv_gf_create_pr(ctx, p, 1, out); }
+
+extern "C" int hx_bgv_gf_space(const hx_bgv_gf* t, int* r, uint64_t* modulus)
+{
+  if (!t)
+    return err(HX_ERR_INVALID, "null argument");
+  if (r)
+    *r = (int)t->r;
+  if (modulus)
+    *modulus = t->p;
+  return HX_OK;
+}
+
 extern "C" int hx_bgv_gf_info(const hx_bgv_gf* t, uint64_t* p, int* d, int* nslots, int* ndims, uint64_t* gens, int64_t* ords,
                               uint64_t* table_bytes, uint64_t* G)
 {
   if (!t)
     return err(HX_ERR_INVALID, "null argument");
   if (p)
-    *p = t->p;
+    *p = t->prime;
   if (d)
     *d = (int)t->d;
   if (nslots)

@@ -176,6 +176,10 @@ int ensure(hx_bgv_gf_matrix* a, hipStream_t st, int slot, size_t bytes)
 
 int gf_geometry(const hx_bgv_gf* t, uint64_t* p, int* d, int* n, std::vector<uint32_t>& G)
 {
+  int r = 1;
+  RC(hx_bgv_gf_space(t, &r, nullptr));
+  if (r != 1)
+    return err(HX_ERR_UNSUPPORTED, "matrices over Galois-ring slots at p^r with r > 1 are not built (r = %d)", r);
   RC(hx_bgv_gf_info(t, p, d, n, nullptr, nullptr, nullptr, nullptr, nullptr));
   std::vector<uint64_t> g((size_t)*d + 1);
   RC(hx_bgv_gf_info(t, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, g.data()));

@@ -14,7 +14,10 @@
 // polyEval (hx_lin_comb):
 //   out = sum_t w[t] * in[t] + addend,  the terms on prime sets of their own, w and the addend one scalar per prime row
 // (src/polyEval.cpp:240-253: tmp = X^i; tmp.multByConstant(f_i); ret += tmp; then ret.addConstant), one read of every
-// term and one write of the sum.  The unit
+// term and one write of the sum; and of the inner loop of unpack (hx_mul_add_circulant):
+//   out[i] = sum_j c[(i + j) mod d] * in[j],  i < nout <= d
+// (src/intraSlot.cpp:108-115: unpacked[i] = frob[0] * C[i]; then += frob[j] * C[(i + j) mod d]), the d Frobenius images
+// read once per block of outputs instead of once per output.  The unit
 // reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
 #include <hip/hip_runtime.h>
 
@@ -139,6 +142,105 @@ mul_add_many_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, ro
     st_stream2(out0 + row_off + boff[b], make_ulonglong2((uint64_t)a0[b][0], (uint64_t)a0[b][1]));
     if (PARTS == 2)
       st_stream2(out1 + row_off + boff[b], make_ulonglong2((uint64_t)a1[b][0], (uint64_t)a1[b][1]));
+  }
+}
+
+// out0[i] = sum_(j<d) c[(i + j) mod d] * in0[j], out1[i] likewise, i < nout <= d <= CIRC_MAX_D (hx_mul_add_circulant): the
+// words that the loop of unpack (src/intraSlot.cpp:108-115) leaves through hx_poly_copy / hx_mul / hx_add, since the
+// canonical residue of an exact sum of products does not depend on the order of its terms.  The arithmetic is
+// mul_add_many_kernel's: canonical residues accumulated unreduced in 128 bits, from zero; with d <= 64 < MAD_CHUNK
+// products per output word, 64 (2^60 - 2)^2 < 2^126, one reduction at the end is enough.
+//
+// Table (device, uint64 words, read through the constant address space: wave-uniform scalar loads): [0, d) the bases
+// of in0[j]; [d, 2d) of in1[j]; [2d, 2d + nout) of out0[i]; [2d + nout, 2d + 2 nout) of out1[i]; then per output row r
+// and t < d the base of the matching row of c[t], bit 0 set when c[t] has one row per batch element.
+//
+// One thread owns two adjacent coefficients of one prime row of one batch element for a block of OB outputs
+// i0 .. i0 + OB - 1: OB x PARTS x 2 accumulators of 128 bits (OB = 8, PARTS = 2: 128 VGPRs).  It walks j = 0 .. d - 1
+// once: per step it loads in0[j] and in1[j] (16 bytes each, non-temporal) and ONE constant vector -- the OB constants
+// that the block needs at step j, c[(i0 + k + j) mod d], are a window of the circulant that slides by one per step, kept
+// in registers by unrolled moves.  The loads of step j + 1 are issued before the products of step j.  Outputs of the
+// last block past nout are neither accumulated nor stored.  No LDS: nothing is shared between threads.
+// Algorithmic bytes per prime row, batch element and block of OB outputs, in rows of 8 N bytes: PARTS d input rows and
+// d + OB - 1 constant rows read, PARTS OB output rows written; with nb = ceil(nout / OB) blocks the call moves
+//   8 N rows batch (nb (PARTS d + d + OB - 1) + PARTS nout)  bytes
+// against 8 N rows batch nout d PARTS 8 of the d^2 copies, products and additions it replaces (per part and term a copy
+// reads a row and writes one, a product reads two and writes one, a sum the same: 2 + 3 + 3 rows).  For d <= OB every operand word leaves
+// HBM once (batch-1 constants are re-read per batch element, out of the L2).
+constexpr int CIRC_MAX_D = 64;
+static_assert(CIRC_MAX_D <= MAD_CHUNK, "one reduction per output word");
+
+template <int PARTS, int OB>
+__global__ void __launch_bounds__(256)
+mul_add_circulant_kernel(ro_u64 tab, int d, int nout, int nblocks, int batch, uint32_t N, MadRows map,
+                         const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b = (int)(blockIdx.z / (uint32_t)nblocks);
+  const int i0 = (int)(blockIdx.z % (uint32_t)nblocks) * OB;
+  const int live = nout - i0 < OB ? nout - i0 : OB;           // outputs of this block (wave-uniform)
+  const PrimeDev pd = primes[map.p[row]];
+  const size_t off = ((size_t)row * batch + b) * N + 2 * (size_t)i;   // in an input or output poly
+  const size_t coff_b = (size_t)b * N + 2 * (size_t)i, coff_1 = 2 * (size_t)i;
+  ro_u64 ctab = tab + 2 * (size_t)d + 2 * (size_t)nout + (size_t)row * d;
+  const auto ldc = [&](int t) {
+    const uint64_t ce = ctab[t];
+    const uint64_t* cp = reinterpret_cast<const uint64_t*>(ce & ~(uint64_t)1);
+    return *reinterpret_cast<const ulonglong2*>(cp + ((ce & 1) ? coff_b : coff_1));
+  };
+  u128 a0[OB][2], a1[OB][2];
+  ulonglong2 w[OB];
+  int t = i0 % d;                                             // the constant the next load takes
+#pragma unroll
+  for (int k = 0; k < OB; k++) {
+    a0[k][0] = a0[k][1] = a1[k][0] = a1[k][1] = 0;
+    w[k] = ldc(t);
+    t = t + 1 == d ? 0 : t + 1;
+  }
+  ulonglong2 nx = ld_stream2(reinterpret_cast<const uint64_t*>(tab[0]) + off), ny = nx;
+  if (PARTS == 2)
+    ny = ld_stream2(reinterpret_cast<const uint64_t*>(tab[d]) + off);
+  for (int j = 0; j < d; j++) {
+    const ulonglong2 x = nx, y = ny;
+    ulonglong2 cn = w[OB - 1];
+    if (j + 1 < d) {                                          // the next step's operands, in flight during the products
+      nx = ld_stream2(reinterpret_cast<const uint64_t*>(tab[j + 1]) + off);
+      if (PARTS == 2)
+        ny = ld_stream2(reinterpret_cast<const uint64_t*>(tab[d + j + 1]) + off);
+      cn = ldc(t);
+      t = t + 1 == d ? 0 : t + 1;
+    }
+#pragma unroll
+    for (int k = 0; k < OB; k++) {
+      if (k < live) {
+        a0[k][0] += (u128)w[k].x * x.x;
+        a0[k][1] += (u128)w[k].y * x.y;
+        if (PARTS == 2) {
+          a1[k][0] += (u128)w[k].x * y.x;
+          a1[k][1] += (u128)w[k].y * y.y;
+        }
+      }
+    }
+#pragma unroll
+    for (int k = 0; k + 1 < OB; k++)
+      w[k] = w[k + 1];
+    w[OB - 1] = cn;
+  }
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t kk = pd.k;
+#pragma unroll
+  for (int k = 0; k < OB; k++) {
+    if (k >= live)
+      break;
+    uint64_t* o0 = reinterpret_cast<uint64_t*>(tab[2 * d + i0 + k]) + off;
+    st_stream2(o0, make_ulonglong2(mad_reduce(a0[k][0], q, mu, mu64, kk), mad_reduce(a0[k][1], q, mu, mu64, kk)));
+    if (PARTS == 2) {
+      uint64_t* o1 = reinterpret_cast<uint64_t*>(tab[2 * d + nout + i0 + k]) + off;
+      st_stream2(o1, make_ulonglong2(mad_reduce(a1[k][0], q, mu, mu64, kk), mad_reduce(a1[k][1], q, mu, mu64, kk)));
+    }
   }
 }
 
@@ -615,6 +717,164 @@ extern "C" int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* cons
     launch<2>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
   else
     launch<1>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+template <int PARTS>
+static void launch_circulant(int ob, dim3 grid, hipStream_t st, const uint64_t* tab, int d, int nout, int nblocks, int batch,
+                             uint32_t N, const hx::MadRows& map, const hx::PrimeDev* primes)
+{
+  if (ob == 4)
+    HX_LAUNCH((hx::mul_add_circulant_kernel<PARTS, 4>), grid, dim3(256), 0, st, hx::as_ro(tab), d, nout, nblocks, batch, N, map,
+              primes);
+  else
+    HX_LAUNCH((hx::mul_add_circulant_kernel<PARTS, 8>), grid, dim3(256), 0, st, hx::as_ro(tab), d, nout, nblocks, batch, N, map,
+              primes);
+}
+
+extern "C" int hx_mul_add_circulant(hx_poly* const* out0, hx_poly* const* out1, int nout, const hx_poly* const* c,
+                                    const hx_poly* const* in0, const hx_poly* const* in1, int d)
+{
+  if (!out0 || !c || !in0)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((out1 == nullptr) != (in1 == nullptr))
+    return err(HX_ERR_INVALID, "out1 and in1 go together (both null for one-part operands)");
+  if (d < 1 || d > hx::CIRC_MAX_D)
+    return err(d < 1 ? HX_ERR_INVALID : HX_ERR_UNSUPPORTED, "hx_mul_add_circulant takes 1 <= d <= %d (d = %d)", hx::CIRC_MAX_D, d);
+  if (nout < 1 || nout > d)
+    return err(HX_ERR_INVALID, "hx_mul_add_circulant takes 1 <= nout <= d (nout = %d, d = %d)", nout, d);
+  const int parts = out1 ? 2 : 1;
+  // every poly, null checks and aliasing first: a refused call touches no output
+  std::vector<const hx_poly*> outs, ins;
+  for (int i = 0; i < nout; i++) {
+    if (!out0[i] || (out1 && !out1[i]))
+      return err(HX_ERR_INVALID, "null poly (output %d)", i);
+    outs.push_back(out0[i]);
+    if (out1)
+      outs.push_back(out1[i]);
+  }
+  for (int t = 0; t < d; t++) {
+    if (!c[t] || !in0[t] || (in1 && !in1[t]))
+      return err(HX_ERR_INVALID, "null poly (term %d)", t);
+    ins.push_back(c[t]);
+    ins.push_back(in0[t]);
+    if (in1)
+      ins.push_back(in1[t]);
+  }
+  {
+    std::vector<const hx_poly*> so(outs), si(ins);
+    std::sort(so.begin(), so.end());
+    std::sort(si.begin(), si.end());
+    if (std::adjacent_find(so.begin(), so.end()) != so.end())
+      return err(HX_ERR_INVALID, "an output appears twice");
+    for (const hx_poly* o : so)
+      if (std::binary_search(si.begin(), si.end(), o))
+        return err(HX_ERR_INVALID, "an output is also an input");
+  }
+  hx_ctx* ctx = hxi::poly_ctx(out0[0]);
+  for (const hx_poly* p : outs)
+    if (hxi::poly_ctx(p) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  for (const hx_poly* p : ins)
+    if (hxi::poly_ctx(p) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  if (v.capturing)
+    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_circulant uploads a pointer table and cannot be captured in a graph");
+  int batch = 0, b2 = 0;
+  std::vector<int> idx, other;
+  RC(shape_of(out0[0], &batch, &idx));
+  const int rows = (int)idx.size();
+  if (rows > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  for (size_t i = 1; i < outs.size(); i++) {
+    RC(shape_of(outs[i], &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "the outputs differ in batch or prime set");
+  }
+  const uint32_t N = v.phim;
+  if (N < 2 || (N & 1))
+    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_circulant needs an even number of coefficients");
+  std::vector<int> crow((size_t)rows * d), cper(d);
+  for (int t = 0; t < d; t++) {
+    RC(shape_of(in0[t], &b2, &other));
+    if (b2 != batch || other != idx)
+      return err(HX_ERR_INVALID, "in0[%d] differs from the outputs in batch or prime set", t);
+    if (in1) {
+      RC(shape_of(in1[t], &b2, &other));
+      if (b2 != batch || other != idx)
+        return err(HX_ERR_INVALID, "in1[%d] differs from the outputs in batch or prime set", t);
+    }
+    RC(shape_of(c[t], &b2, &other));
+    if (b2 != batch && b2 != 1)
+      return err(HX_ERR_INVALID, "c[%d]: batch %d is neither 1 nor %d", t, b2, batch);
+    cper[t] = b2 == batch && batch > 1;
+    for (int r = 0; r < rows; r++) {
+      int at = -1;
+      for (size_t j = 0; j < other.size(); j++)
+        if (other[j] == idx[r]) {
+          at = (int)j;
+          break;
+        }
+      if (at < 0)
+        return err(HX_ERR_INVALID, "c[%d] has no row for prime %d", t, idx[r]);
+      crow[(size_t)r * d + t] = at;
+    }
+  }
+  if (rows == 0)
+    return HX_OK;
+  const int ob = nout <= 4 ? 4 : 8;
+  const int nblocks = (nout + ob - 1) / ob;
+  if ((size_t)batch * nblocks > 65535)
+    return err(HX_ERR_UNSUPPORTED, "batch %d x %d output blocks exceeds the grid", batch, nblocks);
+  if (!*v.linalg) {
+    *v.linalg = new LinState();
+    *v.linalg_free = state_free;
+  }
+  LinState* s = static_cast<LinState*>(*v.linalg);
+  const hipStream_t st = v.stream;
+  const size_t words = 2 * (size_t)d + 2 * (size_t)nout + (size_t)rows * d, bytes = words * 8;
+  int slot = 0;
+  RC(stage_table(s, st, bytes, &slot));
+  uint64_t* h = s->h_tab[slot];
+  uint64_t align = 0;
+  for (int i = 0; i < nout; i++) {
+    uint64_t *o0 = nullptr, *o1 = nullptr;
+    RC(hxi::poly_rows_write(out0[i], &o0));
+    if (out1)
+      RC(hxi::poly_rows_write(out1[i], &o1));
+    h[2 * (size_t)d + i] = (uint64_t)(uintptr_t)o0;
+    h[2 * (size_t)d + nout + i] = (uint64_t)(uintptr_t)o1;
+    align |= h[2 * (size_t)d + i] | h[2 * (size_t)d + nout + i];
+  }
+  const size_t rw = (size_t)batch * N;
+  for (int t = 0; t < d; t++) {
+    h[t] = (uint64_t)(uintptr_t)hxi::poly_rows_read(in0[t]);
+    h[d + t] = in1 ? (uint64_t)(uintptr_t)hxi::poly_rows_read(in1[t]) : 0;
+    const uint64_t* cb = hxi::poly_rows_read(c[t]);
+    const size_t crw = cper[t] ? rw : (size_t)N;
+    for (int r = 0; r < rows; r++)
+      h[2 * (size_t)d + 2 * (size_t)nout + (size_t)r * d + t] =
+          (uint64_t)(uintptr_t)(cb + (size_t)crow[(size_t)r * d + t] * crw) | (uint64_t)cper[t];
+    align |= h[t] | h[d + t] | (uint64_t)(uintptr_t)cb;
+  }
+  if (align & 15)
+    return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
+  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
+  CK(hipEventRecord(s->copied[slot], st));
+  s->pending[slot] = true;
+  hx::MadRows map;
+  for (int r = 0; r < rows; r++)
+    map.p[r] = (uint16_t)idx[r];
+  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)(batch * nblocks));
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  if (parts == 2)
+    launch_circulant<2>(ob, grid, st, s->d_tab, d, nout, nblocks, batch, N, map, primes);
+  else
+    launch_circulant<1>(ob, grid, st, s->d_tab, d, nout, nblocks, batch, N, map, primes);
   CK(hipGetLastError());
   return HX_OK;
 }

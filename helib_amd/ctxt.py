@@ -1622,6 +1622,139 @@ class Ctxt:
         ret.lnNoise = ln
         return ret
 
+    fuseCirculant = False  # fused=None: the call sequence until hx_mul_add_circulant has been measured as the faster form
+
+    @staticmethod
+    def circulantCombination(cts, consts, n=None, size=-1.0, fused=None):
+        """out[i] = sum_j consts[(i + j) mod d] * cts[j] for i < n <= d = len(cts) = len(consts), as n new ciphertexts:
+        the loop of unpack (src/intraSlot.cpp:107-116) -- out[i] = cts[0]; out[i].multByConstant(consts[i]); then per
+        j >= 1 tmp = cts[j]; tmp.multByConstant(consts[(i + j) mod d]); out[i] += tmp.  consts are DoubleCRTs on a
+        superset of every term's primes, `size` their multByConstant size (< 0: the default bound).
+        Fused: the same steps once on parts that hold no rows and only record the integers the steps would have
+        multiplied into each term's words (bal(e2) on the new term and bal(e1) on everything before it when addCtxt
+        harmonises the intFactors; the mod-ups are exact scalings too) -- every out[i] has the same bookkeeping, the
+        constants differing in their words alone -- then per term at most one mod-up to the union of the prime sets and
+        one product by its integer, and one ops.mulAddCirculant (hx_mul_add_circulant) for the d^2 multiply-adds.  Exact
+        sums modulo a prime do not depend on their order: words, lnNoise, primeSet, ptxtSpace, intFactor and ptxtMag are
+        those of the sequence.  It applies to a BGV context when every term holds the canonical parts {1, s}, or all the
+        same single part, d <= 64, on a backend with mulAddCirculant; otherwise, and with fused=False, the sequence
+        runs as it is.  fused=True insists on such a backend; fused=None follows Ctxt.fuseCirculant.  The terms are left
+        as they were."""
+        d = len(cts)
+        if d < 1 or len(consts) != d:
+            raise ValueError("circulantCombination takes d >= 1 ciphertexts and d constants")
+        n = d if n is None else int(n)
+        if not 1 <= n <= d:
+            raise ValueError("circulantCombination: 1 <= n <= d")
+        has = hasattr(cts[0].ops, "mulAddCirculant")
+        if fused and not has:
+            raise RuntimeError("Ctxt::circulantCombination: fused=True, but this backend has no mulAddCirculant")
+        if (Ctxt.fuseCirculant if fused is None else fused) and has:
+            out = Ctxt._circulantFused(cts, consts, n, size)
+            if out is not None:
+                return out
+        out = []
+        for i in range(n):
+            u = cts[0].clone()
+            u.multByConstant(consts[i], size)
+            for j in range(1, d):
+                tmp = cts[j].clone()
+                tmp.multByConstant(consts[(i + j) % d], size)
+                u += tmp
+            out.append(u)
+        return out
+
+    @staticmethod
+    def _circulantFused(cts, consts, n, size):
+        """circulantCombination's fused form, or None where it does not apply (nothing has been touched then)"""
+        d, ctx, ops = len(cts), cts[0].context, cts[0].ops
+        if ctx.ckks or d > 64:
+            return None
+        for ct in cts:
+            ct._materializeTensor()
+        hs = sorted(cts[0].parts, key=str)
+        if not (hs == ["1", "s"] or len(hs) == 1):
+            return None
+        for ct in cts:
+            if sorted(ct.parts, key=str) != hs:
+                return None
+            ix = ct.parts[hs[0]].getIndexSet()
+            if any(ct.parts[h].getIndexSet() != ix for h in hs[1:]):
+                return None
+
+        class Track:
+            """a part without rows: term -> the integer its words have been multiplied by so far"""
+
+            def __init__(self, mult):
+                self.mult = dict(mult)
+
+            def copy(self):
+                return Track(self.mult)
+
+            def __imul__(self, o):                       # a constant: its words are the kernel's to multiply in
+                if isinstance(o, (int, float, complex)):
+                    raise _NotTracked("*= number")
+                return self
+
+            def __getattr__(self, name):                 # anything else the sequence might do needs the rows
+                raise _NotTracked(name)
+
+            def mulConstant(self, c):
+                self.mult = {j: m * int(c) for j, m in self.mult.items()}
+                return self
+
+            def addPrimesAndScale(self, s):              # exact: done on the term's own rows below
+                return self
+
+            def __iadd__(self, o):
+                for j, m in o.mult.items():
+                    self.mult[j] = self.mult.get(j, 0) + m
+                return self
+
+        def shadow(j):
+            ct = cts[j]
+            c = Ctxt(ctx, ops, ct.ksw, ct.ksw_ptxtSpace, ct.ksw_lnNoise)
+            c.primeSet, c.ptxtSpace, c.intFactor = ct.primeSet, ct.ptxtSpace, ct.intFactor
+            c.lnNoise, c.ptxtMag, c.lnRatFactor = ct.lnNoise, ct.ptxtMag, ct.lnRatFactor
+            c.parts = {h: Track({j: 1}) for h in hs}
+            return c
+        try:
+            su = shadow(0)
+            su.multByConstant(None, size)
+            for j in range(1, d):
+                tmp = shadow(j)
+                tmp.multByConstant(None, size)
+                su += tmp
+        except _NotTracked:
+            return None
+        mult = su.parts[hs[0]].mult
+        union = su.primeSet
+        terms = []
+        for j, ct in enumerate(cts):
+            m = mult[j]
+            if ct.primeSet != union or m != 1:
+                ct = ct.clone()
+                ct.modUpToSet(union)
+                for p in ct.parts.values():
+                    p.mulConstant(m)
+            terms.append(ct)
+        idx = terms[0].parts[hs[0]].getIndexSet()
+        if any(t.parts[h].getIndexSet() != idx for t in terms for h in hs):
+            return None                                   # the rows of the terms are in different orders
+        make = getattr(ops, "likeUninit", None) or ops.zerosLike
+        outs = [[make(terms[0].parts[h]) for _ in range(n)] for h in hs]
+        ops.mulAddCirculant(outs[0], outs[1] if len(hs) == 2 else None, list(consts), [t.parts[hs[0]] for t in terms],
+                            [t.parts[hs[1]] for t in terms] if len(hs) == 2 else None)
+        res = []
+        for i in range(n):
+            c = cts[0]._emptyLike()
+            c.parts = {h: outs[k][i] for k, h in enumerate(hs)}
+            c.primeSet, c.ptxtSpace, c.intFactor = su.primeSet, su.ptxtSpace, su.intFactor
+            c.ptxtMag, c.lnRatFactor = su.ptxtMag, su.lnRatFactor
+            c.lnNoise = su.lnNoise
+            res.append(c)
+        return res
+
     def cleanUp(self):
         """Ctxt::cleanUp (src/Ctxt.cpp:788-797)"""
         self.reLinearize()
@@ -1629,6 +1762,10 @@ class Ctxt:
         if self.primeSet & (frozenset(ctx.specialPrimes) | frozenset(ctx.smallPrimes)):
             self.dropSmallAndSpecialPrimes()
         return self
+
+
+class _NotTracked(Exception):
+    """a step of the call sequence that Ctxt._circulantFused's row-less parts cannot record: the sequence runs instead"""
 
 
 class DynamicCtxtPowers:

@@ -443,6 +443,18 @@ typedef struct hx_bgv_gf hx_bgv_gf; /* the tables of one (context, p) pair */
 /* Replaces PAlgebraModDerived's constructor and mapToSlots at G = F_0 (src/PAlgebra.cpp:680-772, 1116-1186).  The
  * refusals of hx_bgv_crt_create, and d > 64: HX_ERR_UNSUPPORTED with the figures. */
 int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out);
+/* The same tables for the plaintext space p^r, r >= 1: a slot is an element of the Galois ring Z_(p^r)[X] / G, G the
+ * Hensel lift of F_0 (the EncryptedArray RecryptData::init builds over p^(e - e' + r), src/recryption.cpp:310-343).
+ * Every table is the same formula modulo p^r over the lifted factors of hx_bgv_crt_create_pr -- the lift of a
+ * factorisation is unique, so X -> X^(t_i) carries the lifted F_0 to the lifted F_i -- and the per-slot map is inverted
+ * with pivots that are units.  hx_bgv_gf_encode, _decode and _embed then work modulo p^r wherever their descriptions
+ * say p; hx_bgv_gf_info gives the prime and the lifted G; a slot (a, 0, ..., 0) is the integer a of
+ * hx_bgv_crt_create_pr, word for word.  r = 1 is hx_bgv_gf_create, byte for byte.  r < 1: HX_ERR_INVALID; p^r >= 2^31:
+ * HX_ERR_UNSUPPORTED with the figure; otherwise the errors of hx_bgv_gf_create.  hx_bgv_gf_matrix_create refuses a
+ * table with r > 1. */
+int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** out);
+/* The exponent r and the modulus p^r of the table's maps (hx_bgv_gf_info gives p); either output may be NULL. */
+int hx_bgv_gf_space(const hx_bgv_gf* t, int* r, uint64_t* modulus);
 int hx_bgv_gf_destroy(hx_bgv_gf* t);
 /* As hx_bgv_crt_info; table_bytes counts every device table; G receives d + 1 words, the constant coefficient first
  * (PAlgebraMod::getFactors()[0], src/PAlgebra.cpp:715-721).  Any output may be NULL. */
@@ -507,6 +519,24 @@ int hx_bgv_gf_gather(const hx_bgv_gf_matrix* a, const hx_bgv_gf_desc* descs, int
  * touching the device. */
 int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* const* c, const hx_poly* const* in0,
                     const hx_poly* const* in1, int n, int accumulate);
+/* The inner loop of unpack (src/intraSlot.cpp:108-115:
+ *   unpacked[i] = frob[0];  unpacked[i].multByConstant(C[i]);
+ *   for j = 1 .. d-1:  tmp = frob[j];  tmp.multByConstant(C[(i + j) mod d]);  unpacked[i] += tmp;)
+ * on the parts of d ciphertexts, in one pass:
+ *   out0[i] = sum_(j<d) c[(i + j) mod d] * in0[j],   out1[i] likewise,   0 <= i < nout <= d <= 64,
+ * row by row modulo each prime; every word is canonical in [0, q) and equal to what the hx_poly_copy / hx_mul / hx_add
+ * sequence leaves (an exact sum modulo q does not depend on the order of its terms).  All operands are in evaluation
+ * form.  in0[j], in1[j] and the outputs share one batch and one prime set (same order); in1 and out1 are both null for
+ * one-part operands.  c[t] has batch 1 (broadcast over the batch) or that batch, and may live on more primes than the
+ * outputs: its rows are matched by prime index, a missing prime is HX_ERR_INVALID.  The outputs are overwritten, not
+ * read.  Null arguments, nout < 1, nout > d, d < 1, a poly of another context, mismatched shapes, an output that is also
+ * an input or appears twice are HX_ERR_INVALID; d > 64 and an odd phi(m) are HX_ERR_UNSUPPORTED; a refused call touches
+ * no output.  Asynchronous on the context's stream.  It uploads a table of operand pointers through the staging ring of
+ * hx_mul_add_many, so like that call it cannot be recorded: under an open graph capture it returns HX_ERR_UNSUPPORTED
+ * before touching the device.  Per block of OB outputs (OB = 4 for nout <= 4, else 8) it reads the 2 d input rows and
+ * d + OB - 1 constant rows once. */
+int hx_mul_add_circulant(hx_poly* const* out0, hx_poly* const* out1, int nout, const hx_poly* const* c,
+                         const hx_poly* const* in0, const hx_poly* const* in1, int d);
 /* dst (batch 1, the prime set of src in the same order) <- batch element b of src: how a batch of encoded diagonals
  * becomes the batch-1 constants above.  Asynchronous on the context's stream; works under a graph capture. */
 int hx_poly_extract(hx_poly* dst, const hx_poly* src, int b);
