@@ -21,7 +21,9 @@ halves and (poly1, dim, D) of the reference are all of this form.
                 in chunks through capi.bgvGfGather (bgv_gf_gather_kernel) and ea.enc.encode
   host path     numpy does both, then ea.enc.encode: a callable matrix, an injected encoder, device_diagonals=False
 
-Both give the same words and sizes.  Refused with a message: BlockMatMulFull*, MatMulFull with GF entries,
+Both give the same words and sizes.  The bodies are private helpers that take the modulus of the slot words and the
+tables (_evalLinPolyMod, _frobEachMod, _mulPlainMod, _hostConstantMod, _constants, the hooks of _GfMatrix and of the exec
+classes): helib_amd.bgv_gr_matmul runs them modulo p^r over helib_amd.bgv_gr.EncryptedArray.  Refused with a message: BlockMatMulFull*, MatMulFull with GF entries,
 multipleTransforms for the GF-entry MatMul1D, r > 1 (bgv_gf.EncryptedArray refuses it).  Nothing here imports oracle/."""
 import os
 import time
@@ -153,7 +155,12 @@ def linPolyFlat(ea, E):
 
 def evalLinPoly(ea, C, a):
     """sum_k C[k] alpha^(p^k) slot by slot: C [d, d] (one map) or [nslots, d, d], a slots -> [B, nslots, d]"""
-    a, p, d = ea._slots(a) % ea.p, ea.p, ea.getDegree()
+    return _evalLinPolyMod(ea, C, a, ea.p)
+
+
+def _evalLinPolyMod(ea, C, a, p):
+    """evalLinPoly with the modulus p of the slot words (ea.frobeniusPlain is sigma^k)"""
+    a, d = ea._slots(a) % p, ea.getDegree()
     C = np.asarray(C, dtype=np.int64) % p
     C = np.broadcast_to(C, (ea.size(), d, d)) if C.ndim == 2 else C
     out = np.zeros_like(a)
@@ -169,6 +176,12 @@ def slotAutomorph(ea, k):
     zeta^(k / t_j) = zeta^(p^e / t_i) for the slot i whose coset holds t_j / k, with t_i k = t_j p^e (mod m), and H(y^(p^e))
     = H(y)^(p^e) over Z_p."""
     _check(ea)
+    return _slotAutomorph(ea, k)
+
+
+def _slotAutomorph(ea, k):
+    """slotAutomorph for any array with bgv_gf's geometry (ea.p the prime): over Z_(p^r) the same holds with sigma^e for
+    the e-th power of the Frobenius, because sigma fixes the lifted F_0"""
     m = ea.m
     k %= m
     cache = ea.__dict__.setdefault("_slotAut", {})
@@ -184,11 +197,16 @@ def slotAutomorph(ea, k):
 
 def _frobEach(ea, a, e):
     """slot s of a [B, n, d] -> its Frob^e[s]"""
-    fr, out = _tables(ea).frob, a.copy()
+    return _frobEachMod(a, e, _tables(ea).frob, ea.p)
+
+
+def _frobEachMod(a, e, fr, p):
+    """_frobEach over the tables fr = frob [d, d, d] modulo p"""
+    out = a.copy()
     for x in np.unique(e):
         if x:
             w = e == x
-            out[:, w] = _matmod(a[:, w], fr[x], ea.p)
+            out[:, w] = _matmod(a[:, w], fr[x], p)
     return out
 
 
@@ -211,14 +229,30 @@ def _geometry(ea, dim):
 
 
 def _ints(ea, a):
+    return _intsMod(a, ea.p)
+
+
+def _intsMod(a, p):
     a = np.asarray(a)
     if a.dtype == object or a.dtype.kind not in "iu" or a.dtype == np.uint64:
-        a = np.array([int(x) % ea.p for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
-    return np.ascontiguousarray(a.astype(np.int64) % ea.p)
+        a = np.array([int(x) % p for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
+    return np.ascontiguousarray(a.astype(np.int64) % p)
 
 
 class _GfMatrix:
     block = False
+    ring = False               # the device matrix is built over a table of any r (capi.BgvGfMatrix(ring=True))
+
+    # what a module over another ring of slots replaces: the check of the array, the modulus of the words, the
+    # linearized-polynomial coefficients of the blocks
+    _checkArray = staticmethod(lambda ea: _check(ea))
+
+    @staticmethod
+    def _modulus(ea):
+        return ea.p
+
+    def _coeffs(self, dense):
+        return buildLinPolyCoeffs(self.ea, dense)
 
     def getDim(self):
         return self.dim
@@ -229,13 +263,14 @@ class _GfMatrix:
     def handle(self, enc):
         """the matrix on the device: uploaded (and, for blocks, turned into coefficients) once"""
         if self._handle is None:
-            self._handle = capi.BgvGfMatrix(enc.table, self.dense, self.blk if self.multiple else np.zeros_like(self.blk), self.col)
+            self._handle = capi.BgvGfMatrix(enc.table, self.dense, self.blk if self.multiple else np.zeros_like(self.blk), self.col,
+                                            ring=self.ring)
         return self._handle
 
     def values(self):
         """[nb, D, D, K, d]: what a slot can hold -- K = d coefficients of every block's linearized polynomial, or K = 1"""
         if self._values is None:
-            self._values = buildLinPolyCoeffs(self.ea, self.dense) if self.block else self.dense[:, :, :, None, :]
+            self._values = self._coeffs(self.dense) if self.block else self.dense[:, :, :, None, :]
         return self._values
 
     def slotValues(self, i, k):
@@ -249,16 +284,17 @@ class MatMul1D(_GfMatrix):
     get(i, j) -> d coefficients (or an integer)"""
 
     def __init__(self, ea, A, dim):
-        _check(ea)
+        self._checkArray(ea)
         if not 0 <= dim < ea.dimension():
             raise LogicError("Matrix dimension not in [0, ea.dimension())")
         self.ea, self.dim, self.multiple, d = ea, dim, False, ea.getDegree()
         self.D, self.blk, self.col = _geometry(ea, dim)
         self.callable = callable(A)
+        p = self._modulus(ea)
         if self.callable:
-            rows = [[np.atleast_1d(_ints(ea, A(i, j))) for j in range(self.D)] for i in range(self.D)]
+            rows = [[np.atleast_1d(_intsMod(A(i, j), p)) for j in range(self.D)] for i in range(self.D)]
             A = [[np.pad(x, (0, d - len(x))) for x in r] for r in rows]
-        a = _ints(ea, A)
+        a = _intsMod(A, p)
         if a.ndim >= 4:
             raise LogicError("MatMul1D with GF entries: multipleTransforms (%d axes) is not built; BlockMatMul1D takes one "
                              "matrix per transform" % a.ndim)
@@ -278,7 +314,7 @@ class BlockMatMul1D(_GfMatrix):
     block = True
 
     def __init__(self, ea, A, dim):
-        _check(ea)
+        self._checkArray(ea)
         if not 0 <= dim <= ea.dimension():
             raise LogicError("Matrix dimension not in [0, ea.dimension()]")
         self.ea, self.dim, d, n = ea, dim, ea.getDegree(), ea.size()
@@ -286,7 +322,7 @@ class BlockMatMul1D(_GfMatrix):
         self.callable = callable(A)
         if self.callable:
             raise LogicError("BlockMatMul1D takes a dense array")
-        a = _ints(ea, A)
+        a = _intsMod(A, self._modulus(ea))
         self.multiple = a.ndim == 5
         if dim == ea.dimension() and not self.multiple:
             raise LogicError("BlockMatMul1D along the size-1 dimension takes one block per slot: [%d, 1, 1, %d, %d]" % (n, d, d))
@@ -316,7 +352,12 @@ def mulPlain(ea, v, mat):
     """mul(PlaintextArray, MatMul1D / BlockMatMul1D) on slots v -> int64 [B, nslots, d]: along mat's dimension and for
     every transform k, w[k][j] = sum_i v[k][i] * A_k[i][j] -- the product in Z_p[X] / G for a GF entry, the coefficient
     row vector times the d x d block for a block entry"""
-    v, p, d, D = ea._slots(v) % ea.p, ea.p, ea.getDegree(), mat.D
+    return _mulPlainMod(ea, v, mat, ea.p)
+
+
+def _mulPlainMod(ea, v, mat, p):
+    """mulPlain with the modulus p of the slot words (ea._mul is the product of the slots' ring)"""
+    v, d, D = ea._slots(v) % p, ea.getDegree(), mat.D
     B, n = v.shape[0], ea.size()
     order = np.argsort(mat.blk * D + mat.col, kind="stable")           # slot of (transform, coordinate)
     x = v[:, order].reshape(B, n // D, D, d)
@@ -342,7 +383,7 @@ class _Maps:
         self.ea, self.rows, self.index = ea, [], {}
 
     def add(self, k, mask=None):
-        perm, frob = slotAutomorph(self.ea, k)
+        perm, frob = _slotAutomorph(self.ea, k)
         src = perm if mask is None else np.where(np.asarray(mask)[perm] != 0, perm, -1)
         row = np.stack([src, np.where(src >= 0, frob, 0)], axis=1).astype(np.int32)
         key = row.tobytes()
@@ -354,31 +395,48 @@ class _Maps:
 
 def hostConstant(ea, mat, i, k, row):
     """one constant on the host: slot s = Frob^e(coefficient k of the entry the slot src[s] reads on diagonal i)"""
+    return _hostConstantMod(mat, i, k, row, _tables(ea).frob, ea.p)
+
+
+def _hostConstantMod(mat, i, k, row, fr, p):
+    """hostConstant over the tables fr = frob [d, d, d] modulo p"""
     src, e = row[:, 0].astype(np.int64), row[:, 1].astype(np.int64)
     val = mat.slotValues(i, k)
     out = np.where((src >= 0)[:, None], val[np.maximum(src, 0)], 0)
-    return _frobEach(ea, out[None], e)[0]
+    return _frobEachMod(out[None], e, fr, p)[0]
 
 
-def _constants(ea, mat, reqs, maps, idx, device):
-    """reqs [(i, k, map)] -> [None for a zero constant | (DoubleCRT of batch 1 on idx, size)]"""
+def _constants(ea, mat, reqs, maps, idx, device, fused=False, const=None, batch=None):
+    """reqs [(i, k, map)] -> [None for a zero constant | (DoubleCRT of batch 1 on idx, size)].  const(i, k, row): one
+    constant on the host (default hostConstant).  fused (device only): the constants never leave the device --
+    enc.encodeGathered gives the flags of a chunk, then the live descriptors go through it in the encoder's batches.
+    batch: constants per encode call for an encoder that is no GfEncoder and names no max_batch (None: one)"""
     enc = ea.enc
-    step = max(1, int(getattr(enc, "max_batch", 16 if isinstance(enc, bgv_gf.GfEncoder) else 1)))
+    step = max(1, int(getattr(enc, "max_batch", (batch or 16) if isinstance(enc, bgv_gf.GfEncoder) or batch else 1)))
     split = getattr(enc, "split", lambda poly: [poly])
     out = [None] * len(reqs)
     table = np.stack(maps.rows) if maps.rows else None
     handle = mat.handle(enc) if device else None
+    if const is None:
+        def const(i, k, row):
+            return hostConstant(ea, mat, i, k, row)
     for lo in range(0, len(reqs), GATHER_CHUNK):
         chunk = reqs[lo:lo + GATHER_CHUNK]
-        if device:
+        if device and fused:
+            descs = np.array(chunk, dtype=np.int32)
+            nz = enc.encodeGathered(handle, descs, table, 1, idx, flags_only=True)
+        elif device:
             slots, nz = capi.bgvGfGather(handle, np.array(chunk, dtype=np.int32), table)
         else:
-            slots = np.stack([hostConstant(ea, mat, i, k, maps.rows[mp]) for i, k, mp in chunk])
+            slots = np.stack([const(i, k, maps.rows[mp]) for i, k, mp in chunk])
             nz = slots.reshape(len(chunk), -1).any(axis=1)
         live = [int(t) for t in np.nonzero(nz)[0]]
         for a in range(0, len(live), step):
             where = live[a:a + step]
-            poly, cf = enc.encode(slots[where], 1, idx, coeffs=True)
+            if device and fused:
+                poly, cf, _ = enc.encodeGathered(handle, descs[where], table, 1, idx, coeffs=True)
+            else:
+                poly, cf = enc.encode(slots[where], 1, idx, coeffs=True)
             for t, dcrt, sz in zip(where, split(poly), enc.norm(cf)):
                 out[lo + t] = (dcrt, float(sz))
     return out
@@ -394,11 +452,16 @@ class MatMul1DExec(bgv_hypercube.MatMul1DExec):
     bgv_hypercube.MatMul1DExec (non-native: multiplier / multiplier1), with the plaintext automorphisms of GF slots; mul
     is theirs"""
 
+    _Matrix = MatMul1D         # the matrix class a bare array is wrapped in
+
+    def _consts(self, reqs, maps, idx):
+        return _constants(self.ea, self.mat, reqs, maps, idx, self.onDevice)
+
     def __init__(self, ea, mat, minimal=False, dim=None, device_diagonals=None):
-        if not isinstance(mat, MatMul1D):
+        if not isinstance(mat, self._Matrix):
             if dim is None:
                 raise LogicError("MatMul1DExec: a bare matrix needs its dimension (or pass a MatMul1D)")
-            mat = MatMul1D(ea, mat, dim)
+            mat = self._Matrix(ea, mat, dim)
         self.ea, self.mat, self.minimal = ea, mat, minimal
         self.dim = dim = mat.getDim()
         self.native = ea.nativeDimension(dim)
@@ -416,7 +479,7 @@ class MatMul1DExec(bgv_hypercube.MatMul1DExec):
             self.rotation = [(-g * (i // g)) if g else 0 for i in range(D)]
             reqs = [(i, 0, maps.add(z.genToPow(dim, self.rotation[i]))) for i in range(D)]
             idx = list(cc.ctxtPrimes) + (list(cc.specialPrimes) if g == 0 else [])
-            self.multiplier = _constants(ea, mat, reqs, maps, idx, self.onDevice)
+            self.multiplier = self._consts(reqs, maps, idx)
         else:
             # :644-688: vec[i] = (diag * mask_i) moved by rho^(-g k), vec1[i] = (diag - diag * mask_i) moved by
             # rho^(DD - g k), k = i / g (g = 0: no move and DD = D)
@@ -424,7 +487,7 @@ class MatMul1DExec(bgv_hypercube.MatMul1DExec):
                 k, mask = (i // g if g else 1), ea.maskSlots(dim, i)
                 reqs.append((i, 0, maps.add(z.genToPow(dim, -g * k), mask)))
                 reqs.append((i, 0, maps.add(z.genToPow(dim, (0 if g else D) - g * k), 1 - mask)))
-            both = _constants(ea, mat, reqs, maps, list(cc.ctxtPrimes) + list(cc.specialPrimes), self.onDevice)
+            both = self._consts(reqs, maps, list(cc.ctxtPrimes) + list(cc.specialPrimes))
             self.multiplier, self.multiplier1 = both[0::2], both[1::2]
         self._tick("construct", t0)
 
@@ -433,11 +496,16 @@ class BlockMatMul1DExec(bgv_matmul.MatMul1DExec):
     """BlockMatMul1DExec (src/matmul.cpp:1514-1976).  vec / vec1 hold None or (DoubleCRT of batch 1, size), indexed as
     the reference: [i * d + j] for strategy +1 (D >= d, the Frobenius factored out), [i + j * D] for strategy -1"""
 
+    _Matrix = BlockMatMul1D
+
+    def _consts(self, reqs, maps, idx):
+        return _constants(self.ea, self.mat, reqs, maps, idx, self.onDevice)
+
     def __init__(self, ea, mat, minimal=False, dim=None, device_diagonals=None):
-        if not isinstance(mat, BlockMatMul1D):
+        if not isinstance(mat, self._Matrix):
             if dim is None:
                 raise LogicError("BlockMatMul1DExec: a bare matrix needs its dimension (or pass a BlockMatMul1D)")
-            mat = BlockMatMul1D(ea, mat, dim)
+            mat = self._Matrix(ea, mat, dim)
         self.ea, self.mat, self.minimal = ea, mat, minimal
         self.dim = dim = mat.getDim()
         self.D, self.d = D, d = mat.D, ea.getDegree()
@@ -469,7 +537,7 @@ class BlockMatMul1DExec(bgv_matmul.MatMul1DExec):
                     reqs1.append((i, j, maps.add(k1, 1 - mask)))
         # the rotated ciphertexts come from a hoisting precon, on the ctxt and special primes: the constants live on both
         idx = list(cc.ctxtPrimes) + list(cc.specialPrimes)
-        got = _constants(ea, mat, reqs + reqs1, maps, idx, self.onDevice)
+        got = self._consts(reqs + reqs1, maps, idx)
         self.vec, self.vec1 = [None] * (D * d), ([None] * (D * d) if not self.native else None)
         for t, at in enumerate(where):
             self.vec[at] = got[t]
@@ -560,6 +628,10 @@ def applyLinPolyLL(ct, encodedC):
 def applyLinPoly1(ea, ct, C):
     """the same map in every slot (:802-821): C [d, d] from buildLinPolyCoeffs"""
     _check(ea)
+    return _applyLinPoly1(ea, ct, C)
+
+
+def _applyLinPoly1(ea, ct, C):
     d = ea.getDegree()
     C = np.asarray(C, dtype=np.int64)
     if C.shape != (d, d):
@@ -570,6 +642,10 @@ def applyLinPoly1(ea, ct, C):
 def applyLinPolyMany(ea, ct, Cvec):
     """another map in every slot (:826-850): Cvec [nslots, d, d], row i from buildLinPolyCoeffs for slot i"""
     _check(ea)
+    return _applyLinPolyMany(ea, ct, Cvec)
+
+
+def _applyLinPolyMany(ea, ct, Cvec):
     d = ea.getDegree()
     Cvec = np.asarray(Cvec, dtype=np.int64)
     if Cvec.shape != (ea.size(), d, d):

@@ -22,7 +22,8 @@ At r = 1 the class gives helib_amd.bgv_gf.EncryptedArray's words.  Unpacking a s
 coordinates and back is helib_amd.intraslot.
 
 Out of scope, refused with a message: a G other than the lifted F_0, d > 64, p^r >= 2^31, and every product of
-helib_amd.bgv_matmul / bgv_gf_matmul over this class at r > 1 (their _modPOnly / _check refuse an array with r > 1).
+helib_amd.bgv_matmul / bgv_gf_matmul over this class at r > 1 (their _modPOnly / _check refuse an array with r > 1;
+helib_amd.bgv_gr_matmul has the linear maps on these slots).
 Nothing here imports oracle/."""
 import numpy as np
 
@@ -48,6 +49,11 @@ class GrEncoder:
 
     def encode(self, v, mul, idx, coeffs=False):
         return capi.bgvGfEncode(self.table, v, idx, mul, coeffs=coeffs)
+
+    def encodeGathered(self, matrix, descs, maps, mul, idx, coeffs=False, flags_only=False):
+        """the constants of a capi.BgvGfMatrix gathered, twisted and encoded without leaving the device
+        (hx_bgv_gf_encode_gathered); flags_only: the non-zero flags alone"""
+        return capi.bgvGfEncodeGathered(self.table, matrix, descs, maps, idx, mul, coeffs=coeffs, flags_only=flags_only)
 
     def split(self, poly):
         return capi.splitBatch(poly)

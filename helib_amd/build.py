@@ -35,8 +35,9 @@ UNIT_HEADERS = {"pfa_kernels.hip": ["pfa_core.h", "pfa_dev.h"], "rns_mfma_kernel
                 "engine.hip": ["pfa_core.h", "pfa_dev.h", "switches.h", "mfma_ext.h", "rns_mfma_dev.h", "ckks_bridge.h"],
                 "ckks_slots.hip": ["ckks_slots.h", "ckks_bridge.h"], "bgv_slots.hip": ["bgv_slots.h", "bgv_encode.h", "ckks_bridge.h"],
                 "bgv_crt.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "ckks_bridge.h"],
-                "bgv_gf.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "bgv_gf.h", "ckks_bridge.h"],
-                "bgv_gf_linalg.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "bgv_gf.h", "bgv_gf_linalg.h", "ckks_bridge.h"],
+                "bgv_gf.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "bgv_gf.h", "bgv_gf_tail.h", "ckks_bridge.h"],
+                "bgv_gf_linalg.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "bgv_gf.h", "bgv_gf_linalg.h", "bgv_gf_tail.h",
+                                      "gather_map.h", "ckks_bridge.h"],
                 "linalg.hip": ["ckks_bridge.h"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value",
          "-Wno-pass-failed"]

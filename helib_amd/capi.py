@@ -68,6 +68,7 @@ SYMBOLS = [
     "hx_bgv_gf_create", "hx_bgv_gf_destroy", "hx_bgv_gf_info", "hx_bgv_gf_encode", "hx_bgv_gf_decode", "hx_bgv_gf_embed",
     "hx_bgv_gf_create_pr", "hx_bgv_gf_space",
     "hx_bgv_gf_linalg_tables", "hx_bgv_gf_matrix_create", "hx_bgv_gf_matrix_destroy", "hx_bgv_gf_matrix_coeffs", "hx_bgv_gf_gather",
+    "hx_bgv_gr_linalg_tables", "hx_bgv_gr_matrix_create", "hx_bgv_gf_encode_gathered",
 ]
 
 
@@ -188,6 +189,9 @@ def lib():
             "hx_bgv_gf_matrix_create": [vp, vp, ip, ip, ip, vp, vp, vp, vp], "hx_bgv_gf_matrix_destroy": [vp],
             "hx_bgv_gf_matrix_coeffs": [vp, vp],
             "hx_bgv_gf_gather": [vp, vp, ip, vp, ip, vp, vp],
+            "hx_bgv_gr_linalg_tables": [u64, ip, ip, vp, vp, vp, vp],
+            "hx_bgv_gr_matrix_create": [vp, vp, ip, ip, ip, vp, vp, vp, vp],
+            "hx_bgv_gf_encode_gathered": [vp, vp, vp, ip, vp, ip, u64, vp, vp, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -924,12 +928,22 @@ def bgvGfLinalgTables(p, d, G):
     return frob.reshape(d, d, d), K.reshape(d, d, d), T.reshape(d * d, d * d)
 
 
+def bgvGrLinalgTables(p, r, d, G):
+    """bgvGfLinalgTables modulo p^r over the lifted G (hx_bgv_gr_linalg_tables): frob, K and T over Z_(p^r); uint32."""
+    d = int(d)
+    g = (C.c_uint64 * (d + 1))(*[int(x) for x in G])
+    frob, K, T = (np.zeros(max(d, 1) ** e, dtype=np.uint32) for e in (3, 3, 4))
+    _chk(lib().hx_bgv_gr_linalg_tables(int(p), int(r), d, g, _p(frob), _p(K), _p(T)))
+    return frob.reshape(d, d, d), K.reshape(d, d, d), T.reshape(d * d, d * d)
+
+
 class BgvGfMatrix:
     """A matrix over GF(p^d) slots on the device (hx_bgv_gf_matrix): GF entries words[nb, D, D, d] or blocks
     words[nb, D, D, d, d] (integers in [0, p)); blk / col [nslots]: the transform and the column every slot reads.  For
-    blocks the linearized-polynomial coefficients of every entry are formed on the device at creation."""
+    blocks the linearized-polynomial coefficients of every entry are formed on the device at creation.  ring=True builds
+    over a table of any r (hx_bgv_gr_matrix_create: words in [0, p^r)); the default refuses r > 1."""
 
-    def __init__(self, table, words, blk, col):
+    def __init__(self, table, words, blk, col, ring=False):
         w = np.ascontiguousarray(np.asarray(words), dtype=np.uint32)
         if w.ndim not in (4, 5) or w.shape[1] != w.shape[2] or any(x != table.d for x in w.shape[3:]):
             raise InvalidArgument(HX_ERR_INVALID, "a GF matrix is [nb, D, D, d] or [nb, D, D, d, d]")
@@ -938,8 +952,8 @@ class BgvGfMatrix:
         if blk.shape != (table.nslots,) or col.shape != (table.nslots,):
             raise InvalidArgument(HX_ERR_INVALID, "blk and col name one transform and one column per slot")
         self.h = C.c_void_p()
-        _chk(lib().hx_bgv_gf_matrix_create(table.context.h, table.h, 1 if self.block else 0, self.nb, self.D, _p(w), _p(blk),
-                                           _p(col), C.byref(self.h)))
+        create = lib().hx_bgv_gr_matrix_create if ring else lib().hx_bgv_gf_matrix_create
+        _chk(create(table.context.h, table.h, 1 if self.block else 0, self.nb, self.D, _p(w), _p(blk), _p(col), C.byref(self.h)))
 
     def coeffs(self):
         """the words the gather reads: uint32 [nb, D, D, d, d] (row k = C[k] of the entry) or the entries [nb, D, D, d]"""
@@ -974,6 +988,27 @@ def bgvGfGather(matrix, descs, maps):
     nz = np.zeros(max(n, 1), dtype=np.int32)
     _chk(lib().hx_bgv_gf_gather(matrix.h, _p(ds), n, _p(mp), mp.shape[0], _p(out), _p(nz)))
     return out, nz[:n] != 0
+
+
+def bgvGfEncodeGathered(table, matrix, descs, maps, idx, mul=1, coeffs=False, flags_only=False):
+    """bgvGfGather and bgvGfEncode in one call, the constants staying on the device (hx_bgv_gf_encode_gathered): ->
+    (DoubleCRT of batch n over `idx`, [coefficients int64 [n, phi(m)],] bool non-zero flags [n]); flags_only=True ->
+    the flags alone, no polynomial is made."""
+    ds = np.ascontiguousarray(descs, dtype=np.int32).reshape(-1, 3)
+    mp = np.ascontiguousarray(maps, dtype=np.int32)
+    if mp.ndim != 3 or mp.shape[1:] != (table.nslots, 2):
+        raise InvalidArgument(HX_ERR_INVALID, "maps is [nmaps, nslots, 2]")
+    n = ds.shape[0]
+    nz = np.zeros(max(n, 1), dtype=np.int32)
+    ctx = table.context
+    if flags_only:
+        _chk(lib().hx_bgv_gf_encode_gathered(table.h, matrix.h, _p(ds), n, _p(mp), mp.shape[0], int(mul) % table.p, None, None, _p(nz)))
+        return nz[:n] != 0
+    out = DoubleCRT(ctx, list(idx), max(n, 1), zero=False)
+    cf = np.zeros((n, ctx.phim), dtype=np.int64) if coeffs else None
+    _chk(lib().hx_bgv_gf_encode_gathered(table.h, matrix.h, _p(ds), n, _p(mp), mp.shape[0], int(mul) % table.p, out.h,
+                                         _p(cf) if coeffs else None, _p(nz)))
+    return (out, cf, nz[:n] != 0) if coeffs else (out, nz[:n] != 0)
 
 
 class BgvMatrix:

@@ -12,7 +12,9 @@
 // multiply-adds of ONE accumulator (a slot contributes d of them to an encode accumulator).  c = alpha A is formed by a
 // kernel of its own ahead of the encode: formed while staging it would be redone for each of the N / 256 coefficient
 // tiles.  The fold is a launch of its own: the top words of W belong to the last coefficient tile, another workgroup.
-// Around them the pieces every BGV slot path shares (bgv_encode.h).
+// Around them the pieces every BGV slot path shares (bgv_encode.h).  Everything of an encode behind "c is on the device"
+// is hxg::gf_encode_words (bgv_gf_tail.h): hx_bgv_gf_encode fills c with the upload and bgv_gf_map_kernel,
+// hx_bgv_gf_encode_gathered (bgv_gf_linalg.hip) with bgv_gf_gather_map_kernel.
 // At r > 1 (hx_bgv_gf_create_pr: slots in the Galois ring Z_(p^r)[X] / G, G the Hensel lift of F_0) the modulus of all of
 // these is p^r < 2^31 (in the kernels' `p`; the table keeps the prime beside it) and the kernels are the same code: as
 // in bgv_crt.hip none of them needs a prime -- bgv_red's quotient estimate is short by at most 1 for any q >= 2, Shoup's
@@ -25,6 +27,7 @@
 
 #include "bgv_gf.h"
 #include "bgv_encode.h"
+#include "bgv_gf_tail.h"
 
 namespace hx {
 
@@ -471,17 +474,20 @@ extern "C" int hx_bgv_gf_info(const hx_bgv_gf* t, uint64_t* p, int* d, int* nslo
   return HX_OK;
 }
 
-extern "C" int hx_bgv_gf_encode(const hx_bgv_gf* tc, const int64_t* slots, int batch, uint64_t mul, hx_poly* out, int64_t* coeffs_out)
+int hxg::gf_view(const hx_bgv_gf* t, GfView* v)
 {
-  if (!tc || !out || !slots)
+  if (!t || !v)
     return err(HX_ERR_INVALID, "null argument");
-  hx_bgv_gf* t = const_cast<hx_bgv_gf*>(tc);   // (its scratch buffers grow; the caller's lock covers them)
-  if (batch < 1)
-    return err(HX_ERR_INVALID, "bad batch %d", batch);
+  *v = GfView{t->ctx, t->p, t->d, t->nslots, t->limit, t->d_A};
+  return HX_OK;
+}
+
+int hxg::gf_encode_words(hx_bgv_gf* t, const char* what, int batch, uint64_t mul, hx_poly* out, int64_t* coeffs_out, const GfFill& fill)
+{
   Encode e{t, out, batch};
   RC(e.check());
   uint64_t* h;
-  RC(e.open("hx_bgv_gf_encode", coeffs_out != nullptr, &h));
+  RC(e.open(what, coeffs_out != nullptr, &h));
   const hipStream_t st = e.st;
   const uint64_t p = t->p, mu = mu_of(p);
   const uint32_t d = t->d, Nw = t->N + d - 1;
@@ -493,10 +499,7 @@ extern "C" int hx_bgv_gf_encode(const hx_bgv_gf* tc, const int64_t* slots, int b
     RC(ensure_xbuf(t, st, 1, (size_t)batch * Nw * 8));
     W = (uint64_t*)t->xbuf[1];
   }
-  CK(hipMemcpyAsync(t->buf[0], slots, total * 8, hipMemcpyHostToDevice, st));
-  HX_LAUNCH(hx::bgv_gf_map_kernel<uint32_t>, dim3(blocks_for(total)), dim3(256), 0, st, (const int64_t*)t->buf[0], t->d_A, t->nslots, d,
-            total, p, mu, t->limit, (uint32_t*)t->xbuf[0]);
-  CK(hipGetLastError());
+  RC(fill(st, (uint32_t*)t->xbuf[0]));
   HX_LAUNCH(hx::bgv_gf_encode_kernel, dim3(tiles_for((Nw + hx::GF_EK - 1) / hx::GF_EK, batch_tiles(batch))), dim3(256), 0, st,
             (const uint32_t*)t->xbuf[0], t->d_E, t->nslots, d, Nw, t->ld, batch, p, mu, t->limit, W);
   CK(hipGetLastError());
@@ -507,6 +510,23 @@ extern "C" int hx_bgv_gf_encode(const hx_bgv_gf* tc, const int64_t* slots, int b
     CK(hipGetLastError());
   }
   return e.finish(mul % p, coeffs_out);
+}
+
+extern "C" int hx_bgv_gf_encode(const hx_bgv_gf* tc, const int64_t* slots, int batch, uint64_t mul, hx_poly* out, int64_t* coeffs_out)
+{
+  if (!tc || !out || !slots)
+    return err(HX_ERR_INVALID, "null argument");
+  hx_bgv_gf* t = const_cast<hx_bgv_gf*>(tc);   // (its scratch buffers grow; the caller's lock covers them)
+  if (batch < 1)
+    return err(HX_ERR_INVALID, "bad batch %d", batch);
+  const size_t total = (size_t)batch * t->nslots * t->d;
+  return hxg::gf_encode_words(t, "hx_bgv_gf_encode", batch, mul, out, coeffs_out, [&](hipStream_t st, uint32_t* c) -> int {
+    CK(hipMemcpyAsync(t->buf[0], slots, total * 8, hipMemcpyHostToDevice, st));
+    HX_LAUNCH(hx::bgv_gf_map_kernel<uint32_t>, dim3(blocks_for(total)), dim3(256), 0, st, (const int64_t*)t->buf[0], t->d_A, t->nslots,
+              t->d, total, t->p, mu_of(t->p), t->limit, c);
+    CK(hipGetLastError());
+    return HX_OK;
+  });
 }
 
 extern "C" int hx_bgv_gf_embed(const hx_bgv_gf* tc, const int64_t* coeffs, int batch, int64_t* slots_out)

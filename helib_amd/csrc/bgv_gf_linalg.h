@@ -11,6 +11,13 @@
 //   T (d^2 x d^2)      T[(j,b)][(k,c)] = [X^c](X^b K[j][k] mod G).  The linearized polynomial of the Z_p-linear map with
 //                      L[j] = image of X^j = sum_b E[j][b] X^b has C[k] = sum_j L[j] K[j][k], i.e. C = E T as flat vectors of
 //                      d^2 words: the product the device forms for every entry of a block matrix.
+//
+// Modulo P = p^r (build_gr_linalg): slots in the Galois ring Z_P[X] / G, G the Hensel lift of F_0.  sigma: X -> X^p is a
+// ring automorphism (it fixes the lifted F_0) that fixes Z_P, so frob[e][l] = X^(l p^e) mod G mod P still gives
+// sigma^e(alpha) = sum_l alpha_l frob[e][l]; M stays a Moore matrix of sigma and K its inverse over the ring, through the
+// same Gram matrix Tr(X^(i+j)), Tr = sum_e sigma^e, which is invertible modulo P because it is modulo p: gf_invert takes
+// pivots that are units.  Every line is the r = 1 line with P where it says p, and X^p keeps the prime in the exponent;
+// the tables reduced mod p are the r = 1 tables.
 #pragma once
 #include "bgv_gf.h"
 
@@ -18,7 +25,8 @@ namespace hxc {
 
 struct GfLinTables {
   uint32_t d = 0;
-  uint64_t p = 0;
+  uint64_t p = 0;               // the modulus of the words: the prime, or p^r
+  uint64_t limit = 0;           // lazy_limit(p): multiply-adds a 64-bit accumulator takes between reductions
   std::vector<uint32_t> frob;   // [d][d][d]
   std::vector<uint32_t> K;      // [d][d][d]: K[j][k], d words each
   std::vector<uint32_t> T;      // [d^2][d^2]
@@ -33,14 +41,18 @@ inline void gf_mulx(uint32_t* a, const uint32_t* G, uint32_t d, uint64_t p)
   a[0] = (uint32_t)((p - c) * G[0] % p);
 }
 
-// "", or the reason the tables cannot be built.  G: d + 1 words below p, monic, irreducible over Z_p.
-inline std::string build_gf_linalg(const uint32_t* G, uint32_t d, uint64_t p, GfLinTables& t)
+// "", or the reason the tables cannot be built.  G: d + 1 words below p = prime^r, monic, irreducible modulo the prime
+// (prime = 0: p itself is the prime).
+inline std::string build_gf_linalg(const uint32_t* G, uint32_t d, uint64_t p, GfLinTables& t, uint64_t prime = 0)
 {
   t = GfLinTables();
+  if (!prime)
+    prime = p;
   if (d < 1 || d > GF_MAX_D || p < 2 || p >= CRT_MAX_P || G[d] != 1)
     return "linear maps on GF(p^d) slots take a monic G of degree d <= 64 and p < 2^31";
   t.d = d;
   t.p = p;
+  t.limit = lazy_limit(p);
   const size_t dd = (size_t)d * d;
   t.frob.assign(dd * d, 0);
   t.K.assign(dd * d, 0);
@@ -52,7 +64,7 @@ inline std::string build_gf_linalg(const uint32_t* G, uint32_t d, uint64_t p, Gf
   std::vector<uint32_t> x(d, 0), xp(d, 0), tmp(d);
   x[1] = 1;
   xp[0] = 1;
-  for (uint64_t e = p; e; e >>= 1) {   // xp = X^p mod G
+  for (uint64_t e = prime; e; e >>= 1) {   // xp = X^p mod G (the prime in the exponent, whatever r)
     if (e & 1) {
       gf_mulmod(xp.data(), x.data(), G, d, p, tmp.data());
       xp = tmp;
@@ -94,7 +106,7 @@ inline std::string build_gf_linalg(const uint32_t* G, uint32_t d, uint64_t p, Gf
       gram[(size_t)i * d + j] = s % p;
     }
   std::vector<uint32_t> beta(dd);   // row j: beta_j, Tr(beta_j X^i) = [i == j]
-  if (!gf_invert(gram, d, p, beta.data()))
+  if (!gf_invert(gram, d, p, beta.data(), prime))
     return "internal: the trace form of Z_p[X] / G is degenerate (G is not separable)";
   for (uint32_t j = 0; j < d; j++) {
     uint32_t* row = t.K.data() + (size_t)j * dd;
@@ -112,6 +124,17 @@ inline std::string build_gf_linalg(const uint32_t* G, uint32_t d, uint64_t p, Gf
       }
     }
   return "";
+}
+
+// The same tables modulo P = p^r over the Hensel-lifted G (d + 1 words below P): "", or the reason.  r = 1 is
+// build_gf_linalg, byte for byte.
+inline std::string build_gr_linalg(const uint32_t* G, uint32_t d, uint64_t p, uint32_t r, GfLinTables& t)
+{
+  t = GfLinTables();
+  const uint64_t P = crt_modulus(p, r);
+  if (!P)
+    return "linear maps on Galois-ring slots take p^r < 2^31 with r >= 1";
+  return build_gf_linalg(G, d, P, t, p);
 }
 
 }  // namespace hxc

@@ -451,7 +451,7 @@ int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out);
  * say p; hx_bgv_gf_info gives the prime and the lifted G; a slot (a, 0, ..., 0) is the integer a of
  * hx_bgv_crt_create_pr, word for word.  r = 1 is hx_bgv_gf_create, byte for byte.  r < 1: HX_ERR_INVALID; p^r >= 2^31:
  * HX_ERR_UNSUPPORTED with the figure; otherwise the errors of hx_bgv_gf_create.  hx_bgv_gf_matrix_create refuses a
- * table with r > 1. */
+ * table with r > 1; hx_bgv_gr_matrix_create takes it. */
 int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** out);
 /* The exponent r and the modulus p^r of the table's maps (hx_bgv_gf_info gives p); either output may be NULL. */
 int hx_bgv_gf_space(const hx_bgv_gf* t, int* r, uint64_t* modulus);
@@ -504,6 +504,34 @@ typedef struct hx_bgv_gf_desc {
  * power of the Frobenius to each.  Anything out of range: HX_ERR_INVALID before the device is touched. */
 int hx_bgv_gf_gather(const hx_bgv_gf_matrix* a, const hx_bgv_gf_desc* descs, int ndesc, const int32_t* maps, int nmaps,
                      int64_t* slots_out, int* nonzero_out);
+
+/* ---------------- linear maps on Galois-ring slots modulo p^r (bgv_gf_linalg.hip) ----------------
+ * Over Z_(p^r)[X] / G, G the Hensel lift of F_0, a Z_(p^r)-linear map of a slot is sum_k C[k] sigma^k(alpha) with
+ * sigma: X -> X^p (EncryptedArrayDerived::buildLinPolyCoeffs with its ppsolve branch, src/EncryptedArray.cpp:740-798).
+ * hx_bgv_gf_linalg_tables modulo P = p^r: frob[e][l] = X^(l p^e) mod G mod P, K = the inverse over the ring of the Moore
+ * matrix M[i][j] = sigma^i(X^j) (buildLinPolyMatrix + ppInvert, src/NumbTh.cpp:1099-1111, src/EncryptedArray.cpp:783-787;
+ * here through the Gram matrix of traces, inverted with pivots that are units) and the flat table T.  G: d + 1 words,
+ * monic, the lifted F_0.  r = 1 gives hx_bgv_gf_linalg_tables byte for byte, and the tables reduced mod p are the r = 1
+ * tables.  r < 1: HX_ERR_INVALID; d > 64 or p^r >= 2^31: HX_ERR_UNSUPPORTED. */
+int hx_bgv_gr_linalg_tables(uint64_t p, int r, int d, const uint64_t* G, uint32_t* frob_out, uint32_t* K_out, uint32_t* T_out);
+/* hx_bgv_gf_matrix_create over a table of any r >= 1 (hx_bgv_gf_create or hx_bgv_gf_create_pr): the same contract with
+ * the modulus p^r where that one says p -- words below p^r, the coefficients of every block formed modulo p^r on the
+ * device (replaces buildLinPolyCoeffs per entry in BlockMatMul1D_derived_impl::processDiagonal1/2 over p^r,
+ * src/matmul.cpp:1369-1373, 1452-1457).  hx_bgv_gf_matrix_destroy, hx_bgv_gf_matrix_coeffs and hx_bgv_gf_gather work on
+ * the handle unchanged.  hx_bgv_gf_matrix_create keeps refusing r > 1. */
+int hx_bgv_gr_matrix_create(hx_ctx* ctx, const hx_bgv_gf* t, int block, int nb, int D, const uint32_t* words, const int32_t* blk,
+                            const int32_t* col, hx_bgv_gf_matrix** out);
+/* hx_bgv_gf_gather and hx_bgv_gf_encode in one call, the constants never leaving the device: for every descriptor the
+ * CRT components the encode reads -- gather, sigma^e and the per-slot map in one kernel -- then the encode itself
+ * (replaces build_ConstMultiplier's poly-space plaintextAutomorph / mask products and the encode of every constant of
+ * BlockMatMul1DExec_construct / MatMul1DExec_construct, src/matmul.cpp:375-389, 626-688, 1537-1658).  out (batch ndesc on
+ * its own prime set), mul and coeffs_out as for hx_bgv_gf_encode: the same words as hx_bgv_gf_encode of
+ * hx_bgv_gf_gather's slots, a zero polynomial for a constant that is zero.  nonzero_out[ndesc] as for hx_bgv_gf_gather.
+ * out = NULL (then coeffs_out = NULL too) computes the flags alone and writes no row.  The matrix must have been built
+ * over t's context, modulus and geometry.  Null arguments, anything out of range, another context: HX_ERR_INVALID
+ * before the device is touched; fails with HX_ERR_INVALID under an open graph capture. */
+int hx_bgv_gf_encode_gathered(const hx_bgv_gf* t, const hx_bgv_gf_matrix* a, const hx_bgv_gf_desc* descs, int ndesc,
+                              const int32_t* maps, int nmaps, uint64_t mul, hx_poly* out, int64_t* coeffs_out, int* nonzero_out);
 
 /* ---------------- fused multiply-add of the matrix product (linalg.hip) ---------------- */
 /* out0 (+)= sum_t c[t] * in0[t],  out1 (+)= sum_t c[t] * in1[t]   (t < n), row by row modulo each prime.
