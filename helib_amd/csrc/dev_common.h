@@ -65,6 +65,12 @@ struct ModDownPrep {
   uint64_t poly_stride;  // words between the x blocks of consecutive polys (0: batch*N, the
                          // single-prime layout [poly][batch][N]; the several-primes path keeps
                          // [poly][dropped prime][batch][N] and launches once per dropped prime)
+  // the single-prime launchers (launch_moddown_pow2 / launch_moddown_tensor_pow2) only:
+  uint32_t fuse;         // 0: the prep kernel stores x, moddown_S_kernel forms S (HX_NO_PREP_FUSE=1); 1: the prep kernel
+                         // stores x and S; 2 (N = 2^14, ptxt < 2^32): and goes on to the embedding norm of delta/qd = x/qd - S
+  double inv_qd;         // fuse = 2: 1/qd;
+  const double* wtab;    //   the norm kernels' table, W^k = (wtab[2k], wtab[2k+1]) for k < N, W = exp(2 pi i / 2N);
+  unsigned long long* norm_out;   //   squared maximum per prep workgroup ([poly][batch]), stored by the workgroup itself
 };
 // several dropped primes in ONE prep launch (scale_down_multi_fused): workgroup block j of
 // polys.n * batch workgroups inverse-transforms dropped row row[j] (prime prime[j]) of every poly

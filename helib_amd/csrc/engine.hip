@@ -232,6 +232,9 @@ struct hx_ctx {
   int xs_first = 0, xs_rows = 0;
   double xs_inv_qd = 0;
   bool want_fdelta = false;  // the caller also wants the fdelta coefficients on the host
+  // the prep kernels of that block stored the block's squared norms themselves (ModDownPrep::fuse = 2), into the
+  // pinned slot prep_np: embed_norms() queues the slot instead of launching a kernel; flush_xs() gives it back
+  bool prep_norm = false;
   double2* d_wtab = nullptr;           // W^k, k < N, W = exp(2 pi i / m)  (m a power of two)
   // general m (complex-double Bluestein, norm_kernels.h): v_k, exp(2 pi i k/P) (k < P/2), transform
   // of the chirp, and the transform-domain work buffer
@@ -255,6 +258,7 @@ struct hx_ctx {
   std::vector<void*> norm_slabs;
   bool defer_norms = false;
   std::vector<NormPending> norm_pending, norm_free;
+  NormPending prep_np{};   // (prep_norm)
   // The norm kernels run on a stream of their own, next to whatever the context enqueues after them
   // (they have no consumer on the device: only the host reads the result).  One LDS-bound workgroup per
   // CU with almost no VALU work co-resides with the HBM-bound tensor / key-switch kernels.  Ordering:
@@ -617,6 +621,8 @@ static void ctx_free(hx_ctx* c)
   hipFree(c->d_bn_Z);
   hipFree(c->d_norm2);
   hipFree(c->d_norm_park);
+  if (c->prep_norm)   // (a slot the prep kernels wrote and nobody asked for)
+    c->norm_free.push_back(c->prep_np);
   for (auto* v : {&c->norm_pending, &c->norm_free})
     for (auto& np : *v) {
       hipEventDestroy(np.ev);
@@ -2988,6 +2994,14 @@ static void clear_args(ExtArgs& a)
 // size of the complex Bluestein transform of the general-m norms: the integer transform's 2^bk
 static int bn_logp(const hx_ctx* c) { return next_pow2_exp(2 * c->m - 1); }
 
+// a norm slot the prep kernels filled for an (x, S) block that will not be read in place after all: back to the free
+// list (its next user's kernel is ordered behind the prep kernels on the context's stream)
+static void prep_norm_drop(hx_ctx* c)
+{
+  if (c->prep_norm)
+    c->norm_free.push_back(c->prep_np);
+  c->prep_norm = false;
+}
 static int frac_begin(hx_ctx* c, size_t doubles)
 {
   if (!c->pow2 && bn_logp(c) > 18)
@@ -3006,6 +3020,7 @@ static int frac_begin(hx_ctx* c, size_t doubles)
   c->frac_pos = 0;
   c->want_frac = true;
   c->xs_rows = 0;
+  prep_norm_drop(c);
   return HX_OK;
 }
 static double* frac_take(hx_ctx* c, size_t doubles)
@@ -3023,6 +3038,7 @@ static int flush_xs(hx_ctx* c)
 {
   if (c->xs_rows <= 0)
     return HX_OK;
+  prep_norm_drop(c);
   const size_t n = (size_t)c->xs_rows * c->phim;
   HX_LAUNCH(hx::frac_from_xs_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)),
                      dim3(256), 0, c->stream, c->scratch[0],
@@ -3124,49 +3140,26 @@ static int embed_norms_general(hx_ctx* c, const double* d_f, int rows, hipStream
   return HX_OK;
 }
 
-static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
+// the norm kernels' table W^k, k < N (power-of-two rings), made on first use
+static int norm_wtab(hx_ctx* c)
 {
+  if (!c->pow2 || c->d_wtab)
+    return HX_OK;
   const uint32_t N = c->phim;
-  const int logn = c->logn;
-  if (c->pow2 && !c->d_wtab) {
-    std::vector<double> h(2 * (size_t)N);
-    const long double two_pi = 6.283185307179586476925286766559005768394L;
-    for (uint32_t k = 0; k < N; k++) {
-      long double ang = two_pi * (long double)k / (long double)c->m;
-      h[2 * (size_t)k] = (double)cosl(ang);
-      h[2 * (size_t)k + 1] = (double)sinl(ang);
-    }
-    HIPCHK(hipMalloc((void**)&c->d_wtab, sizeof(double) * 2 * (size_t)N));
-    HIPCHK(hipMemcpy(c->d_wtab, h.data(), sizeof(double) * 2 * (size_t)N, hipMemcpyHostToDevice));
+  std::vector<double> h(2 * (size_t)N);
+  const long double two_pi = 6.283185307179586476925286766559005768394L;
+  for (uint32_t k = 0; k < N; k++) {
+    long double ang = two_pi * (long double)k / (long double)c->m;
+    h[2 * (size_t)k] = (double)cosl(ang);
+    h[2 * (size_t)k + 1] = (double)sinl(ang);
   }
-  if (c->norm_cap < (size_t)rows) {
-    retire_or_free(c, c->d_norm2);
-    c->d_norm2 = nullptr;
-    c->norm_cap = 0;
-    HIPCHK(hipMalloc((void**)&c->d_norm2, sizeof(unsigned long long) * (size_t)rows));
-    c->norm_cap = (size_t)rows;
-  }
-  // which source the kernel will read: the mod-down's (x, S) in place, or doubles at d_f (then a pending
-  // (x, S) block is written out as doubles first -- on the main stream, before the hand-over below)
-  const bool quarter_form = c->pow2 && logn >= 2 && logn - 1 <= hx::NORM_MAX_LOGH;
-  const bool use_xs = quarter_form && c->xs_rows == rows && d_f == c->d_frac;
-  if (!use_xs)
-    CHK(flush_xs(c));
-  hipStream_t ns = c->stream;
-  // (measured, profiles/r03_norm_side_stream_ab.txt: no gain -- the one-workgroup-per-CU norm kernel does not get
-  // onto the CUs next to a kernel that fills them -- so the side stream is opt-in: HX_NORM_ASYNC=1)
-  const bool side_stream = c->sw.norm_async;
-  if (side_stream && !c->capturing) {
-    if (!c->norm_stream) {
-      HIPCHK(hipStreamCreateWithFlags(&c->norm_stream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->norm_in_ev, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->norm_out_ev, hipEventDisableTiming));
-    }
-    HIPCHK(hipEventRecord(c->norm_in_ev, c->stream));             // behind the producers of the input
-    HIPCHK(hipStreamWaitEvent(c->norm_stream, c->norm_in_ev, 0));
-    ns = c->norm_stream;
-  }
-  // read-back through a pinned slot and an event
+  HIPCHK(hipMalloc((void**)&c->d_wtab, sizeof(double) * 2 * (size_t)N));
+  HIPCHK(hipMemcpy(c->d_wtab, h.data(), sizeof(double) * 2 * (size_t)N, hipMemcpyHostToDevice));
+  return HX_OK;
+}
+// a pinned read-back slot (and its event) for `rows` squared norms, off the free list or new
+static int norm_slot_take(hx_ctx* c, int rows, hx_ctx::NormPending* out)
+{
   hx_ctx::NormPending np{};
   bool have = false;
   for (size_t i = 0; i < c->norm_free.size(); i++)
@@ -3199,6 +3192,52 @@ static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
     HIPCHK(hipHostMalloc((void**)&np.pinned, np.cap * sizeof(unsigned long long), hipHostMallocDefault));
     HIPCHK(hipEventCreateWithFlags(&np.ev, hipEventDisableTiming));
   }
+  *out = np;
+  return HX_OK;
+}
+
+static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
+{
+  const uint32_t N = c->phim;
+  const int logn = c->logn;
+  CHK(norm_wtab(c));
+  if (c->norm_cap < (size_t)rows) {
+    retire_or_free(c, c->d_norm2);
+    c->d_norm2 = nullptr;
+    c->norm_cap = 0;
+    HIPCHK(hipMalloc((void**)&c->d_norm2, sizeof(unsigned long long) * (size_t)rows));
+    c->norm_cap = (size_t)rows;
+  }
+  // which source the kernel will read: the mod-down's (x, S) in place, or doubles at d_f (then a pending
+  // (x, S) block is written out as doubles first -- on the main stream, before the hand-over below)
+  const bool quarter_form = c->pow2 && logn >= 2 && logn - 1 <= hx::NORM_MAX_LOGH;
+  const bool use_xs = quarter_form && c->xs_rows == rows && d_f == c->d_frac;
+  if (!use_xs)
+    CHK(flush_xs(c));
+  hipStream_t ns = c->stream;
+  // (measured, profiles/r03_norm_side_stream_ab.txt: no gain -- the one-workgroup-per-CU norm kernel does not get
+  // onto the CUs next to a kernel that fills them -- so the side stream is opt-in: HX_NORM_ASYNC=1)
+  const bool side_stream = c->sw.norm_async;
+  if (side_stream && !c->capturing) {
+    if (!c->norm_stream) {
+      HIPCHK(hipStreamCreateWithFlags(&c->norm_stream, hipStreamNonBlocking));
+      HIPCHK(hipEventCreateWithFlags(&c->norm_in_ev, hipEventDisableTiming));
+      HIPCHK(hipEventCreateWithFlags(&c->norm_out_ev, hipEventDisableTiming));
+    }
+    HIPCHK(hipEventRecord(c->norm_in_ev, c->stream));             // behind the producers of the input
+    HIPCHK(hipStreamWaitEvent(c->norm_stream, c->norm_in_ev, 0));
+    ns = c->norm_stream;
+  }
+  // read-back through a pinned slot and an event; the slot of an (x, S) block whose prep kernels carried the norm
+  // is already taken and written (scale_down_impl), and no kernel is launched for it below
+  hx_ctx::NormPending np{};
+  const bool from_prep = c->prep_norm && use_xs;
+  if (from_prep) {
+    np = c->prep_np;
+    c->prep_norm = false;
+  } else {
+    CHK(norm_slot_take(c, rows, &np));
+  }
   // (the slot goes back to the free list if anything below fails before it is queued)
   struct SlotGuard {
     hx_ctx* c;
@@ -3220,11 +3259,10 @@ static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
   unsigned long long* const out2 = direct ? np.pinned : c->d_norm2;
   if (!direct)
     HIPCHK(hipMemsetAsync(c->d_norm2, 0, sizeof(unsigned long long) * (size_t)rows, ns));
-  bool attr = false;   // (hxp::dyn_lds is idempotent per device)
   if (!c->pow2) {
     CHK(flush_xs(c));
     CHK(embed_norms_general(c, d_f, rows, ns));
-  } else if (!attr) {
+  } else {   // (hxp::dyn_lds is idempotent per device)
     HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_kernel, 16 << hx::NORM_MAX_LOGH));
 #define HX_NORM_ATTR(...)                                                                               \
   HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_kernel<__VA_ARGS__>,                   \
@@ -3237,10 +3275,11 @@ static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
     HX_NORM_ATTR(hx::NormSrcXS, 14);
 #undef HX_NORM_ATTR
     HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_split_kernel, 16 << hx::NORM_MAX_LOGH));
-    attr = true;
   }
   if (!c->pow2) {
     // (done above)
+  } else if (from_prep) {
+    c->xs_rows = 0;   // (the maxima are in the slot, stored by the prep workgroups)
   } else if (logn >= 2 && logn - 1 <= hx::NORM_MAX_LOGH) {
     // real-input form: one N/2-point transform per polynomial, one workgroup each
     const unsigned M = N >> 1;
@@ -3263,30 +3302,38 @@ static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
     // N = 2^14: the register-tiled kernel (norm_r16.h); HX_NORM_OLD keeps the LDS-pass kernel (A/B)
     const bool r16 = !c->sw.norm_old;
     constexpr size_t r16_lds = (size_t)hx::R16_LDS_DOUBLES * sizeof(double);   // one array: two workgroups per CU
-    if (r16 && logn == 14) {
-      bool attr16 = false;   // (hxp::dyn_lds is idempotent per device)
-      if (!attr16) {
-        HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<hx::NormSrcXS>, (int)r16_lds));
-        HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<hx::NormSrcF64>, (int)r16_lds));
-        attr16 = true;
-      }
+    // the direct form (no pairing pass); HX_NO_PREP_FUSE keeps the paired kernel (A/B)
+    const bool paired = c->sw.no_prep_fuse;
+    if (r16 && logn == 14) {   // (hxp::dyn_lds is idempotent per device)
+      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<hx::NormSrcXS>, (int)r16_lds));
+      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<hx::NormSrcF64>, (int)r16_lds));
+      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_paired_kernel<hx::NormSrcXS>, (int)r16_lds));
+      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_paired_kernel<hx::NormSrcF64>, (int)r16_lds));
     }
+#define HX_R16_LAUNCH(SRCT, srcv)                                                                                       \
+  do {                                                                                                                  \
+    if (paired)                                                                                                         \
+      HX_LAUNCH((hx::embed_norm_r16_paired_kernel<SRCT>), dim3((unsigned)rows), dim3(hx::R16_THREADS), r16_lds, ns, srcv, \
+                c->d_wtab, out2, direct);                                                                               \
+    else                                                                                                                \
+      HX_LAUNCH((hx::embed_norm_r16_kernel<SRCT>), dim3((unsigned)rows), dim3(hx::R16_THREADS), r16_lds, ns, srcv,      \
+                c->d_wtab, out2, direct);                                                                               \
+  } while (0)
     if (c->xs_rows == rows && d_f == c->d_frac) {
       hx::NormSrcXS src{c->scratch[0], reinterpret_cast<const int64_t*>(c->scratch[1]), c->xs_inv_qd};
       if (r16 && logn == 14)
-        HX_LAUNCH((hx::embed_norm_r16_kernel<hx::NormSrcXS>), dim3((unsigned)rows), dim3(hx::R16_THREADS), r16_lds, ns, src,
-                  c->d_wtab, out2, direct);
+        HX_R16_LAUNCH(hx::NormSrcXS, src);
       else
         HX_NORM_LAUNCH(hx::NormSrcXS, src);
     } else {
       CHK(flush_xs(c));
       hx::NormSrcF64 src{d_f};
       if (r16 && logn == 14)
-        HX_LAUNCH((hx::embed_norm_r16_kernel<hx::NormSrcF64>), dim3((unsigned)rows), dim3(hx::R16_THREADS), r16_lds, ns, src,
-                  c->d_wtab, out2, direct);
+        HX_R16_LAUNCH(hx::NormSrcF64, src);
       else
         HX_NORM_LAUNCH(hx::NormSrcF64, src);
     }
+#undef HX_R16_LAUNCH
 #undef HX_NORM_LAUNCH
     c->xs_rows = 0;
   } else if (logn - 1 > hx::NORM_MAX_LOGH && !c->sw.norm_plain) {
@@ -3951,6 +3998,25 @@ static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* 
         return fail(HX_ERR_INVALID, "dropped primes are not invertible modulo ptxtSpace");
     }
     P.qd = qd;
+    // Who forms S, and the norm (dev_common.h: ModDownPrep::fuse).  The norm rides in the prep workgroups when the
+    // whole norm batch comes from this call (the condition under which the norm kernel would read (x, S) in place,
+    // below), the ring is the radix-16 one and the read-back is a plain store into the pinned slot on this stream.
+    P.fuse = c->sw.no_prep_fuse ? 0u : 1u;
+    const size_t nfrac = rw * (size_t)pb.n;
+    const bool xs_in_place = c->want_frac && c->xs_rows == 0 && c->frac_pos == 0 && nfrac <= c->frac_cap && !c->want_fdelta;
+    // (ptxt < 2^32: the norm-carrying kernels keep no scalar registers for the wide correction's constants)
+    const bool norm_in_prep = P.fuse && xs_in_place && c->logn == 14 && !c->sw.norm_old && !c->sw.norm_memcpy &&
+                              !c->sw.norm_async && !c->capturing && (ptxt >> 32) == 0;
+    if (norm_in_prep) {
+      prep_norm_drop(c);   // (a slot an earlier call took and then failed before it had an (x, S) block to go with it)
+      CHK(norm_wtab(c));
+      CHK(norm_slot_take(c, pb.n * a->batch, &c->prep_np));
+      c->prep_norm = true;   // (given back by flush_xs / frac_begin unless embed_norms() queues it)
+      P.fuse = 2;
+      P.inv_qd = 1.0 / (double)qd;
+      P.wtab = reinterpret_cast<const double*>(c->d_wtab);
+      P.norm_out = c->prep_np.pinned;
+    }
     if (nadd > 0) {
       uint64_t F = 1;
       for (int i = 0; i < nadd; i++)
@@ -4021,8 +4087,10 @@ static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* 
                                                          c->d_primes, c->d_tw, c->stream)
                         : hx::launch_moddown_pow2(c->logn, pb, pbo, drow, dprime, kr, nk, a->batch, P, A,
                                                   c->d_primes, c->d_tw, c->stream);
-    if (e != hipSuccess)
+    if (e != hipSuccess) {
+      prep_norm_drop(c);
       return fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
+    }
     fresh_guard.armed = false;
     for (int i = 0; i < pb.n; i++)
       if (fresh[i]) {  // the shared input slab stays with its other holders (or goes back to the
@@ -4036,7 +4104,8 @@ static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* 
       if (!fr)
         return fail(HX_ERR_INVALID, "internal: fraction buffer too small");
       if (c->xs_rows == 0 && c->frac_pos == n && !c->want_fdelta) {
-        // the whole norm batch comes from this call: the norm kernel reads (x, S) itself
+        // the whole norm batch comes from this call: the norm kernel reads (x, S) itself -- or the prep kernels
+        // have already formed the norms (xs_in_place above is this very condition, taken before the launch)
         c->xs_first = 0;
         c->xs_rows = pb.n * a->batch;
         c->xs_inv_qd = 1.0 / (double)qd;

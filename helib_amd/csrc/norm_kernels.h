@@ -24,29 +24,7 @@
 
 namespace hx {
 
-__device__ __forceinline__ void block_max_to(double mx, double* sm, unsigned tid, unsigned nth,
-                                             unsigned long long* dst, bool direct = false)
-{
-  for (int off = 32; off > 0; off >>= 1) {
-    const double o = __shfl_down(mx, off, 64);
-    mx = o > mx ? o : mx;
-  }
-  __syncthreads();
-  if ((tid & 63u) == 0)
-    sm[tid >> 6] = mx;
-  __syncthreads();
-  if (tid == 0) {
-    const unsigned nw = (nth + 63) >> 6;
-    for (unsigned w = 1; w < nw; w++)
-      mx = sm[w] > mx ? sm[w] : mx;
-    // direct: this workgroup is the only writer of *dst (one workgroup per polynomial) -- a plain store, which may go
-    // to device-visible host memory; otherwise several workgroups meet in a zeroed word
-    if (direct)
-      *dst = (unsigned long long)__double_as_longlong(mx);
-    else
-      atomicMax(dst, (unsigned long long)__double_as_longlong(mx));
-  }
-}
+// (block_max_to: norm_r16.h, shared with the mod-switch prep kernels)
 
 // f: rows x N doubles; wtab[k] = W^k for k < N (W^(k+N) = -W^k); out2[row] must be zeroed.
 // General form: the N-point DFT of g_i = f_i W^i, S = N/H sub-transforms per row.
@@ -102,6 +80,7 @@ struct NormSrcF64 {
   {
     return reinterpret_cast<const double2*>(f + (size_t)row * N)[i];
   }
+  __device__ __forceinline__ double elem(unsigned row, unsigned N, unsigned i) const { return f[(size_t)row * N + i]; }
 };
 struct NormSrcXS {
   const uint64_t* xs;
@@ -112,6 +91,10 @@ struct NormSrcXS {
     const ulonglong2 x = reinterpret_cast<const ulonglong2*>(xs + (size_t)row * N)[i];
     const longlong2 s = reinterpret_cast<const longlong2*>(S + (size_t)row * N)[i];
     return make_double2((double)x.x * inv_qd - (double)s.x, (double)x.y * inv_qd - (double)s.y);
+  }
+  __device__ __forceinline__ double elem(unsigned row, unsigned N, unsigned i) const
+  {
+    return (double)xs[(size_t)row * N + i] * inv_qd - (double)S[(size_t)row * N + i];
   }
 };
 
@@ -168,36 +151,29 @@ embed_norm_quarter_kernel(SRC src, const double2* __restrict__ wtab, int logn_rt
 // the other loads, and every row of a launch of <= 512 rows is resident at once.  The price is barriers (the real
 // parts cross the array, then the imaginary parts); the last stage moved from the pairing pass into a lane
 // exchange (DPP quad_perm), and the pairing forms each pair once instead of twice.
-__device__ __forceinline__ double lane_xor1(double v)
-{
-  int lo = __double2loint(v), hi = __double2hiint(v);
-  lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
-  hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
-  return __hiloint2double(hi, lo);
-}
-// FROM -> TO: positions of the 16 values before / after (r16_pos_A / _B / _C)
-template <unsigned (*FROM)(unsigned, unsigned), unsigned (*TO)(unsigned, unsigned)>
-__device__ __forceinline__ void r16_transpose(cplx16 (&v)[16], double* sm, unsigned t)
-{
-#pragma unroll
-  for (unsigned k = 0; k < 16; k++)
-    sm[r16_pad(FROM(t, k))] = v[k].x;
-  __syncthreads();
-#pragma unroll
-  for (unsigned k = 0; k < 16; k++)
-    v[k].x = sm[r16_pad(TO(t, k))];
-  __syncthreads();
-#pragma unroll
-  for (unsigned k = 0; k < 16; k++)
-    sm[r16_pad(FROM(t, k))] = v[k].y;
-  __syncthreads();
-#pragma unroll
-  for (unsigned k = 0; k < 16; k++)
-    v[k].y = sm[r16_pad(TO(t, k))];
-}
+// embed_norm_r16_kernel is the direct form (norm_r16.h: the halves packed instead of the parities, every output an
+// evaluation of f, no pairing pass); embed_norm_r16_paired_kernel the round-4 form kept as the control arm
+// (HX_NO_PREP_FUSE=1).
 template <class SRC>
 __global__ void __launch_bounds__(R16_THREADS)
 embed_norm_r16_kernel(SRC src, const double2* __restrict__ wtab, unsigned long long* __restrict__ out2, bool direct)
+{
+  extern __shared__ __attribute__((aligned(16))) double sm[];
+  const unsigned row = blockIdx.x, t = threadIdx.x;
+  const tw16* wt = reinterpret_cast<const tw16*>(wtab);
+  cplx16 v[16];
+  const tw16 wth = wt[t];
+#pragma unroll
+  for (unsigned k = 0; k < 16; k++) {
+    const unsigned p = r16_pos_A(t, k);
+    v[k] = r16_direct_twist(src.elem(row, R16_N, p), src.elem(row, R16_N, p + R16_M), wth, wt[r16_direct_tw_k(k)], k);
+  }
+  const double mx = r16_direct_max2(v, sm, t, wt);
+  block_max_to(mx, sm, t, R16_THREADS, out2 + row, direct);
+}
+template <class SRC>
+__global__ void __launch_bounds__(R16_THREADS)
+embed_norm_r16_paired_kernel(SRC src, const double2* __restrict__ wtab, unsigned long long* __restrict__ out2, bool direct)
 {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const unsigned row = blockIdx.x, t = threadIdx.x;

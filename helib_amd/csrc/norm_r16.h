@@ -18,6 +18,9 @@
 // on the CPU against the definition.
 #pragma once
 #include <stdint.h>
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#endif
 
 #ifndef HXD
 #if defined(__HIPCC__)
@@ -49,8 +52,9 @@ HXD tw16 r16_cmul(tw16 a, tw16 b) { return tw16{a.x * b.x - a.y * b.y, a.x * b.y
 // rest are its products with the 16th roots of unity exp(pi i k / 8), read from the table at wave-uniform
 // addresses (wtab[k 2^LOGTAB / 8]) -- the first version loaded all 15 twiddles of a pass per thread from the
 // strided table and was latency-bound on them (slower than the LDS-pass kernel it was to replace).
-template <int LOGS, int LOGTAB = 14>
-HXD void r16_pass(cplx16 (&v)[16], unsigned j0, const tw16* wtab)
+// TAB: anything that gives a tw16 by value for an index (a plain pointer; R16ConstTab below on the device).
+template <int LOGS, int LOGTAB = 14, class TAB = const tw16*>
+HXD void r16_pass(cplx16 (&v)[16], unsigned j0, TAB wtab)
 {
   constexpr unsigned S = 1u << LOGS;
   tw16 B = wtab[j0 * ((1u << LOGTAB) / (S * 8u))];
@@ -117,6 +121,25 @@ HXD unsigned r16_brev8(unsigned x)
 HXD unsigned r16_pair_tw_thread(unsigned t) { return 8192u * (t & 1u) + 2u * r16_brev8(t >> 1) + 1u; }
 HXD unsigned r16_pair_tw_k(unsigned k) { return 512u * r16_brev4(k); }
 
+// ---- the direct form: no pairing pass ----
+// Split f by HALVES instead of by parity.  With M = N/2, W^M = i and W^(4jM) = 1:
+//   f(W^(4j+1)) = sum_{p<M} (f_p + i f_(p+M)) W^p exp(2 pi i jp / M),   j < M,
+// the SAME M-point transform (root W^4, passes A/B/C and the lane stage above) of z_p = (f_p + i f_(p+M)) W^p, and
+// every output is an evaluation of f itself -- at W^(4j+1), one from each conjugate pair of the primitive 2N-th
+// roots (W^(4j+3) = conj W^(4(M-1-j)+1)), and |f| is the same at both of a pair because f is real.  The norm is
+// max_j |Z_j|: no partner, no exchange through the array, no pairing twiddles.  Pass A's thread t takes f at
+// t + 512 k and t + 512 (k + 16): of the row transform's inverse (ntt_core.h: coef_const<14>(e) = 512 e) these are
+// the thread's OWN registers e = k and e = k + 16, which is what lets the mod-switch prep kernel go on into the norm
+// without a data exchange (ntt_kernels.hip: PrepFuseIO).
+// Load twist W^(t + 512 k) = wtab[t] * wtab[512 k]: one table entry per thread, 16 wave-uniform constants.
+HXD unsigned r16_direct_tw_k(unsigned k) { return 512u * k; }
+HXD cplx16 r16_direct_twist(double lo, double hi, tw16 wth, tw16 wk, unsigned k)   // lo = f_p, hi = f_(p+M), p = t + 512 k
+{
+  const tw16 w = k == 0 ? wth : r16_cmul(wth, wk);
+  return cplx16{lo * w.x - hi * w.y, lo * w.y + hi * w.x};
+}
+HXD double r16_abs2(cplx16 z) { return z.x * z.x + z.y * z.y; }
+
 // N = 2^15 as S = 2 sub-transforms of H = 8192 points (norm_kernels.h, embed_norm_quarter_split_kernel):
 // input point i of sub-transform `sub`: h_i = sum_{t<2} z_(i+tH) U^((i+tH) sub),
 //   z_n U^(n sub) = (f_2n + i f_(2n+1)) W^(2n (2 sub + 1)),  W = exp(2 pi i / 2N),  wtab[k] = W^k for k < N
@@ -154,5 +177,88 @@ HXD double r16x2_pair(unsigned h, cplx16 own, cplx16 other, tw16 wth, tw16 wk, u
   const tw16 w = k == 0 ? wth : r16_cmul(wth, u);
   return h ? r16_pair_norm2(other, own, w) : r16_pair_norm2(own, other, w);
 }
+
+#if defined(__HIPCC__)
+// ---- device side of the phases above, shared by the norm kernels (norm_kernels.h) and by the mod-switch prep
+// kernels that carry the norm in their own workgroup (ntt_kernels.hip) ----
+__device__ __forceinline__ void block_max_to(double mx, double* sm, unsigned tid, unsigned nth,
+                                             unsigned long long* dst, bool direct = false)
+{
+  for (int off = 32; off > 0; off >>= 1) {
+    const double o = __shfl_down(mx, off, 64);
+    mx = o > mx ? o : mx;
+  }
+  __syncthreads();
+  if ((tid & 63u) == 0)
+    sm[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned nw = (nth + 63) >> 6;
+    for (unsigned w = 1; w < nw; w++)
+      mx = sm[w] > mx ? sm[w] : mx;
+    // direct: this workgroup is the only writer of *dst (one workgroup per polynomial) -- a plain store, which may go
+    // to device-visible host memory; otherwise several workgroups meet in a zeroed word
+    if (direct)
+      *dst = (unsigned long long)__double_as_longlong(mx);
+    else
+      atomicMax(dst, (unsigned long long)__double_as_longlong(mx));
+  }
+}
+__device__ __forceinline__ double lane_xor1(double v)
+{
+  int lo = __double2loint(v), hi = __double2hiint(v);
+  lo = __builtin_amdgcn_mov_dpp(lo, 0xB1, 0xF, 0xF, true);   // quad_perm [1, 0, 3, 2]
+  hi = __builtin_amdgcn_mov_dpp(hi, 0xB1, 0xF, 0xF, true);
+  return __hiloint2double(hi, lo);
+}
+// FROM -> TO: positions of the 16 values before / after (r16_pos_A / _B / _C)
+template <unsigned (*FROM)(unsigned, unsigned), unsigned (*TO)(unsigned, unsigned)>
+__device__ __forceinline__ void r16_transpose(cplx16 (&v)[16], double* sm, unsigned t)
+{
+#pragma unroll
+  for (unsigned k = 0; k < 16; k++)
+    sm[r16_pad(FROM(t, k))] = v[k].x;
+  __syncthreads();
+#pragma unroll
+  for (unsigned k = 0; k < 16; k++)
+    v[k].x = sm[r16_pad(TO(t, k))];
+  __syncthreads();
+#pragma unroll
+  for (unsigned k = 0; k < 16; k++)
+    sm[r16_pad(FROM(t, k))] = v[k].y;
+  __syncthreads();
+#pragma unroll
+  for (unsigned k = 0; k < 16; k++)
+    v[k].y = sm[r16_pad(TO(t, k))];
+}
+// The table behind a constant-address-space pointer.  A kernel that has stored to global memory before it reads the
+// table (the prep kernels: x and S) gets its wave-uniform entries as VECTOR loads through a plain pointer -- the
+// compiler cannot rule the stores out as writers of the table -- four registers per constant, some sixty per pass;
+// from the constant address space they are scalar loads, as in a kernel that stores nothing first.  (The table is
+// written once, when the context makes it.)
+struct R16ConstTab {
+  const double __attribute__((address_space(4)))* p;
+  __device__ explicit R16ConstTab(const double* q) : p((const double __attribute__((address_space(4)))*)(uintptr_t)q) {}
+  __device__ __forceinline__ tw16 operator[](unsigned i) const { return tw16{p[2u * i], p[2u * i + 1u]}; }
+};
+// the direct form from the twisted points (v[k] at r16_pos_A(t, k)) to the thread's largest |Z|^2
+template <class TAB>
+__device__ __forceinline__ double r16_direct_max2(cplx16 (&v)[16], double* sm, unsigned t, TAB wt)
+{
+  r16_pass<9>(v, t, wt);
+  r16_transpose<r16_pos_A, r16_pos_B>(v, sm, t);
+  r16_pass<5>(v, t & 31u, wt);
+  __syncthreads();
+  r16_transpose<r16_pos_B, r16_pos_C>(v, sm, t);
+  r16_pass<1>(v, t & 1u, wt);
+  double mx = 0;
+#pragma unroll
+  for (unsigned k = 0; k < 16; k++) {
+    const double n2 = r16_abs2(r16_last_lane(v[k], cplx16{lane_xor1(v[k].x), lane_xor1(v[k].y)}, t));
+    mx = n2 > mx ? n2 : mx;
+  }
+  return mx;
+}
+#endif
 
 }  // namespace hx

@@ -924,6 +924,15 @@ struct io_skip_load : std::false_type {};
 template <class IO>
 struct io_skip_load<IO, std::void_t<decltype(IO::SKIP_LOAD)>> : std::integral_constant<bool, IO::SKIP_LOAD> {};
 
+// An IO functor may state INV_STORE_ALL = true: the inverse transform's last phase then hands it the whole register
+// file (bound AR::INV_OUT, coefficient tid + coef_const<LOGN>(e) in v[e]) and the workgroup's array instead of
+// storing word by word -- inv_store_all<LOGN, AR>(tid, v, lds, c) normalises, stores, and may go on working on
+// what the registers hold (the mod-switch prep kernels that form S and the embedding norm: ntt_kernels.hip).
+template <class IO, class = void>
+struct io_inv_store_all : std::false_type {};
+template <class IO>
+struct io_inv_store_all<IO, std::void_t<decltype(IO::INV_STORE_ALL)>> : std::integral_constant<bool, IO::INV_STORE_ALL> {};
+
 // The bound (units of q) of what an IO functor's load hands the forward transform: IO::LOAD_BOUND, or -- when the
 // functor's own arithmetic depends on the row's arithmetic (the mod-down apply loads: a Shoup product is below 4q, a
 // Proth-form one below 2q) -- IO::load_bound<AR>().
@@ -1169,10 +1178,14 @@ struct RowNTT {
             HX_SCHED_FENCE();
         });
       }
+      if constexpr (io_inv_store_all<IO>::value) {
+        io.template inv_store_all<LOGN, AR>(tid, v, lds, c);
+      } else {
 #pragma unroll
-      for (int e = 0; e < 32; e++) {
-        io.store(tid, coef_const<LOGN>(e), norm_from<AR::INV_OUT>(v[e], c));
-        HX_IO_FENCE(e);
+        for (int e = 0; e < 32; e++) {
+          io.store(tid, coef_const<LOGN>(e), norm_from<AR::INV_OUT>(v[e], c));
+          HX_IO_FENCE(e);
+        }
       }
     }
   }

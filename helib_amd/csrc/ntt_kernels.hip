@@ -11,6 +11,7 @@
 #include "prof.h"
 
 #include "ntt_kernel_util.h"
+#include "norm_r16.h"
 
 // One translation unit per ring size.  The row kernels are straight-line code of ~7000 instructions each, in
 // 3 ring sizes x 2 arithmetics x a dozen IO functors: compiled as one unit this file takes nine minutes.  Built
@@ -139,8 +140,8 @@ struct BufIOT {
 
 // inverse transform of the dropped row: stores x = F * iNTT(row) in [0,qd)  (F = 1 without the
 // fused mod-up; otherwise F rides on the last stage's N^-1 twiddles, no extra multiplication).
-// The delta preparation S(x) is a separate element-wise kernel (below): inside this store its
-// ~250 instructions per element and dozen uniform 64-bit constants pushed the kernel into scratch.
+// The delta preparation S(x) is formed by PrepFuseIO (below) on top of this store in the single-prime mod-switch;
+// the several-primes path has no S and uses this functor as it is.
 struct InvPrepIO {
   static constexpr int LOAD_BOUND = 1;
   static constexpr bool LAZY_STORE = false;
@@ -178,19 +179,28 @@ struct InvPrepIO {
 
 // delta = x - qd*S:  S = [x > (qd-1)/2]  (centring, src/DoubleCRT.cpp:1098-1099)
 //                      + balanced((delta0 mod p) * qd^-1 mod p)  (ptxtSpace correction, :1485-1508)
+// What a caller knows at compile time about the two questions the plaintext space decides: CORR -- is there a
+// correction at all (ptxt > 1); NARROW -- is ptxt < 2^32 (the one-word product).  RunTime: read from P, which is what
+// moddown_S_kernel does.  A row kernel that forms S element by element settles both once, outside its element loop,
+// and then runs straight-line code; or settles NARROW alone where it has no scalar registers to spare for the wide
+// form's constants.  (r = 0 gives dm = 0 and adds nothing: with the width known the test on r is dropped, not the case.)
+enum class Known { No, Yes, RunTime };
+template <Known CORR = Known::RunTime, Known NARROW = Known::RunTime>
 __device__ __forceinline__ int64_t moddown_S_of(const ModDownPrep& P, uint64_t x)
 {
   const bool neg = x > P.half;
   int64_t S = neg ? 1 : 0;
-  if (P.ptxt > 1) {
+  const bool corr = CORR == Known::RunTime ? P.ptxt > 1 : CORR == Known::Yes;
+  if (corr) {
     const uint64_t p = P.ptxt;
     uint64_t r = red64(x, p, P.ptxt_mu64);
     if (neg)
       r = sub_mod(r, P.qd_mod_p, p);  // delta mod p, non-negative
-    if (r != 0) {
+    if (NARROW != Known::RunTime || r != 0) {
       // (uniform: a plaintext space below 2^32 -- the product fits a word and red64 replaces the 128-bit Barrett)
-      const uint64_t dm = (p >> 32) == 0 ? red64(r * P.qdinv_mod_p, p, P.ptxt_mu64)
-                                         : mul_mod(r, P.qdinv_mod_p, p, P.ptxt_mu, P.ptxt_k);
+      const bool narrow = NARROW == Known::RunTime ? (p >> 32) == 0 : NARROW == Known::Yes;
+      const uint64_t dm = narrow ? red64(r * P.qdinv_mod_p, p, P.ptxt_mu64)
+                                 : mul_mod(r, P.qdinv_mod_p, p, P.ptxt_mu, P.ptxt_k);
       const uint64_t p2 = p >> 1;
       const bool sub_p = dm > p2 || (((p & 1) == 0) && dm == p2 && neg);
       S += sub_p ? (int64_t)dm - (int64_t)p : (int64_t)dm;
@@ -210,11 +220,91 @@ moddown_S_kernel(ModDownPrep P, size_t n2)
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n2; i += (size_t)gridDim.x * blockDim.x) {
     const ulonglong2 x = xs[i];
     longlong2 s;
-    s.x = moddown_S_of(P, x.x);
-    s.y = moddown_S_of(P, x.y);
+    s.x = moddown_S_of<>(P, x.x);
+    s.y = moddown_S_of<>(P, x.y);
     S[i] = s;
   }
 }
+
+// The single-prime mod-switch's prep store with S formed on the canonical word it is about to store (FUSE >= 1: no
+// moddown_S_kernel launch, x is not read back), on top of the store of BASE (InvPrepIO, or InvPrepTensorIO below).
+// The store is the last thing the inverse transform does: its twiddles and staging words are dead, the 32
+// coefficients are the only vector state, and S takes the plaintext-space constants from P once, outside the
+// element loop (moddown_S_of<CORR, NARROW>) -- inside a per-element branch the same arithmetic put the kernel into scratch.
+// FUSE == 2 (N = 2^14, the whole norm batch comes from this launch): the workgroup goes on to the canonical-embedding
+// norm of delta/qd = x/qd - S in the direct form of norm_r16.h -- thread tid holds the coefficients tid + 512 e, and
+// pass A of that form wants f at tid + 512 k and tid + 512 (k + 16): its own registers e = k and e = k + 16.  No
+// load phase, no (x, S) read back; the transform's array (Geo<14>::LDS_WORDS words = R16_LDS_DOUBLES doubles)
+// becomes the norm's.  P.norm_out[workgroup] takes the squared maximum as a plain store (block_max_to, direct).
+template <class BASE, int FUSE>
+struct PrepFuseIO : BASE {
+  static constexpr bool INV_STORE_ALL = true;
+  const ModDownPrep& P;
+  v4i32 rS;
+  template <class... A>
+  __device__ PrepFuseIO(const ModDownPrep& p, size_t soff, unsigned bytes, A&&... base)
+      : BASE(base...), P(p), rS(make_rsrc(reinterpret_cast<const uint64_t*>(p.S) + soff, bytes))
+  {
+  }
+  template <int LOGN, class AR, Known CORR, Known NARROW>
+  __device__ __forceinline__ void store_xs(unsigned tid, uint64_t (&v)[32], const QC& c) const
+  {
+#pragma unroll
+    for (int e = 0; e < 32; e++) {
+      const uint64_t x = norm_from<AR::INV_OUT>(v[e], c);
+      BASE::store(tid, coef_const<LOGN>(e), x);
+      const int64_t S = moddown_S_of<CORR, NARROW>(P, x);
+      v2i32 sw;
+      sw.x = (int)(uint32_t)(uint64_t)S;
+      sw.y = (int)(uint32_t)((uint64_t)S >> 32);
+      hx_buffer_store_v2(sw, rS, (int)(tid * 8u), (int)(coef_const<LOGN>(e) * 8u), 0);
+      if constexpr (FUSE == 2) {
+        // (NormSrcXS::elem.  Pinned here: the value is used only behind the barrier, and the compiler otherwise sinks
+        // the conversion there, keeping x AND S of all 32 elements live across this loop -- 128 registers, in scratch)
+        double d = (double)x * P.inv_qd - (double)S;
+        asm volatile("" : "+v"(d));
+        v[e] = (uint64_t)__double_as_longlong(d);
+        HX_SCHED_FENCE();   // (and one element's temporaries at a time: all 32 values stay live here)
+      } else {
+        HX_IO_FENCE(e);
+      }
+    }
+  }
+  template <int LOGN, class AR>
+  __device__ __forceinline__ void inv_store_all(unsigned tid, uint64_t (&v)[32], uint32_t* lds, const QC& c) const
+  {
+    if constexpr (FUSE == 2)   // (one loop, fenced element by element: the engine takes FUSE = 2 for ptxt < 2^32 only)
+      store_xs<LOGN, AR, Known::RunTime, Known::Yes>(tid, v, c);
+    else if (P.ptxt <= 1)
+      store_xs<LOGN, AR, Known::No, Known::Yes>(tid, v, c);
+    else if ((P.ptxt >> 32) == 0)
+      store_xs<LOGN, AR, Known::Yes, Known::Yes>(tid, v, c);
+    else
+      store_xs<LOGN, AR, Known::Yes, Known::No>(tid, v, c);
+    if constexpr (FUSE == 2) {
+      static_assert(LOGN == (int)R16_LOGN && Geo<LOGN>::T == (int)R16_THREADS &&
+                        (size_t)Geo<LOGN>::LDS_WORDS * 4 == (size_t)R16_LDS_DOUBLES * 8,
+                    "the norm tail takes over the row transform's workgroup and array as they are");
+      __syncthreads();   // every thread is past the transform's last read of the array
+      // (a work-item id of the tail's own, as every phase of the transform has: what is derived from it -- table and
+      // array addresses -- then starts here and not in front of the last register pass, where the file is full)
+      const unsigned t = fresh_tid((unsigned)__builtin_amdgcn_readfirstlane((int)(tid >> 6)));
+      double* sm = reinterpret_cast<double*>(lds);
+      const R16ConstTab wt(P.wtab);
+      const tw16 wth = wt[t];
+      cplx16 z[16];
+#pragma unroll
+      for (unsigned k = 0; k < 16; k++) {
+        z[k] = r16_direct_twist(__longlong_as_double((long long)v[k]), __longlong_as_double((long long)v[k + 16]), wth,
+                                wt[r16_direct_tw_k(k)], k);
+        if (k % 4 == 3)
+          HX_SCHED_FENCE();   // (four of the sixteen uniform constants in scalar registers at a time)
+      }
+      const double mx = r16_direct_max2(z, sm, t, wt);
+      block_max_to(mx, sm, t, R16_THREADS, P.norm_out + blockIdx.x, true);
+    }
+  }
+};
 
 // forward transform of a kept row.  With inv = qd^-1 mod q_r and delta = x - qd*S:
 //   load  = delta * inv = x*inv - S  (mod q_r)      (qd*inv = 1: S needs no multiplication,
@@ -443,7 +533,9 @@ __device__ __forceinline__ void ntt_body(uint32_t* lds, const IO& io, const TW* 
 }
 
 // scaleDownToSet, one dropped prime: inverse transform of its row with the delta preparation
-template <int LOGN>
+// FUSE: 0 = x only (the several-primes path one prime at a time, and the control arm, where moddown_S_kernel follows);
+// 1 = x and S; 2 = x, S and the embedding norm of delta/qd (PrepFuseIO; workgroup i writes P.norm_out[i])
+template <int LOGN, int FUSE = 0>
 __global__ void __launch_bounds__(Geo<LOGN>::T, HX_NTT_MINWAVES(LOGN))
 ntt_moddown_prep_kernel(PolyBases polys, int row, int prime, int batch, ModDownPrep P,
                         const PrimeDev* __restrict__ primes, const TW* __restrict__ tw_arena)
@@ -454,9 +546,15 @@ ntt_moddown_prep_kernel(PolyBases polys, int row, int prime, int batch, ModDownP
   const size_t N = Geo<LOGN>::N;
   const uint64_t* in = poly_base(polys, (unsigned)pi);
   const size_t pstride = P.poly_stride ? (size_t)P.poly_stride : (size_t)batch * N;
-  const InvPrepIO io(in + ((size_t)row * batch + b) * N, P, (size_t)pi * pstride + (size_t)b * N,
-                     (unsigned)N * 8u);
-  ntt_body<LOGN, true>(lds, io, tw_arena + pd->tw_inv_off, pd);
+  const size_t boff = (size_t)pi * pstride + (size_t)b * N;
+  if constexpr (FUSE == 0) {
+    const InvPrepIO io(in + ((size_t)row * batch + b) * N, P, boff, (unsigned)N * 8u);
+    ntt_body<LOGN, true>(lds, io, tw_arena + pd->tw_inv_off, pd);
+  } else {
+    const PrepFuseIO<InvPrepIO, FUSE> io(P, boff, (unsigned)N * 8u, in + ((size_t)row * batch + b) * N, P, boff,
+                                         (unsigned)N * 8u);
+    ntt_body<LOGN, true>(lds, io, tw_arena + pd->tw_inv_off, pd);
+  }
 }
 // the same for up to MD_MAXDROP dropped primes at once (the several-primes mod-switch): one launch of
 // ndrop * polys * batch workgroups instead of ndrop launches of polys * batch -- a single such launch
@@ -586,7 +684,7 @@ struct InvPrepTensorIO {
   __device__ __forceinline__ TW last_tw(TW def, int which) const { return has_up ? (which ? upN : upS) : def; }
   __device__ __forceinline__ TWM last_tw(TWM def, int which) const { return has_up ? (which ? upN.wp : upS.wp) : def; }
 };
-template <int LOGN>
+template <int LOGN, int FUSE = 0>   // (FUSE: as ntt_moddown_prep_kernel)
 __global__ void __launch_bounds__(Geo<LOGN>::T, HX_NTT_MINWAVES(LOGN))
 ntt_moddown_prep_tensor_kernel(TensorSrc T, int row, int prime, int batch, ModDownPrep P,
                                const PrimeDev* __restrict__ primes, const TW* __restrict__ tw_arena)
@@ -595,9 +693,15 @@ ntt_moddown_prep_tensor_kernel(TensorSrc T, int row, int prime, int batch, ModDo
   const int b = (int)(blockIdx.x % (unsigned)batch), pi = (int)(blockIdx.x / (unsigned)batch);   // pi = product part
   const PrimeDev* pd = primes + prime;
   const size_t N = Geo<LOGN>::N;
-  const InvPrepTensorIO io(T, (unsigned)pi, ((size_t)row * batch + b) * N, P, ((size_t)pi * batch + b) * N,
-                           (unsigned)N * 8u, pd);
-  ntt_body<LOGN, true>(lds, io, tw_arena + pd->tw_inv_off, pd);
+  const size_t roff = ((size_t)row * batch + b) * N, xoff = ((size_t)pi * batch + b) * N;
+  if constexpr (FUSE == 0) {
+    const InvPrepTensorIO io(T, (unsigned)pi, roff, P, xoff, (unsigned)N * 8u, pd);
+    ntt_body<LOGN, true>(lds, io, tw_arena + pd->tw_inv_off, pd);
+  } else {
+    const PrepFuseIO<InvPrepTensorIO, FUSE> io(P, xoff, (unsigned)N * 8u, T, (unsigned)pi, roff, P, xoff, (unsigned)N * 8u,
+                                               pd);
+    ntt_body<LOGN, true>(lds, io, tw_arena + pd->tw_inv_off, pd);
+  }
 }
 
 // the same for up to MD_MAXDROP dropped primes at once (ntt_moddown_prep_multi_kernel with the product parts as input)
@@ -1266,6 +1370,11 @@ static hipError_t moddown_attrs()
   constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
   hipError_t e = hxp::dyn_lds((const void*)ntt_moddown_prep_kernel<LOGN>, (int)lds_bytes);
   if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_prep_kernel<LOGN, 1>, (int)lds_bytes);
+  if constexpr (LOGN == 14)
+    if (e == hipSuccess)
+      e = hxp::dyn_lds((const void*)ntt_moddown_prep_kernel<LOGN, 2>, (int)lds_bytes);
+  if (e == hipSuccess)
     e = hxp::dyn_lds((const void*)ntt_moddown_prep_multi_kernel<LOGN>, (int)lds_bytes);
   if (e == hipSuccess)
     e = hxp::dyn_lds((const void*)ntt_moddown_apply_kernel<LOGN, false>, (int)lds_bytes);
@@ -1292,10 +1401,20 @@ static hipError_t launch_moddown(const PolyBases& polys, const PolyBases& outs, 
   hipError_t e = moddown_attrs<LOGN>();
   if (e != hipSuccess)
     return e;
-  HX_LAUNCH((ntt_moddown_prep_kernel<LOGN>), dim3((unsigned)polys.n * (unsigned)batch),
-                     dim3(Geo<LOGN>::T), lds_bytes, st, polys, drop_row, drop_prime, batch, P, primes,
-                     tw_arena);
-  {
+  // P.fuse: who forms S (and the norm) -- dev_common.h
+  const dim3 pgrid((unsigned)polys.n * (unsigned)batch), pblock(Geo<LOGN>::T);
+  if (P.fuse == 2) {
+    if constexpr (LOGN == 14)
+      HX_LAUNCH((ntt_moddown_prep_kernel<LOGN, 2>), pgrid, pblock, lds_bytes, st, polys, drop_row, drop_prime, batch, P,
+                primes, tw_arena);
+    else
+      return hipErrorInvalidValue;
+  } else if (P.fuse == 1) {
+    HX_LAUNCH((ntt_moddown_prep_kernel<LOGN, 1>), pgrid, pblock, lds_bytes, st, polys, drop_row, drop_prime, batch, P,
+              primes, tw_arena);
+  } else {
+    HX_LAUNCH((ntt_moddown_prep_kernel<LOGN>), pgrid, pblock, lds_bytes, st, polys, drop_row, drop_prime, batch, P, primes,
+              tw_arena);
     const size_t n = (size_t)polys.n * (size_t)batch * Geo<LOGN>::N;
     HX_LAUNCH((moddown_S_kernel<0>), dim3((unsigned)((n / 2 + 255) / 256 > 8192 ? 8192 : (n / 2 + 255) / 256)),
                        dim3(256), 0, st, P, n / 2);
@@ -1327,6 +1446,11 @@ static hipError_t moddown_tensor_attrs()
   constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
   hipError_t e = hxp::dyn_lds((const void*)ntt_moddown_prep_tensor_kernel<LOGN>, (int)lds_bytes);
   if (e == hipSuccess)
+    e = hxp::dyn_lds((const void*)ntt_moddown_prep_tensor_kernel<LOGN, 1>, (int)lds_bytes);
+  if constexpr (LOGN == 14)
+    if (e == hipSuccess)
+      e = hxp::dyn_lds((const void*)ntt_moddown_prep_tensor_kernel<LOGN, 2>, (int)lds_bytes);
+  if (e == hipSuccess)
     e = hxp::dyn_lds((const void*)ntt_moddown_prep_multi_tensor_kernel<LOGN>, (int)lds_bytes);
   if (e == hipSuccess)
     e = hxp::dyn_lds((const void*)ntt_moddown_apply_tensor_kernel<LOGN, false>, (int)lds_bytes);
@@ -1343,9 +1467,19 @@ static hipError_t launch_moddown_tensor(const TensorSrc& T, const PolyBases& out
   hipError_t ea = moddown_tensor_attrs<LOGN>();
   if (ea != hipSuccess)
     return ea;
-  HX_LAUNCH((ntt_moddown_prep_tensor_kernel<LOGN>), dim3(3u * (unsigned)batch), dim3(Geo<LOGN>::T), lds_bytes, st, T,
-            drop_row, drop_prime, batch, P, primes, tw_arena);
-  {
+  const dim3 pgrid(3u * (unsigned)batch), pblock(Geo<LOGN>::T);
+  if (P.fuse == 2) {
+    if constexpr (LOGN == 14)
+      HX_LAUNCH((ntt_moddown_prep_tensor_kernel<LOGN, 2>), pgrid, pblock, lds_bytes, st, T, drop_row, drop_prime, batch, P,
+                primes, tw_arena);
+    else
+      return hipErrorInvalidValue;
+  } else if (P.fuse == 1) {
+    HX_LAUNCH((ntt_moddown_prep_tensor_kernel<LOGN, 1>), pgrid, pblock, lds_bytes, st, T, drop_row, drop_prime, batch, P,
+              primes, tw_arena);
+  } else {
+    HX_LAUNCH((ntt_moddown_prep_tensor_kernel<LOGN>), pgrid, pblock, lds_bytes, st, T, drop_row, drop_prime, batch, P, primes,
+              tw_arena);
     const size_t n = (size_t)3 * (size_t)batch * Geo<LOGN>::N;
     HX_LAUNCH((moddown_S_kernel<0>), dim3((unsigned)((n / 2 + 255) / 256 > 8192 ? 8192 : (n / 2 + 255) / 256)), dim3(256), 0, st, P,
               n / 2);

@@ -37,6 +37,10 @@ struct Switches {
   bool no_ks_last_fuse = false;  // HX_NO_KS_LAST_FUSE=1 relinearisation: every extension row through ntt_row_kernel<., false, 8> and the
                                  //                      key switch as keyswitch_kernel<D>, instead of each output row's last digit transform
                                  //                      fused into the key switch (ntt_keyswitch_last_kernel)
+  bool no_prep_fuse = false;     // HX_NO_PREP_FUSE=1    single-prime mod-switch as before: S by moddown_S_kernel behind the prep kernels, the
+                                 //                      (x, S) norm by its own kernel, the radix-16 norm in its paired form -- instead of S
+                                 //                      (and at N = 2^14 the norm) formed in the prep kernels' workgroups and the pairing-free
+                                 //                      norm
   // row transforms (ntt_core.h)
   bool half15 = false;           // HX_HALF15=1          N = 2^15 forward rows (out of place) as two 2^14-point workgroups per row: measured 3-4 % SLOWER
                                  //                      than the one-workgroup kernel (profiles/r06_ab_half_row_forward_2p15.json); kept as a probe
@@ -84,6 +88,7 @@ inline Switches read()
   s.no_tensor_multi = on("HX_NO_TENSOR_MULTI");
   s.no_mulrelin_fuse = on("HX_NO_MULRELIN_FUSE");
   s.no_ks_last_fuse = on("HX_NO_KS_LAST_FUSE");
+  s.no_prep_fuse = on("HX_NO_PREP_FUSE");
   s.no_proth = on("HX_NO_PROTH");
   s.blue_old = on("HX_BLUE_OLD");
   s.no_pfa = on("HX_NO_PFA") || s.blue_old;

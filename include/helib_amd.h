@@ -210,6 +210,9 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
  *   HX_NO_KS_LAST_FUSE                        relinearisation: every extension row transformed by the row kernel and the key
  *                                            switch as a launch of its own, instead of each output row's last digit transform
  *                                            fused into the key switch
+ *   HX_NO_PREP_FUSE                           single-prime mod-switch: S by a kernel of its own behind the prep kernel, the
+ *                                            norm of its (x, S) block by a norm kernel, N = 2^14 norms in the paired form --
+ *                                            instead of S (and that norm) formed in the prep kernel's workgroup
  *   HX_NO_PROTH                               row transforms: Shoup butterflies on every row (by default rows of primes
  *                                            q = 1 mod 2^32 -- every chain prime of the benchmarks -- run the Proth-form ones)
  *   HX_NO_PROTH_RNS                           exact-RNS kernels: Barrett / Shoup products on Proth-form primes too (by default
