@@ -36,11 +36,12 @@ MAX_MODULUS = 1 << 31       # hxc::CRT_MAX_P: the tables hold 32-bit words
 
 class GrEncoder:
     """Galois-ring slot vectors <-> polynomials on the device (hx_bgv_gf_* on a table of hx_bgv_gf_create_pr):
-    bgv_gf.GfEncoder's members, and G (the lifted F_0, d + 1 integers in [0, p^r))"""
+    bgv_gf.GfEncoder's members, and G (the lifted F_0, d + 1 integers in [0, p^r)).  gens / ords: the hypercube of the
+    slots follows these generators (capi.BgvGf), as ContextBuilder.gens().ords() chooses it in the reference"""
 
-    def __init__(self, hxctx, p, r):
+    def __init__(self, hxctx, p, r, gens=None, ords=None):
         self.g = hxctx
-        self.table = capi.BgvGf(hxctx, p, r)
+        self.table = capi.BgvGf(hxctx, p, r, gens=gens, ords=ords)
         self.G = list(self.table.G)
 
     def dims(self):
@@ -73,9 +74,11 @@ class EncryptedArray(bgv_pr.EncryptedArray):
     """context: a BGV helib_amd.ctxt.ChainContext with gcd(p, m) = 1 and any r >= 1 with p^r < 2^31; hxctx: the
     capi.Context holding its primes; G: None for the lifted F_0, or its coefficients (constant first, any
     representatives mod p^r).  An injected encoder has GrEncoder's members (encode takes [B, nslots, d] or, for constants,
-    [B, nslots]) and G.  self.p is the prime, self.P = p^r the modulus of the slots."""
+    [B, nslots]) and G.  self.p is the prime, self.P = p^r the modulus of the slots.  gens / ords: the generators of the
+    slot hypercube and their orders (helib_amd.evalmap needs a hypercube that follows a factorisation of m); they go to
+    the encoder this class builds, so they exclude an injected one."""
 
-    def __init__(self, context, hxctx, G=None, encoder=None):
+    def __init__(self, context, hxctx, G=None, encoder=None, gens=None, ords=None):
         p, r = context.p, int(getattr(context, "r", 1))
         if not getattr(context, "ckks", False):
             if r >= 1 and p ** r >= MAX_MODULUS:
@@ -85,7 +88,10 @@ class EncryptedArray(bgv_pr.EncryptedArray):
                 x, d = x * p % context.m, d + 1
             if d > MAX_D:
                 raise LogicError("EncryptedArray: d = ord_m(p) = %d: Galois-ring slots are built for d <= %d" % (d, MAX_D))
-        super().__init__(context, hxctx, encoder=encoder if encoder is not None else GrEncoder(hxctx, p, r))
+        if (gens is not None or ords is not None) and encoder is not None:
+            raise LogicError("EncryptedArray: gens / ords choose the hypercube of the encoder this class builds; an injected "
+                             "encoder brings its own through dims()")
+        super().__init__(context, hxctx, encoder=encoder if encoder is not None else GrEncoder(hxctx, p, r, gens, ords))
         P, d = self.P, self.zMStar.ordP
         self.G = [int(x) % P for x in self.enc.G]
         if len(self.G) != d + 1 or self.G[d] != 1:

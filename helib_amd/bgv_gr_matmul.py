@@ -28,7 +28,8 @@ Constants reach the encode by one of three paths, all with identical words and s
                 an encoder without encodeGathered, or where the device path cannot run, raises LogicError
 
 Refused with a message: MatMulFull and BlockMatMulFull* with ring entries, multipleTransforms for the ring-entry MatMul1D,
-an array that is not bgv_gr.EncryptedArray, EvalMap.  Nothing here imports oracle/."""
+an array that is not bgv_gr.EncryptedArray.  EvalMap over these execs is helib_amd.evalmap.EvalMap (the name here keeps
+raising, as it did before that module existed).  Nothing here imports oracle/."""
 import numpy as np
 
 from . import bgv_gf_matmul as GM

@@ -69,6 +69,8 @@ SYMBOLS = [
     "hx_bgv_gf_create_pr", "hx_bgv_gf_space",
     "hx_bgv_gf_linalg_tables", "hx_bgv_gf_matrix_create", "hx_bgv_gf_matrix_destroy", "hx_bgv_gf_matrix_coeffs", "hx_bgv_gf_gather",
     "hx_bgv_gr_linalg_tables", "hx_bgv_gr_matrix_create", "hx_bgv_gf_encode_gathered",
+    "hx_bgv_gf_create_gens",
+    "hx_powerful_create", "hx_powerful_destroy", "hx_poly_to_powerful", "hx_powerful_to_poly", "hx_powerful_words",
 ]
 
 
@@ -192,6 +194,10 @@ def lib():
             "hx_bgv_gr_linalg_tables": [u64, ip, ip, vp, vp, vp, vp],
             "hx_bgv_gr_matrix_create": [vp, vp, ip, ip, ip, vp, vp, vp, vp],
             "hx_bgv_gf_encode_gathered": [vp, vp, vp, ip, vp, ip, u64, vp, vp, vp],
+            "hx_bgv_gf_create_gens": [vp, u64, ip, vp, vp, ip, vp],
+            "hx_powerful_create": [vp, vp, ip, vp], "hx_powerful_destroy": [vp],
+            "hx_poly_to_powerful": [vp, vp], "hx_powerful_to_poly": [vp, vp],
+            "hx_powerful_words": [vp, ip, u64, vp, ip, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -837,12 +843,25 @@ class BgvGf:
     """The tables of one (Context, p, r) triple for slots in GF(p^d) = Z_p[X] / G, G = F_0 (hx_bgv_gf): EncryptedArray(context,
     G); with r > 1 slots in the Galois ring Z_(p^r)[X] / G, G the Hensel lift of F_0 (hx_bgv_gf_create_pr).  d, nslots,
     gens, ords (signed), table_bytes, G (d + 1 integers, the constant coefficient first); prime, r; p is the modulus p^r
-    the maps work in."""
+    the maps work in.  gens / ords: the hypercube follows these generators (hx_bgv_gf_create_gens: the order is
+    |ords[i]|, the sign recomputed); None is the library's own choice."""
 
-    def __init__(self, context, p, r=1):
+    def __init__(self, context, p, r=1, gens=None, ords=None):
         self.context, self.prime, self.r = context, int(p), int(r)
         self.h = C.c_void_p()
-        if self.r == 1:
+        if (gens is None) != (ords is None):
+            raise InvalidArgument(HX_ERR_INVALID, "gens and ords come together")
+        if gens is not None and len(gens) > 0:
+            if len(gens) != len(ords):
+                raise InvalidArgument(HX_ERR_INVALID, "%d generators with %d orders" % (len(gens), len(ords)))
+            g = np.array([int(x) for x in gens], dtype=np.uint64)
+            o = np.array([int(x) for x in ords], dtype=np.int64)
+            _chk(lib().hx_bgv_gf_create_gens(context.h, self.prime, self.r, _p(g), _p(o), len(g), C.byref(self.h)))
+            rr, mod = C.c_int(), C.c_uint64()
+            _chk(lib().hx_bgv_gf_space(self.h, C.byref(rr), C.byref(mod)))
+            assert rr.value == self.r and mod.value == self.prime ** self.r
+            self.p = int(mod.value)
+        elif self.r == 1:
             _chk(lib().hx_bgv_gf_create(context.h, self.prime, C.byref(self.h)))
             self.p = self.prime
         else:
@@ -1267,3 +1286,49 @@ def mulRelin(c0, c1, d0, d1, W, digits, norms=False, defer=False):
     _chk(lib().hx_mul_relin_norms(c0.h, c1.h, d0.h, d1.h, W.h, _p(dig_idx), _p(dig_off), len(digits), out0.h, out1.h,
                                   _p(nrm)))
     return out0, out1, nrm
+
+
+class Powerful:
+    """The powerful-basis tables of one (Context, mvec) pair (hx_powerful): m = prod mvec with pairwise coprime factors;
+    Z_q[X] / Phi_m <-> the cube phi(m_1) x ... x phi(m_k), the last coordinate fastest (src/powerful.cpp:152-244)."""
+
+    def __init__(self, context, mvec):
+        self.context, self.mvec = context, [int(x) for x in mvec]
+        self.h = C.c_void_p()
+        mv = np.array(self.mvec, dtype=np.uint64)
+        _chk(lib().hx_powerful_create(context.h, _p(mv), len(mv), C.byref(self.h)))
+
+    def close(self):
+        if self.h:
+            lib().hx_powerful_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def polyToPowerful(table, poly):
+    """every coefficient row of the DoubleCRT (after iFFT) -> its powerful cube modulo the row's prime, in place
+    (hx_poly_to_powerful)"""
+    _chk(lib().hx_poly_to_powerful(table.h, poly.h))
+    return poly
+
+
+def powerfulToPoly(table, poly):
+    """the inverse of polyToPowerful, in place (hx_powerful_to_poly)"""
+    _chk(lib().hx_powerful_to_poly(table.h, poly.h))
+    return poly
+
+
+def powerfulWords(table, words, q, to_powerful):
+    """PowerfulConversion::polyToPowerful / powerfulToPoly of int64 words [B, phi(m)] modulo 2 <= q < 2^62 -> int64
+    [B, phi(m)] in [0, q) (hx_powerful_words)"""
+    w = np.ascontiguousarray(np.atleast_2d(np.asarray(words, dtype=np.int64)))
+    if w.ndim != 2 or w.shape[1] != table.context.phim:
+        raise InvalidArgument(HX_ERR_INVALID, "the words are not [B, phi(m)]")
+    out = np.zeros_like(w)
+    _chk(lib().hx_powerful_words(table.h, 1 if to_powerful else 0, int(q), _p(w), w.shape[0], _p(out)))
+    return out

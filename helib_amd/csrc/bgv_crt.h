@@ -342,9 +342,16 @@ inline uint64_t crt_modulus(uint64_t p, uint32_t r)
 
 // 0, or the reason the tables cannot be built.  tables = false: the geometry alone (m, p, d, nslots, gens, ords).
 // r: the tables are modulo p^r (the top of this file).
-inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables = true, uint32_t r = 1)
+// sup_gens / sup_ords (both or neither): the hypercube follows these generators instead of find_generators', as
+// PAlgebra's constructor takes them from ContextBuilder.gens().ords() (src/PAlgebra.cpp:476-507): a supplied sign is
+// not trusted -- the order is |ords[i]| and nativeness is recomputed -- and what the caller got wrong is reported with
+// a message that starts with "generators:".
+constexpr size_t CRT_MAX_GENS = 8;   // what hx_bgv_crt_info / hx_bgv_gf_info write
+inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables = true, uint32_t r = 1,
+                             const std::vector<uint64_t>* sup_gens = nullptr, const std::vector<int64_t>* sup_ords = nullptr)
 {
   char msg[200];
+  const bool supplied = sup_gens && sup_ords && !sup_gens->empty();
   if (p < 2 || !hxh::is_prime(p))
     return "the plaintext modulus is not a prime";
   if (r < 1)
@@ -378,12 +385,67 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
   t.phim = phim;
   t.nslots = phim / d;
   t.ld = (phim + 3) / 4 * 4;
-  find_generators(m, p, t.gens, t.ords);
-  uint64_t cube = 1;
-  for (int64_t o : t.ords)
-    cube *= (uint64_t)(o < 0 ? -o : o);
-  if (cube != t.nslots)
-    return "internal: the hypercube of Z_m^* / <p> does not have phi(m) / d points";
+  if (supplied) {
+    const size_t ng = sup_gens->size();
+    if (ng != sup_ords->size() || ng > CRT_MAX_GENS) {
+      snprintf(msg, sizeof msg, "generators: %zu generators with %zu orders; at most %zu of each are taken", ng, sup_ords->size(),
+               CRT_MAX_GENS);
+      return msg;
+    }
+    uint64_t cube = 1;
+    for (size_t i = 0; i < ng; i++) {
+      const uint64_t g = (*sup_gens)[i] % m;
+      const int64_t so = (*sup_ords)[i];
+      const uint64_t o = (uint64_t)(so < 0 ? -so : so);
+      if (hxh::gcd(g, m) != 1) {
+        snprintf(msg, sizeof msg, "generators: generator %zu = %llu is not coprime to m = %llu", i, (unsigned long long)(*sup_gens)[i],
+                 (unsigned long long)m);
+        return msg;
+      }
+      if (o < 1 || o > phim || cube * o > phim) {
+        snprintf(msg, sizeof msg, "generators: order %zu = %lld does not fit a hypercube of phi(m) / d = %u points", i, (long long)so,
+                 t.nslots);
+        return msg;
+      }
+      cube *= o;
+      t.gens.push_back(g);
+      t.ords.push_back(hxh::powmod(g, o, m) == 1 ? (int64_t)o : -(int64_t)o);
+    }
+    if (cube != t.nslots) {
+      snprintf(msg, sizeof msg, "generators: the orders multiply to %llu, Z_m^* / <p> has phi(m) / d = %u elements",
+               (unsigned long long)cube, t.nslots);
+      return msg;
+    }
+    // the exponent vectors enumerate Z_m^* / <p> exactly once: every representative lands in a coset of its own
+    std::vector<uint8_t> seen(m, 0);
+    std::vector<uint64_t> ex(ng, 0);
+    for (uint32_t i = 0; i < t.nslots; i++) {
+      uint64_t ti = 1 % m;
+      for (size_t g = 0; g < ng; g++)
+        ti = ti * hxh::powmod(t.gens[g], ex[g], m) % m;
+      if (seen[ti]) {
+        snprintf(msg, sizeof msg, "generators: the representatives do not enumerate Z_m^* / <p> once: point %u = %llu falls in "
+                 "the coset of an earlier one (m = %llu, p = %llu)", i, (unsigned long long)ti, (unsigned long long)m,
+                 (unsigned long long)p);
+        return msg;
+      }
+      uint64_t x = ti;
+      for (uint32_t k = 0; k < d; k++, x = x * (p % m) % m)
+        seen[x] = 1;
+      for (size_t g = ng; g-- > 0;) {
+        if (++ex[g] < (uint64_t)(t.ords[g] < 0 ? -t.ords[g] : t.ords[g]))
+          break;
+        ex[g] = 0;
+      }
+    }
+  } else {
+    find_generators(m, p, t.gens, t.ords);
+    uint64_t cube = 1;
+    for (int64_t o : t.ords)
+      cube *= (uint64_t)(o < 0 ? -o : o);
+    if (cube != t.nslots)
+      return "internal: the hypercube of Z_m^* / <p> does not have phi(m) / d points";
+  }
   if (!tables)
     return "";
   const uint64_t bytes = (uint64_t)t.nslots * t.ld * 4;
@@ -497,7 +559,8 @@ inline std::string build_crt(uint64_t m, uint64_t p, CrtTables& t, bool tables =
     const uint64_t u = c0 * hxh::invmod(ti, m) % m;   // zeta^u is a root of F_i
     const uint32_t cs = coset[u];
     if (cs == 0xffffffffu || seen[cs])
-      return "internal: the representatives of Z_m^* / <p> do not reach every factor once";
+      return supplied ? "generators: the representatives of Z_m^* / <p> do not reach every factor once"
+                      : "internal: the representatives of Z_m^* / <p> do not reach every factor once";
     seen[cs] = 1;
     const std::vector<uint32_t>& f = fac[cs];
     std::copy(f.begin(), f.end(), t.factors.begin() + (size_t)i * (d + 1));

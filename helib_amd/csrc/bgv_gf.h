@@ -98,12 +98,14 @@ inline bool gf_invert(std::vector<uint64_t> a, uint32_t d, uint64_t p, uint32_t*
   return true;
 }
 
-// "", or the reason the tables cannot be built.  r: the tables are modulo p^r (the top of this file)
-inline std::string build_gf(uint64_t m, uint64_t prime, GfTables& t, uint32_t r = 1)
+// "", or the reason the tables cannot be built.  r: the tables are modulo p^r (the top of this file); sup_gens /
+// sup_ords: build_crt's (the hypercube over supplied generators)
+inline std::string build_gf(uint64_t m, uint64_t prime, GfTables& t, uint32_t r = 1, const std::vector<uint64_t>* sup_gens = nullptr,
+                            const std::vector<int64_t>* sup_ords = nullptr)
 {
   char msg[200];
   t = GfTables();
-  std::string why = build_crt(m, prime, t.crt, false, r);   // the geometry first: d decides
+  std::string why = build_crt(m, prime, t.crt, false, r, sup_gens, sup_ords);   // the geometry first: d decides
   if (!why.empty())
     return why;
   if (t.crt.d > GF_MAX_D) {
@@ -111,7 +113,7 @@ inline std::string build_gf(uint64_t m, uint64_t prime, GfTables& t, uint32_t r 
              (unsigned long long)m, (unsigned long long)prime, GF_MAX_D);
     return msg;
   }
-  why = build_crt(m, prime, t.crt, true, r);
+  why = build_crt(m, prime, t.crt, true, r, sup_gens, sup_ords);
   if (!why.empty())
     return why;
   const CrtTables& c = t.crt;

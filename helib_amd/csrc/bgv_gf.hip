@@ -1,5 +1,5 @@
 // bgv_gf.hip -- C ABI of BGV slot encoding and decoding with slots in GF(p^d) = Z_p[X] / G, G = F_0, d = ord_m(p), r = 1
-// (include/helib_amd.h: hx_bgv_gf_create, hx_bgv_gf_create_pr, hx_bgv_gf_space, hx_bgv_gf_info, hx_bgv_gf_encode,
+// (include/helib_amd.h: hx_bgv_gf_create, hx_bgv_gf_create_pr, hx_bgv_gf_create_gens, hx_bgv_gf_space, hx_bgv_gf_info, hx_bgv_gf_encode,
 // hx_bgv_gf_decode, hx_bgv_gf_embed):
 // EncryptedArray(context, G) over the G = F_0 branches of PAlgebraModDerived (src/PAlgebra.cpp:1064-1067, 1096-1100,
 // 1168-1186, 1243-1278).  The tables are bgv_gf.h's; with B elements, n slots, N = phi(m):
@@ -355,11 +355,14 @@ extern "C" int hx_bgv_gf_destroy(hx_bgv_gf* t)
   return HX_OK;
 }
 
-extern "C" int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** out)
+// hx_bgv_gf_create_pr and hx_bgv_gf_create_gens: ngens = 0 is the hypercube of find_generators
+static int gf_create(hx_ctx* ctx, uint64_t p, int r, const uint64_t* gens, const int64_t* ords, int ngens, hx_bgv_gf** out)
 {
-  if (!ctx || !out)
+  if (!ctx || !out || (ngens > 0 && (!gens || !ords)))
     return err(HX_ERR_INVALID, "null argument");
   *out = nullptr;
+  if (ngens < 0 || ngens > (int)hxc::CRT_MAX_GENS)
+    return err(HX_ERR_INVALID, "%d generators: between 0 and %d are taken", ngens, (int)hxc::CRT_MAX_GENS);
   hxi::CtxView v{};
   RC(hxi::ctx_enter(ctx, &v));
   std::unique_lock<std::recursive_mutex> lk(*v.mu);
@@ -382,9 +385,12 @@ extern "C" int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** o
   if (m < 3 || v.phim % 2 != 0)
     return err(HX_ERR_UNSUPPORTED, "BGV slots need m >= 3 (m = %llu)", (unsigned long long)m);
   hxc::GfTables tab;
-  const std::string why = hxc::build_gf(m, p, tab, (uint32_t)r);
+  const std::vector<uint64_t> sg(gens, gens + (ngens > 0 ? ngens : 0));
+  const std::vector<int64_t> so(ords, ords + (ngens > 0 ? ngens : 0));
+  const std::string why = ngens > 0 ? hxc::build_gf(m, p, tab, (uint32_t)r, &sg, &so) : hxc::build_gf(m, p, tab, (uint32_t)r);
   if (!why.empty())
-    return err(why.rfind("internal", 0) == 0 ? HX_ERR_DEVICE : HX_ERR_UNSUPPORTED, "%s", why.c_str());
+    return err(why.rfind("internal", 0) == 0 ? HX_ERR_DEVICE : why.rfind("generators:", 0) == 0 ? HX_ERR_INVALID : HX_ERR_UNSUPPORTED,
+               "%s", why.c_str());
   const hxc::CrtTables& c = tab.crt;
   if (c.phim != v.phim)
     return err(HX_ERR_DEVICE, "internal: phi(m) = %u, the context says %u", c.phim, v.phim);
@@ -434,7 +440,13 @@ extern "C" int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** o
   return HX_OK;
 }
 
+extern "C" int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** out) { return gf_create(ctx, p, r, nullptr, nullptr, 0, out); }
 extern "C" int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out) { return hx_bgv_gf_create_pr(ctx, p, 1, out); }
+extern "C" int hx_bgv_gf_create_gens(hx_ctx* ctx, uint64_t p, int r, const uint64_t* gens, const int64_t* ords, int ngens,
+                                     hx_bgv_gf** out)
+{
+  return gf_create(ctx, p, r, gens, ords, ngens, out);
+}
 
 extern "C" int hx_bgv_gf_space(const hx_bgv_gf* t, int* r, uint64_t* modulus)
 {

@@ -1,0 +1,198 @@
+"""The powerful basis (src/powerful.cpp of the reference): for m = m_1 ... m_k with pairwise coprime factors,
+
+    Z_q[X] / Phi_m  ~  Z_q[X_1..X_k] / (Phi_m1(X_1), ..., Phi_mk(X_k)),     X^i -> prod_j X_j^(i_j),
+
+i = sum_j i_j (m / m_j) mod m.  An element of the right-hand side is a cube of phi(m_1) x ... x phi(m_k) = phi(m) words,
+the last coordinate fastest.  EvalMap (helib_amd.evalmap) consumes and produces it, and recryption applies it to every
+ciphertext part after its raw mod-switch.
+
+  PowerfulTranslationIndexes(mvec)    m, phim, phivec, divvec, invvec, polyToCubeMap, cubeToPolyMap, shortToLongMap
+                                      (src/powerful.cpp:152-190), and shortToExp = cubeToPolyMap o shortToLongMap
+  PowerfulConversion(mvec, hxctx)     polyToPowerful(F, q) / powerfulToPoly(cube, q) on int64 words [B, phi(m)] modulo any
+                                      2 <= q < 2^62 (:199-244).  With a capi.Context the device does it
+                                      (hx_powerful_words); without one numpy does, and the words are identical
+  PowerfulDCRT(hxctx, mvec)           dcrtToPowerful(dcrt) / powerfulToDCRT(dcrt): the per-prime step of
+                                      PowerfulDCRT::dcrtToPowerful / powerfulToZZX (:354-415) in place on the coefficient
+                                      rows of a capi.DoubleCRT (after iFFT), each row modulo its own prime
+
+Neither direction multiplies: Phi_n = prod_(s | rad n) (x^(n/s) - 1)^mu(s) is a quotient of products of binomials, so a
+remainder modulo Phi_n is a few shifted subtractions and running sums (helib_amd/csrc/powerful.h has the pass list the
+device runs; the numpy form below is the same arithmetic on whole arrays).
+
+Refused with a message: factors that are not pairwise coprime or below 2, a product that is not the context's m, q
+outside [2, 2^62).  Nothing here imports oracle/."""
+from math import gcd
+
+import numpy as np
+
+from . import capi
+from .ckks import LogicError
+
+MAX_Q = 1 << 62
+
+
+def _primes(n):
+    out, q = [], 2
+    while q * q <= n:
+        if n % q == 0:
+            out.append(q)
+            while n % q == 0:
+                n //= q
+        q += 1
+    if n > 1:
+        out.append(n)
+    return out
+
+
+def _phi(n):
+    for q in _primes(n):
+        n = n // q * (q - 1)
+    return n
+
+
+def phiBinomials(n):
+    """(num, den): Phi_n = prod_(e in num) (x^e - 1) / prod_(e in den) (x^e - 1) up to the factor x^n - 1, e = n / s over
+    the squarefree s | n, s > 1, by the sign of mu(s) (hxc::PhiBinomials)"""
+    ps, num, den = _primes(n), [], []
+    for mask in range(1, 1 << len(ps)):
+        s, bits = 1, 0
+        for i, q in enumerate(ps):
+            if mask >> i & 1:
+                s, bits = s * q, bits + 1
+        (den if bits % 2 else num).append(n // s)
+    return num, den
+
+
+class PowerfulTranslationIndexes:
+    def __init__(self, mvec):
+        self.mvec = mvec = [int(x) for x in mvec]
+        if not mvec or any(x < 2 for x in mvec):
+            raise LogicError("PowerfulTranslationIndexes: every factor is at least 2 (mvec = %s)" % (mvec,))
+        for i in range(len(mvec)):
+            for j in range(i):
+                if gcd(mvec[i], mvec[j]) != 1:
+                    raise LogicError("PowerfulTranslationIndexes: the factors %d and %d are not coprime" % (mvec[j], mvec[i]))
+        k = len(mvec)
+        self.m = int(np.prod([int(x) for x in mvec], dtype=object))
+        self.phivec = [_phi(x) for x in mvec]
+        self.phim = int(np.prod(self.phivec, dtype=object))
+        self.divvec = [self.m // x for x in mvec]
+        self.invvec = [pow(d % x, -1, x) for d, x in zip(self.divvec, mvec)]
+        m = self.m
+        i = np.arange(m, dtype=np.int64)
+        j = np.zeros(m, dtype=np.int64)
+        for d in range(k):
+            j = j * mvec[d] + (i % mvec[d]) * self.invvec[d] % mvec[d]
+        self.polyToCubeMap = j
+        self.cubeToPolyMap = np.zeros(m, dtype=np.int64)
+        self.cubeToPolyMap[j] = i
+        coords = np.unravel_index(np.arange(self.phim), self.phivec)
+        self.shortToLongMap = np.ravel_multi_index(coords, mvec).astype(np.int64)
+        self.shortToExp = self.cubeToPolyMap[self.shortToLongMap]
+
+
+def _mulBinomial(w, e, q):
+    if e < w.shape[-1]:
+        w[..., e:] = (w[..., e:] - w[..., :-e]) % q         # (the right-hand side is formed from the old words first)
+
+
+def _divBinomial(w, e, q):
+    L = w.shape[-1]
+    if e >= L:
+        return
+    steps = -(-L // e)
+    if steps * q < 1 << 63:                                 # no running sum can leave int64
+        pad = np.zeros(w.shape[:-1] + (steps * e,), dtype=np.int64)
+        pad[..., :L] = w
+        pad = np.cumsum(pad.reshape(w.shape[:-1] + (steps, e)), axis=-2) % q
+        w[...] = pad.reshape(w.shape[:-1] + (steps * e,))[..., :L]
+        return
+    for s in range(e, L, e):
+        t = min(s + e, L)
+        w[..., s:t] = (w[..., s:t] + w[..., s - e:t - e]) % q
+
+
+def _remPhi(X, n, phi, q):
+    """[..., n] words in [0, q) -> the remainder modulo Phi_n, [..., phi] (hxc::rem_phi on whole arrays)"""
+    num, den = phiBinomials(n)
+    dq = n - 1 - phi
+    w = np.ascontiguousarray(X[..., ::-1][..., :dq + 1])
+    for e in den:
+        _mulBinomial(w, e, q)
+    for e in num:
+        _divBinomial(w, e, q)
+    W = np.zeros(X.shape[:-1] + (phi,), dtype=np.int64)
+    c = min(phi, dq + 1)
+    W[..., :c] = w[..., ::-1][..., :c]
+    for e in num:
+        _mulBinomial(W, e, q)
+    for e in den:
+        _divBinomial(W, e, q)
+    return (X[..., :phi] - W) % q
+
+
+class PowerfulConversion:
+    def __init__(self, mvec, hxctx=None):
+        self.indexes = ix = mvec if isinstance(mvec, PowerfulTranslationIndexes) else PowerfulTranslationIndexes(mvec)
+        self.g = hxctx
+        self.table = None
+        if hxctx is not None:
+            if hxctx.m != ix.m:
+                raise LogicError("PowerfulConversion: the factors multiply to %d, the context's m is %d" % (ix.m, hxctx.m))
+            self.table = capi.Powerful(hxctx, ix.mvec)
+
+    def _words(self, a, q):
+        q = int(q)
+        if not 2 <= q < MAX_Q:
+            raise LogicError("PowerfulConversion: the modulus q = %d is not in [2, 2^62)" % q)
+        a = np.asarray(a)
+        if a.dtype == object:
+            a = np.array([int(x) % q for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
+        a = np.atleast_2d(a.astype(np.int64))
+        if a.ndim != 2 or a.shape[1] != self.indexes.phim:
+            raise LogicError("PowerfulConversion: the words are not [B, phi(m) = %d]" % self.indexes.phim)
+        return a % q, q
+
+    def polyToPowerful(self, F, q):
+        """phi(m) coefficients of F mod (Phi_m, q), lowest first -> the powerful cube, int64 [B, phi(m)] in [0, q)"""
+        a, q = self._words(F, q)
+        if self.table is not None:
+            return capi.powerfulWords(self.table, a, q, True)
+        ix = self.indexes
+        cube = np.zeros((a.shape[0], ix.m), dtype=np.int64)
+        cube[:, ix.polyToCubeMap[:ix.phim]] = a
+        cube = cube.reshape([a.shape[0]] + ix.mvec)
+        for d, (n, ph) in enumerate(zip(ix.mvec, ix.phivec)):   # every hypercolumn of dimension d modulo Phi_(m_d)
+            col = np.ascontiguousarray(np.moveaxis(cube, d + 1, -1))
+            cube = np.moveaxis(_remPhi(col, n, ph, q), -1, d + 1)
+        return np.ascontiguousarray(cube).reshape(a.shape[0], ix.phim)
+
+    def powerfulToPoly(self, cube, q):
+        """the powerful cube -> the phi(m) coefficients, int64 [B, phi(m)] in [0, q)"""
+        a, q = self._words(cube, q)
+        if self.table is not None:
+            return capi.powerfulWords(self.table, a, q, False)
+        ix = self.indexes
+        tmp = np.zeros((a.shape[0], ix.m), dtype=np.int64)
+        tmp[:, ix.shortToExp] = a
+        return np.ascontiguousarray(_remPhi(tmp, ix.m, ix.phim, q))
+
+
+class PowerfulDCRT:
+    def __init__(self, hxctx, mvec):
+        self.indexes = ix = mvec if isinstance(mvec, PowerfulTranslationIndexes) else PowerfulTranslationIndexes(mvec)
+        if hxctx is None:
+            raise LogicError("PowerfulDCRT works on device rows: it takes the capi.Context holding the primes")
+        if hxctx.m != ix.m:
+            raise LogicError("PowerfulDCRT: the factors multiply to %d, the context's m is %d" % (ix.m, hxctx.m))
+        self.g = hxctx
+        self.table = capi.Powerful(hxctx, ix.mvec)
+
+    def dcrtToPowerful(self, dcrt):
+        """coefficient rows (DoubleCRT.iFFT) -> powerful cubes, row by row modulo the row's prime, in place"""
+        return capi.polyToPowerful(self.table, dcrt)
+
+    def powerfulToDCRT(self, dcrt):
+        """powerful cubes -> coefficient rows, in place (DoubleCRT.FFT then gives the evaluation form back)"""
+        return capi.powerfulToPoly(self.table, dcrt)
+

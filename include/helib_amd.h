@@ -456,6 +456,15 @@ int hx_bgv_gf_create(hx_ctx* ctx, uint64_t p, hx_bgv_gf** out);
  * HX_ERR_UNSUPPORTED with the figure; otherwise the errors of hx_bgv_gf_create.  hx_bgv_gf_matrix_create refuses a
  * table with r > 1; hx_bgv_gr_matrix_create takes it. */
 int hx_bgv_gf_create_pr(hx_ctx* ctx, uint64_t p, int r, hx_bgv_gf** out);
+/* hx_bgv_gf_create_pr over a hypercube the caller chooses: slot i belongs to t_i = prod_j gens[j]^(e_j), (e_0, ..)
+ * the i-th exponent vector with the last generator's exponent fastest, 0 <= e_j < |ords[j]| -- what PAlgebra's
+ * constructor does with ContextBuilder.gens().ords() (src/PAlgebra.cpp:476-509).  As there (:497-501) a supplied sign
+ * is not trusted: the order is |ords[i]| and hx_bgv_gf_info reports it negated when gens[i]^|ords[i]| != 1 mod m.
+ * EvalMap needs such a hypercube: dimension i generated by an element that is 1 modulo every factor of m but the i-th
+ * (src/EvalMap.cpp:42-105).  ngens = 0 is hx_bgv_gf_create_pr, byte for byte.  Refused with HX_ERR_INVALID and the
+ * figures, before any device allocation: more than 8 generators, a generator not coprime to m, orders that do not
+ * multiply to phi(m) / d, exponent vectors that do not enumerate Z_m^* / <p> exactly once. */
+int hx_bgv_gf_create_gens(hx_ctx* ctx, uint64_t p, int r, const uint64_t* gens, const int64_t* ords, int ngens, hx_bgv_gf** out);
 /* The exponent r and the modulus p^r of the table's maps (hx_bgv_gf_info gives p); either output may be NULL. */
 int hx_bgv_gf_space(const hx_bgv_gf* t, int* r, uint64_t* modulus);
 int hx_bgv_gf_destroy(hx_bgv_gf* t);
@@ -709,6 +718,32 @@ int hx_ctx_graph_begin(hx_ctx* ctx);
 int hx_ctx_graph_end(hx_ctx* ctx, hx_graph** out);
 int hx_graph_launch(hx_graph* g);
 int hx_graph_destroy(hx_graph* g);
+
+/* ---------------- the powerful basis (powerful.hip) ----------------
+ * For m = m_1 ... m_k with pairwise coprime factors, Z_q[X] / Phi_m is isomorphic to
+ * Z_q[X_1..X_k] / (Phi_m1(X_1), ..., Phi_mk(X_k)) by X^i -> prod_j X_j^(i_j), i = sum_j i_j (m / m_j) mod m.  An
+ * element of the right-hand side is a cube of phi(m_1) x ... x phi(m_k) = phi(m) words, the last coordinate fastest:
+ * PowerfulTranslationIndexes, PowerfulConversion and PowerfulDCRT (src/powerful.cpp:22-190, 199-244, 354-415).  EvalMap
+ * consumes and produces it and recryption applies it to every ciphertext part after its raw mod-switch.  Both
+ * directions take additions and subtractions only (Phi_n is a quotient of products of binomials), so a modulus is any
+ * integer in [2, 2^62).  Calls synchronise the context's stream and fail with HX_ERR_INVALID under an open graph
+ * capture. */
+typedef struct hx_powerful hx_powerful; /* the tables of one (context, mvec) pair */
+/* PowerfulTranslationIndexes(mvec) (src/powerful.cpp:152-190) on the device.  HX_ERR_INVALID with the figures: k not
+ * in [1, 8], a factor below 2, factors that are not pairwise coprime, a product that is not the context's m.  Destroy
+ * the tables before their context. */
+int hx_powerful_create(hx_ctx* ctx, const uint64_t* mvec, int k, hx_powerful** out);
+int hx_powerful_destroy(hx_powerful* t);
+/* The per-prime step of PowerfulDCRT::dcrtToPowerful (src/powerful.cpp:354-383), in place: every coefficient row of a
+ * (as hx_ntt_inverse leaves them: [batch][phi(m)] words below the row's prime) becomes its powerful cube modulo that
+ * prime. */
+int hx_poly_to_powerful(const hx_powerful* t, hx_poly* a);
+/* The inverse (the per-prime step of PowerfulDCRT::powerfulToZZX, :385-415): cube rows back to coefficient rows. */
+int hx_powerful_to_poly(const hx_powerful* t, hx_poly* a);
+/* PowerfulConversion::polyToPowerful (to_powerful != 0) / powerfulToPoly (src/powerful.cpp:199-244) of host words
+ * in[batch][phi(m)] (any int64, reduced into [0, q)) modulo any 2 <= q < 2^62 -> out[batch][phi(m)] in [0, q), by the
+ * same kernel on one row. */
+int hx_powerful_words(const hx_powerful* t, int to_powerful, uint64_t q, const int64_t* in, int batch, int64_t* out);
 
 #ifdef __cplusplus
 }
