@@ -24,7 +24,7 @@ UNITS = [("ntt_kernels.hip", ["-DHX_NTT_ONLY=13", "-DHX_NTT_PART=1"], "ntt_kerne
          ("conv_kernels.hip", [], "conv_kernels.o"), ("pfa_kernels.hip", [], "pfa_kernels.o"), ("rns_mfma_kernels.hip", [], "rns_mfma_kernels.o"),
          ("ckks_slots.hip", [], "ckks_slots.o"), ("bgv_slots.hip", [], "bgv_slots.o"), ("bgv_crt.hip", [], "bgv_crt.o"),
          ("bgv_gf.hip", [], "bgv_gf.o"), ("bgv_gf_linalg.hip", [], "bgv_gf_linalg.o"),
-         ("powerful.hip", [], "powerful.o"),
+         ("powerful.hip", [], "powerful.o"), ("recrypt.hip", [], "recrypt.o"),
          ("linalg.hip", [], "linalg.o"),
          ("engine.hip", [], "engine.o")]
 SOURCES = sorted({u[0] for u in UNITS})
@@ -40,6 +40,7 @@ UNIT_HEADERS = {"pfa_kernels.hip": ["pfa_core.h", "pfa_dev.h"], "rns_mfma_kernel
                 "bgv_gf_linalg.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "bgv_gf.h", "bgv_gf_linalg.h", "bgv_gf_tail.h",
                                       "gather_map.h", "ckks_bridge.h"],
                 "powerful.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "powerful.h", "ckks_bridge.h"],
+                "recrypt.hip": ["bgv_slots.h", "bgv_encode.h", "recrypt_core.h", "ckks_bridge.h"],
                 "linalg.hip": ["ckks_bridge.h"]}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value",
          "-Wno-pass-failed"]

@@ -71,6 +71,7 @@ SYMBOLS = [
     "hx_bgv_gr_linalg_tables", "hx_bgv_gr_matrix_create", "hx_bgv_gf_encode_gathered",
     "hx_bgv_gf_create_gens",
     "hx_powerful_create", "hx_powerful_destroy", "hx_poly_to_powerful", "hx_powerful_to_poly", "hx_powerful_words",
+    "hx_recrypt_prep",
 ]
 
 
@@ -198,6 +199,7 @@ def lib():
             "hx_powerful_create": [vp, vp, ip, vp], "hx_powerful_destroy": [vp],
             "hx_poly_to_powerful": [vp, vp], "hx_powerful_to_poly": [vp, vp],
             "hx_powerful_words": [vp, ip, u64, vp, ip, vp],
+            "hx_recrypt_prep": [vp, vp, u64, u64, u64, u64, u64, ip, vp, vp],
         }
         for name, args in sig.items():
             f = getattr(L, name)
@@ -1332,3 +1334,18 @@ def powerfulWords(table, words, q, to_powerful):
     out = np.zeros_like(w)
     _chk(lib().hx_powerful_words(table.h, 1 if to_powerful else 0, int(q), _p(w), w.shape[0], _p(out)))
     return out
+
+
+def recryptPrep(poly, out_set, q, p, p2r, p2ePrime, tie_seed, part, debug=False):
+    """The pre-processing of reCrypt for one ciphertext part (hx_recrypt_prep): rawModSwitch to q = p^e + 1,
+    newMakeDivisible and the division by p2ePrime = p^e', per coefficient, on the device.  poly: coefficient rows (after
+    iFFT and polyToPowerful); -> a new DoubleCRT on the primes out_set whose row t is w mod t.  debug: also the host
+    arrays x, v, int64 [batch, phi(m)]."""
+    out = DoubleCRT(poly.context, list(out_set), poly.batch, zero=False)
+    x = v = None
+    if debug:
+        x = np.zeros((poly.batch, poly.context.phim), dtype=np.int64)
+        v = np.zeros_like(x)
+    _chk(lib().hx_recrypt_prep(poly.h, out.h, int(q), int(p), int(p2r), int(p2ePrime),
+                               int(tie_seed) & (2 ** 64 - 1), int(part), None if x is None else _p(x), None if v is None else _p(v)))
+    return (out, x, v) if debug else out

@@ -20,6 +20,8 @@ struct CtxView {
   void (**state_free)(void*); // ... and how the context releases it
   void** linalg;              // the same pair for linalg.hip
   void (**linalg_free)(void*);
+  void** recrypt;             // the same pair for recrypt.hip
+  void (**recrypt_free)(void*);
   const void* d_primes;       // the per-prime constants (hx::PrimeDev[], dev_common.h) on the device
   int device;
 };

@@ -283,6 +283,9 @@ struct hx_ctx {
   // the fused multiply-add (linalg.hip): its pointer tables
   void* linalg = nullptr;
   void (*linalg_free)(void*) = nullptr;
+  // recryption's pre-processing (recrypt.hip): the plan's place on the device
+  void* recrypt = nullptr;
+  void (*recrypt_free)(void*) = nullptr;
 };
 
 struct hx_poly {
@@ -592,6 +595,8 @@ static void ctx_free(hx_ctx* c)
     c->ckks_free(c->ckks);
   if (c->linalg_free)   // linalg.hip's pointer tables
     c->linalg_free(c->linalg);
+  if (c->recrypt_free)  // recrypt.hip's plan
+    c->recrypt_free(c->recrypt);
   if (c->d_tw)
     hipFree(c->d_tw);
   for (auto& kv : c->plans) {
@@ -5301,6 +5306,8 @@ int ctx_enter(hx_ctx* c, CtxView* v)
   v->state_free = &c->ckks_free;
   v->linalg = &c->linalg;
   v->linalg_free = &c->linalg_free;
+  v->recrypt = &c->recrypt;
+  v->recrypt_free = &c->recrypt_free;
   v->d_primes = c->d_primes;
   v->device = c->device;
   return HX_OK;

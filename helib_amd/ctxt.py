@@ -240,14 +240,60 @@ def lweEstimateSecurity(n, log2AlphaInv, hwt):
     return max(0.0, slope * n / log2AlphaInv + const)
 
 
+BOOT_DFLT_SK_HWT = 120     # include/helib/Context.h:33-35 (MIN_SK_HWT): the default Hamming weight of a bootstrappable secret key
+
+
+def _compute_fudge(p2ePrime, p2e):
+    """compute_fudge (src/recryption.cpp:155-198): the v coefficients are not quite uniform"""
+    eps = 0.0
+    if p2ePrime > 1:
+        eps = 1.0 / (float(p2ePrime) * float(p2ePrime)) if p2ePrime % 2 == 0 else 1.0 / float(p2e)
+    return 1.0 + eps
+
+
+def setAE(context):
+    """RecryptData::setAE (src/recryption.cpp:200-256) -> (e, ePrime): the pair with the smallest e - e' such that
+    p^e >= 2 (fudge p^e' + 2 p^r + 2) boundForRecryption, p^e + 1 < 2^30."""
+    coeff_bound = context.boundForRecryption()
+    p, r = context.p, context.r
+    frstTerm = 2 * p ** r + 2
+    e_bnd, p2e_bnd = 0, 1
+    while p2e_bnd <= ((1 << 30) - 2) // p:
+        e_bnd += 1
+        p2e_bnd *= p
+    ePrime, e = 0, r + 1
+    while e <= e_bnd and p ** e < frstTerm * coeff_bound * 2:
+        e += 1
+    if e > e_bnd:
+        raise RuntimeError("setAE: cannot find suitable e")
+    ePrimeTry = 1
+    while ePrimeTry <= e_bnd:
+        p2ePrimeTry = p ** ePrimeTry
+        eTry = max(r + 1, ePrimeTry + 1)
+        while eTry <= e_bnd and eTry - ePrimeTry < e - ePrime:
+            p2eTry = p ** eTry
+            if p2eTry >= (p2ePrimeTry * _compute_fudge(p2ePrimeTry, p2eTry) + frstTerm) * coeff_bound * 2:
+                break
+            eTry += 1
+        if eTry <= e_bnd and eTry - ePrimeTry < e - ePrime:
+            e, ePrime = eTry, ePrimeTry
+        ePrimeTry += 1
+    return e, ePrime
+
+
 class ChainContext:
     """ContextBuilder<BGV>().m(m).p(p).r(r).bits(bits).c(c) -> buildModChain; with ckks=True
     ContextBuilder<CKKS>().m(m).precision(r).bits(bits).c(c): p = -1, plaintext space 1, r = the
-    precision in bits (include/helib/Context.h:1040-1130)."""
+    precision in bits (include/helib/Context.h:1040-1130).  bootstrappable=True is .bootstrappable(true)
+    (Context::buildModChain's willBeBootstrappable, src/Context.cpp:1037-1073; ignored for CKKS): skHwt = 0 becomes
+    BOOT_DFLT_SK_HWT, setAE fixes e and ePrime, and the special primes are sized for the plaintext space
+    p^(r + e - e') of the encrypted recryption key."""
 
     def __init__(self, m, p, r=1, bits=300, c=3, stdev=3.2, scale=10.0, skHwt=0, resolution=3,
-                 bitsInSpecialPrimes=0, ckks=False):
+                 bitsInSpecialPrimes=0, ckks=False, bootstrappable=False):
         self.ckks = bool(ckks)
+        self.bootstrappable = bool(bootstrappable) and not self.ckks
+        self.e = self.ePrime = 0
         if self.ckks:
             p = -1
         self.m, self.p, self.r = m, p, r
@@ -259,6 +305,8 @@ class ChainContext:
             raise ValueError("Cannot initialise modulus chain with nBits < 1")
         if skHwt < 0:
             raise ValueError("invalid skHwt parameter")
+        if skHwt == 0 and self.bootstrappable:     # src/Context.cpp:1054-1058
+            self.hwt = BOOT_DFLT_SK_HWT
         self.primes = []
         self.smallPrimes, self.ctxtPrimes, self.specialPrimes = [], [], []
         pSize = self._ctxtPrimeSize(bits)
@@ -357,6 +405,9 @@ class ChainContext:
             h = self.phim / 2.0 if self.hwt == 0 else self.hwt
             log_phim = max(math.log(self.phim), 1.0)
             p2e = self.ptxtSpace
+            if self.bootstrappable:   # bigger p^e for bootstrapping (src/Context.cpp:884-894)
+                self.e, self.ePrime = setAE(self)
+                p2e *= self.p ** (self.e - self.ePrime)
             if self.ckks:   # a smaller noise estimate, to protect precision (src/Context.cpp:957-965)
                 nBits = (maxDigitLog + math.log(self.stdev) + math.log(nDgts) - 0.5 * math.log(h)) / LN2
             elif self.pow2:
@@ -381,6 +432,24 @@ class ChainContext:
                 continue
             self._add(q, self.specialPrimes)
             nPrimes -= 1
+
+    # ---- recryption parameters (include/helib/Context.h:616-638) ----
+    def stdDevForRecryption(self):
+        """Context::stdDevForRecryption: sqrt(phi(m) / m * skHwt * 2^k / 3) / 2, k the number of prime factors of m
+        (PAlgebra::getNFactors, src/PAlgebra.cpp:513-515)"""
+        k, n, f = 0, self.m, 2
+        while f * f <= n:
+            if n % f == 0:
+                k += 1
+                while n % f == 0:
+                    n //= f
+            f += 1
+        k += 1 if n > 1 else 0
+        return math.sqrt(self.phim / float(self.m) * float(self.hwt) * float(1 << k) / 3.0) * 0.5
+
+    def boundForRecryption(self):
+        """Context::boundForRecryption: a high-probability bound on |w0 + w1 s| in the powerful basis"""
+        return 0.5 + self.scale * self.stdDevForRecryption()
 
     # ---- helpers ----
     def logOfPrime(self, i):
@@ -498,6 +567,14 @@ class Ctxt:
         c.ksw_map = self.ksw_map
         c._like = self._like
         return c
+
+    def assign(self, other):
+        """*this = other for a ciphertext of the same context and keys: this object takes over other's parts and
+        bookkeeping (other must not be used afterwards); other's deferred noise updates are completed first, since
+        they are bound to it"""
+        other.lnNoise  # noqa: B018
+        self.__dict__.update(other.__dict__)
+        return self
 
     def _emptyLike(self):
         """Ctxt tmp(pubKey, ptxtSpace): an empty ciphertext under this one's keys, in its plaintext space"""
@@ -784,6 +861,15 @@ class Ctxt:
         self.lnNoise = self.lnNoise - math.log(p)
         self.ptxtSpace //= p
         self.intFactor %= self.ptxtSpace
+        return self
+
+    def reducePtxtSpace(self, newPtxtSpace):
+        """Ctxt::reducePtxtSpace (src/Ctxt.cpp:576-584): the plaintext space becomes its gcd with newPtxtSpace"""
+        g = math.gcd(self.ptxtSpace, int(newPtxtSpace))
+        if g <= 1:
+            raise RuntimeError("New and old plaintext spaces are coprime")
+        self.ptxtSpace = g
+        self.intFactor %= g
         return self
 
     def multByP(self, e=1):
@@ -1128,6 +1214,49 @@ class Ctxt:
         self.parts = {"1": o0, "s": o1}
         self.primeSet = self.primeSet | frozenset(sp)
         self._defer(update)
+
+    def switchToKey(self, ks):
+        """Ctxt::reLinearize(keyID) (src/Ctxt.cpp:720-786, as src/recryption.cpp:434 calls it) for a canonical
+        ciphertext: the s part is key-switched by ks, a keys.KeySwitchInfo from this key to another one, and the
+        result, parts "1" and "s", is relative to THAT key.  The mod-up, the digits and the noise are reLinearize's."""
+        self._materializeTensor()
+        if set(self.parts) - {"1", "s"}:
+            raise RuntimeError("switchToKey takes a ciphertext in canonical form")
+        if "s" not in self.parts:
+            return self
+        ctx = self.context
+        self.dropSmallAndSpecialPrimes()
+        sp = list(ctx.specialPrimes)
+        logProd = ctx.logOfProduct(sp)
+        digits = [[i for i in d if i in self.primeSet] for d in ctx.digits]
+        digits = [d for d in digits if d]
+        self.ptxtSpace = math.gcd(self.ptxtSpace, ks.ptxtSpace)
+        self.intFactor %= self.ptxtSpace
+        res = self.ops.reLinearize(self.parts["1"], None, self.parts["s"], ks.W, digits, sp)
+        added = -math.inf
+        for d in digits:   # the high-probability bound on a digit (src/DoubleCRT.cpp:520-529)
+            added = logaddexp(added, math.log(ctx.noiseBoundForUniform(0.5, ctx.phim)) + ctx.logOfProduct(d) +
+                              math.log(ks.noiseBound))
+        ln = logaddexp(self.lnNoise + logProd, added)
+        self.parts = {"1": res[0], "s": res[1]}
+        self.primeSet = self.primeSet | frozenset(sp)
+        self.lnNoise = ln
+        return self
+
+    def replicated(self, batch):
+        """this ciphertext with every part repeated over `batch` elements (a part of batch 1 is broadcast into a zeroed
+        part of the wanted batch): what `ctxt = recryptEkey` needs when the constants that follow are batched"""
+        c = self.clone()
+        for h, part in list(c.parts.items()):
+            have = getattr(part, "batch", 1)
+            if have == batch:
+                continue
+            if have != 1:
+                raise RuntimeError("replicated: a part holds %d elements, not 1" % have)
+            wide = type(part)(part.context, part.getIndexSet(), batch)
+            wide += part
+            c.parts[h] = wide
+        return c
 
     def _matrixFor(self, hnd):
         """PubKey::getKeySWmatrix for the part's handle; LogicError in the reference when absent"""

@@ -151,6 +151,11 @@ class PubKey:
         self.ptxtSpace = context.ptxtSpace
         self.skBounds = []
         self.keySwitching = {}            # (fromSPower, fromXPower) -> KeySwitchInfo
+        # matrices between two different keys, (fromSPower, fromXPower, fromIdx, toIdx) -> KeySwitchInfo: the map above
+        # is keyed by the powers alone and keeps answering for key 0 as it did
+        self.keySwitchingTo = {}
+        self.recryptKeyID = -1            # genRecryptData: the key recryption switches to ...
+        self.recryptEkey = None           # ... and its encryption under key 0 at plaintext space p^(e - e' + r)
 
     # -- PubKey::getKeySWmatrix --
     def haveKeySWmatrix(self, fromSPower, fromXPower):
@@ -439,14 +444,21 @@ class SecKey(PubKey):
             return None
         if fromSPower == 1 and fromXPower == 1 and fromIdx == toIdx:
             return None
-        if self.haveKeySWmatrix(fromSPower, fromXPower):
+        cross = (fromSPower, fromXPower, fromIdx, toIdx) if fromIdx != toIdx else None
+        if cross is not None:
+            if cross in self.keySwitchingTo:
+                return self.keySwitchingTo[cross]
+        elif self.haveKeySWmatrix(fromSPower, fromXPower):
             return self.keySwitching[(fromSPower, fromXPower)]
         idx = list(cc.ctxtPrimes) + list(cc.specialPrimes)
         fromKey = self._keyRows(idx, fromSPower, fromXPower, fromIdx)
         n = len(cc.digits)
         a = [be.randomize(idx, self.sampler.rng) for _ in range(n)]
         if p < 2:
-            p = self.ptxtSpace
+            if getattr(cc, "bootstrappable", False):   # the larger bootstrapping plaintext space (src/keys.cpp:1214-1221)
+                p = cc.p ** (cc.e - cc.ePrime + cc.r)
+            else:
+                p = self.ptxtSpace
         b, noise = [], 0.0
         for i in range(n):
             bi, noise = RLWE1(be, self.sampler, idx, a[i], self.sKeys[toIdx], p)
@@ -458,8 +470,29 @@ class SecKey(PubKey):
         hb = np.stack([x.download()[:, 0] for x in b])
         ha = np.stack([x.download()[:, 0] for x in a])
         ks = KeySwitchInfo(fromSPower, fromXPower, be.keySwitch(idx, hb, ha), p, noise, hb, ha)
-        self.keySwitching[(fromSPower, fromXPower)] = ks
+        if cross is not None:
+            self.keySwitchingTo[cross] = ks
+        else:
+            self.keySwitching[(fromSPower, fromXPower)] = ks
         return ks
+
+    def genRecryptData(self, rc):
+        """SecKey::genRecryptData (src/keys.cpp:1678-1713) -> the ID of the recryption key: a second key of Hamming
+        weight rc.skHwt imported without matrices of its own, the matrix from key 0 to it at plaintext space p^r, and
+        that key's polynomial encrypted under key 0 at plaintext space p^(e - e' + r).  rc: helib_amd.recryption's
+        RecryptData."""
+        if self.recryptKeyID >= 0:
+            return self.recryptKeyID
+        if not getattr(self.cc, "bootstrappable", False):
+            raise RuntimeError("Cannot generate recrypt data for non-bootstrappable context")
+        p2r = self.cc.p ** self.cc.r
+        p2ePr = self.cc.p ** (rc.e - rc.ePrime + self.cc.r)
+        keyPoly, bound = self.sampler.sampleHWtBounded(rc.skHwt)
+        keyID = self.ImportSecKey(keyPoly, bound, p2r, maxDegKswitch=1)
+        self.GenKeySWmatrix(1, 1, 0, keyID, p2r)
+        self.recryptEkey = self.skEncrypt(keyPoly, p2ePr, 0)
+        self.recryptKeyID = keyID
+        return keyID
 
     def skEncrypt(self, ptxt, ptxtSpace=0, skIdx=0):
         cc, be = self.cc, self.be

@@ -192,6 +192,19 @@ class PowerfulDCRT:
         """coefficient rows (DoubleCRT.iFFT) -> powerful cubes, row by row modulo the row's prime, in place"""
         return capi.polyToPowerful(self.table, dcrt)
 
+    def coefficientCube(self, dcrt):
+        """the powerful cubes of a DoubleCRT in evaluation form, as a new DoubleCRT (the operand is left alone): copy,
+        iFFT, dcrtToPowerful -- PowerfulDCRT::dcrtToPowerful (src/powerful.cpp:354-383) with the rows kept apart"""
+        cube = dcrt.copy()
+        cube.iFFT()
+        return self.dcrtToPowerful(cube)
+
+    def fromCube(self, cube):
+        """the inverse, in place: powerfulToDCRT, then FFT -- the rows are in evaluation form again"""
+        self.powerfulToDCRT(cube)
+        cube.FFT()
+        return cube
+
     def powerfulToDCRT(self, dcrt):
         """powerful cubes -> coefficient rows, in place (DoubleCRT.FFT then gives the evaluation form back)"""
         return capi.powerfulToPoly(self.table, dcrt)

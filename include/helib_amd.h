@@ -745,6 +745,43 @@ int hx_powerful_to_poly(const hx_powerful* t, hx_poly* a);
  * same kernel on one row. */
 int hx_powerful_words(const hx_powerful* t, int to_powerful, uint64_t q, const int64_t* in, int batch, int64_t* out);
 
+/* ---------------- recryption's pre-processing (recrypt.hip, recrypt_core.h) ----------------
+ * The step of PubKey::reCrypt (src/recryption.cpp:367-545) between the switch to the recryption key and the product with
+ * the encrypted key: Ctxt::rawModSwitch (src/Ctxt.cpp:2949-3049) from Q = prod S, S the part's primes, to q = p^e + 1,
+ * then newMakeDivisible (src/recryption.cpp:73-136) and the division by p2ePrime = p^e' (:495-497) -- for one
+ * ciphertext part, in one kernel, one thread per coefficient, with no big integers (the mixed-radix lift of
+ * hx_poly_rem, and Q^-1 modulo 2^64 for the quotient; helib_amd/csrc/recrypt_core.h has the proof).
+ *   in:  the part as coefficient rows, [k][batch][phi(m)] words below each row's prime: hx_ntt_inverse, then
+ *        hx_poly_to_powerful.  A poly carries no mark of its form (no entry of this header can tell evaluation rows
+ *        from coefficient rows), so this is the caller's to get right, as it is for hx_poly_to_powerful.
+ *   out: another poly of the same context and batch on the primes T of the encrypted recryption key (its rows are
+ *        overwritten): row t becomes w mod t in [0, t), in the same coefficient order as the input.
+ * Per coefficient, as exact integers:
+ *   1. c = the centred lift of the residues in [-Q/2, Q/2), as DoubleCRT::toPoly gives it.
+ *   2. c q = Q X + Y by floor division; Y > floor(Q/2): Y -= Q, X += 1.
+ *   3. delta = (Y mod p2r)(Q^-1 mod p2r) mod p2r >= 0; delta -= p2r if delta > floor(p2r/2), or p2r is even,
+ *      delta = p2r/2 and (Y < 0, or Y = 0 and tie bit 0).
+ *   4. x = X + delta; x -= q if x > floor(q/2), or q even, x = q/2 and tie bit 1; else x += q if x < -floor(q/2), or
+ *      q even, x = -q/2 and tie bit 1.
+ *   5. z = x mod p2ePrime in [0, p2ePrime); v = p2ePrime - z if z > floor(p2ePrime/2), or p = 2, z = p2ePrime/2 and tie
+ *      bit 2; else v = -z; p2ePrime = 1: v = 0.  w = (x + q v) / p2ePrime, exactly.
+ *   6. out row t = w mod t.
+ * The reference goes powerful -> polynomial basis after 4 (powerfulToZZX, src/Ctxt.cpp:3041), back for 5
+ * (ZZXtoPowerful, src/recryption.cpp:95) and to the polynomial basis again before it divides (:131, :495-497); both maps are integer-linear and inverse to each other on integers this small, and no
+ * step looks at a coefficient's position, so the fused chain on the cube gives the cube of the reference's result.
+ * Its ties are NTL::RandomBnd(2); here tie bit `which` of coefficient j of batch element b is bit 61 + which of
+ * mix(mix(mix(mix(tie_seed) + part) + b) + j), mix the splitmix64 finaliser (recrypt_core.h): reproducible from the
+ * seed, balanced.  x_host / v_host (either may be NULL): [batch][phi(m)] signed words, the x of step 4 and the v of
+ * step 5, for tests.
+ * HX_ERR_INVALID with the figures: gcd(q, p2r) != 1; q != 1 mod p2ePrime; gcd(Q mod q, q) != 1; q >= 2^30 (the
+ * reference's e_bnd, src/recryption.cpp:211-217); p2r or p2ePrime not a power of p below 2^30; an output prime below
+ * 2^31 (|w| < q is reduced without a division); out = in,
+ * another context, another batch; an open graph capture.  HX_ERR_UNSUPPORTED: more than 16 input rows (three
+ * ciphertext primes and the special primes are what reCrypt leaves), more than 64 output rows, a batch above 65535.  A refused call
+ * touches no output.  Synchronous. */
+int hx_recrypt_prep(const hx_poly* in, hx_poly* out, uint64_t q, uint64_t p, uint64_t p2r, uint64_t p2ePrime,
+                    uint64_t tie_seed, int part, int64_t* x_host, int64_t* v_host);
+
 #ifdef __cplusplus
 }
 #endif
