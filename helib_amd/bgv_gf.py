@@ -13,50 +13,33 @@ element of GF(p^d) = Z_p[X] / G, d = ord_m(p), r = 1.  helib_amd.bgv_crt / bgv_h
   frobeniusAutomorph  Ctxt::frobeniusAutomorph (keys: helib_amd.keys.addFrbMatrices): slot alpha -> alpha^(p^j) mod G
   mulPlain / frobeniusPlain     the plain-side truths: the slot-wise product mod (G, p) and alpha -> alpha^(p^j)
 
+The members that know a slot is an element of Z_p[X] / G -- the check of G, _slots, the Frobenius, the plain side -- and
+the encoder are helib_amd.slot_ring's (SlotRing, SlotEncoder) with the modulus P = p; this module adds the constructor.
+
 Out of scope, refused with a message: a G other than F_0 (a root of G in Z_p[X] / F_0 would have to be found: the
 reference's FindRoots branch of mapToSlots, src/PAlgebra.cpp:1116-1186), deg G < d, d > 64, and p^r with r > 1, which is
 helib_amd.bgv_gr (slots in the Galois ring Z_(p^r)[X] / G; unpack / repack over either class: helib_amd.intraslot).  Linearized
 polynomials, MatMul1D with GF entries and BlockMatMul1D over these slots are helib_amd.bgv_gf_matmul (helib_amd.bgv_matmul
 takes integer matrices of two axes).  Nothing here imports oracle/."""
-import numpy as np
-
-from . import bgv_hypercube, capi
+from . import bgv_hypercube, capi, slot_ring
 from .ckks import LogicError
 
 
-class GfEncoder:
+class GfEncoder(slot_ring.SlotEncoder):
     """GF(p^d) slot vectors <-> polynomials on the device (hx_bgv_gf_*): CrtEncoder's members, and G"""
 
     def __init__(self, hxctx, p):
-        self.g = hxctx
-        self.table = capi.BgvGf(hxctx, p)
-        self.G = list(self.table.G)
-
-    def dims(self):
-        """(gens, signed ords) of the hypercube of Z_m^* / <p>"""
-        return self.table.gens, self.table.ords
-
-    def encode(self, v, mul, idx, coeffs=False):
-        return capi.bgvGfEncode(self.table, v, idx, mul, coeffs=coeffs)
-
-    def split(self, poly):
-        return capi.splitBatch(poly)
-
-    def embed(self, coeffs):
-        return capi.bgvGfEmbed(self.table, coeffs)
-
-    def decode(self, acc, factor_inv):
-        return capi.bgvGfDecode(self.table, acc, factor_inv)
-
-    def norm(self, coeffs):
-        """embeddingLargestCoeff of every zzX [B, phi(m)]"""
-        return capi.embeddingLargestCoeff(self.g, np.asarray(coeffs, dtype=np.float64))
+        super().__init__(hxctx, capi.BgvGf(hxctx, p))
 
 
-class EncryptedArray(bgv_hypercube.EncryptedArray):
+class EncryptedArray(slot_ring.SlotRing, bgv_hypercube.EncryptedArray):
     """context: a BGV helib_amd.ctxt.ChainContext with gcd(p, m) = 1 and r = 1; hxctx: the capi.Context holding its
     primes; G: None for F_0, or F_0's coefficients (constant first, any representatives mod p).  An injected encoder has
-    GfEncoder's members (encode takes [B, nslots, d] or, for constants, [B, nslots]) and G."""
+    GfEncoder's members (encode takes [B, nslots, d] or, for constants, [B, nslots]) and G.  self.P = self.p is the
+    modulus of the slots."""
+
+    _otherG = ("EncryptedArray: G is not F_0, the first factor of Phi_m mod p; another G needs a root of G "
+               "in Z_p[X] / F_0 (the reference's FindRoots branch of mapToSlots), which is not built")
 
     def __init__(self, context, hxctx, G=None, encoder=None):
         if getattr(context, "ckks", False):
@@ -65,102 +48,5 @@ class EncryptedArray(bgv_hypercube.EncryptedArray):
             raise capi.HxError(capi.HX_ERR_UNSUPPORTED,
                                "BGV slots: plaintext space p^r with r > 1 (Hensel lifting) is not built")
         super().__init__(context, hxctx, encoder=encoder if encoder is not None else GfEncoder(hxctx, context.p))
-        p, d = self.p, self.zMStar.ordP
-        self.G = [int(x) % p for x in self.enc.G]
-        if len(self.G) != d + 1 or self.G[d] != 1:
-            raise LogicError("EncryptedArray: the encoder's G is not monic of degree d = %d" % d)
-        if G is not None:
-            g = [int(x) % p for x in G]
-            while g and g[-1] == 0:
-                g.pop()
-            if len(g) - 1 < d:
-                raise LogicError("EncryptedArray: deg G = %d < d = %d is not built (only G = F_0, of degree d)" % (len(g) - 1, d))
-            if g != self.G:
-                raise LogicError("EncryptedArray: G is not F_0, the first factor of Phi_m mod p; another G needs a root of G "
-                                 "in Z_p[X] / F_0 (the reference's FindRoots branch of mapToSlots), which is not built")
-        self._G = np.array(self.G[:d], dtype=np.int64)
-        self._frob = None
-
-    def getG(self):
-        return list(self.G)
-
-    def getDegree(self):
-        return self.zMStar.ordP
-
-    def _slots(self, v):
-        """-> int64 [B, nslots, d].  One axis: one vector of constants; two: [B, <= nslots] constants; three:
-        [B, <= nslots, <= d]; what is missing is zero."""
-        a = np.asarray(v)
-        if a.dtype == object or a.dtype.kind not in "iu" or a.dtype == np.uint64:
-            a = np.array([int(x) % self.p for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
-        a = a.astype(np.int64)
-        if a.ndim == 1:
-            a = a[None, :]
-        if a.ndim == 2:
-            a = a[:, :, None]
-        n, d = self.size(), self.getDegree()
-        if a.ndim != 3 or a.shape[1] > n or a.shape[2] > d:
-            raise capi.InvalidArgument(capi.HX_ERR_INVALID, "more values than slots, or more coefficients than d")
-        out = np.zeros((a.shape[0], n, d), dtype=np.int64)
-        out[:, :a.shape[1], :a.shape[2]] = a
-        return out
-
-    def decrypt_batch(self, ct, sk):
-        """SecKey::Decrypt + decode for every element of a batched Ctxt -> int64 [B, nslots, d] in [0, p)"""
-        out = super().decrypt_batch(ct, sk)
-        return out if out.ndim == 3 else self._slots(out)
-
-    def frobeniusAutomorph(self, ct, j):
-        """EncryptedArray::frobeniusAutomorph: every slot alpha -> alpha^(p^j) mod G, by Ctxt::frobeniusAutomorph
-        (X -> X^(p^j): H(X^(p^j)) = H^(p^j) mod p, and the slot maps are ring maps); j counts mod d"""
-        ct.frobeniusAutomorph(j % self.getDegree())
-        return ct
-
-    # ---- the plain side ----
-    def _mul(self, a, b):
-        """the product in Z_p[X] / G along the last axis of two arrays [B, n, d] with entries in [0, p)"""
-        p, d = self.p, self.getDegree()
-        w = np.zeros(np.broadcast_shapes(a.shape, b.shape)[:2] + (2 * d - 1,), dtype=np.int64)
-        for l in range(d):                                  # every product is below p^2 < 2^62 and reduced at once
-            w[:, :, l:l + d] = (w[:, :, l:l + d] + a[:, :, l:l + 1] * b % p) % p
-        for k in range(2 * d - 2, d - 1, -1):               # X^k = -X^(k - d) (G - X^d)
-            w[:, :, k - d:k] = (w[:, :, k - d:k] - w[:, :, k:k + 1] * self._G % p) % p
-        return np.ascontiguousarray(w[:, :, :d])
-
-    def mulPlain(self, a, b):
-        """the slot-wise product in Z_p[X] / G -> int64 [B, nslots, d]"""
-        return self._mul(self._slots(a) % self.p, self._slots(b) % self.p)
-
-    def _frobenius(self):
-        """row l = X^(l p) mod G: alpha^p = sum_l alpha_l X^(l p), the coefficients being fixed by the Frobenius"""
-        if self._frob is None:
-            p, d = self.p, self.getDegree()
-            one, x = np.zeros((1, 1, d), dtype=np.int64), np.zeros((1, 1, d), dtype=np.int64)
-            one[0, 0, 0] = 1
-            if d == 1:
-                x[0, 0, 0] = -self.G[0] % p                 # X mod the linear G
-            else:
-                x[0, 0, 1] = 1
-            xp, e = one, p                                  # X^p by square and multiply
-            while e:
-                if e & 1:
-                    xp = self._mul(xp, x)
-                x = self._mul(x, x)
-                e >>= 1
-            rows, cur = [], one
-            for _ in range(d):
-                rows.append(cur[0, 0])
-                cur = self._mul(cur, xp)
-            self._frob = np.stack(rows)
-        return self._frob
-
-    def frobeniusPlain(self, a, j):
-        """every slot alpha -> alpha^(p^j) mod G -> int64 [B, nslots, d]"""
-        a, p, d = self._slots(a) % self.p, self.p, self.getDegree()
-        F = self._frobenius()
-        for _ in range(j % d):
-            nxt = np.zeros_like(a)
-            for l in range(d):
-                nxt = (nxt + a[:, :, l:l + 1] * F[l] % p) % p
-            a = nxt
-        return a
+        self.P = self.p
+        self._initRing(G)

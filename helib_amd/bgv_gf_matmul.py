@@ -21,92 +21,23 @@ halves and (poly1, dim, D) of the reference are all of this form.
                 in chunks through capi.bgvGfGather (bgv_gf_gather_kernel) and ea.enc.encode
   host path     numpy does both, then ea.enc.encode: a callable matrix, an injected encoder, device_diagonals=False
 
-Both give the same words and sizes.  The bodies are private helpers that take the modulus of the slot words and the
-tables (_evalLinPolyMod, _frobEachMod, _mulPlainMod, _hostConstantMod, _constants, the hooks of _GfMatrix and of the exec
-classes): helib_amd.bgv_gr_matmul runs them modulo p^r over helib_amd.bgv_gr.EncryptedArray.  Refused with a message: BlockMatMulFull*, MatMulFull with GF entries,
+Both give the same words and sizes.  The arithmetic -- the tables, the linearized polynomials, the slot automorphisms,
+the plain-side products, one constant on the host -- lives in helib_amd.slot_ring, which reads the modulus from the
+array (ea.P); the functions here are this module's check of the array in front of it.  What is this module's own is the
+matrices, the constants of an exec (_Maps, _constants) and the execs; helib_amd.bgv_gr_matmul subclasses them over
+helib_amd.bgv_gr.EncryptedArray.  Refused with a message: BlockMatMulFull*, MatMulFull with GF entries,
 multipleTransforms for the GF-entry MatMul1D, r > 1 (bgv_gf.EncryptedArray refuses it).  Nothing here imports oracle/."""
 import os
 import time
 
 import numpy as np
 
-from . import bgv, bgv_gf, bgv_hypercube, bgv_matmul, capi
-from . import ctxt as hc
+from . import bgv_gf, bgv_hypercube, bgv_matmul, capi, slot_ring
 from . import keys as hk
 from . import linalg
 from .ckks import LogicError
 
 GATHER_CHUNK = 64      # descriptors per gather call: 64 n d words of scratch
-
-
-# ---- arithmetic modulo p ----
-def _matmod(a, b, p):
-    """a @ b mod p for non-negative int64 arrays below p, through Python integers when the sums could leave int64"""
-    if p * p * max(1, a.shape[-1]) < 2 ** 63:
-        return a @ b % p
-    return np.array((a.astype(object) @ b.astype(object)) % p, dtype=np.int64)
-
-
-def _invmod(a, p):
-    """the inverse of a square matrix over Z_p (Gauss-Jordan on Python integers); LogicError when singular"""
-    n = a.shape[0]
-    w = np.concatenate([a.astype(object) % p, np.eye(n, dtype=object)], axis=1)
-    for c in range(n):
-        piv = next((r for r in range(c, n) if w[r, c]), None)
-        if piv is None:
-            raise LogicError("a singular matrix modulo p")
-        if piv != c:
-            w[[c, piv]] = w[[piv, c]]
-        w[c] = w[c] * pow(int(w[c, c]), -1, p) % p
-        for r in range(n):
-            if r != c and w[r, c]:
-                w[r] = (w[r] - w[r, c] * w[c]) % p
-    return np.array(w[:, n:], dtype=np.int64)
-
-
-class _Tables:
-    """frob[e][l] = X^(l p^e) mod G; M[i][j] = (X^j)^(p^i) = frob[i][j] (buildLinPolyMatrix); K = M^-1 over the field,
-    K[j][k] = beta_j^(p^k) with beta the dual basis of the powers of X under the trace (M is a Moore matrix: (K M)[j][j'] =
-    sum_k (beta_j X^j')^(p^k) = Tr(beta_j X^j')); beta = the inverse of the Gram matrix Tr(X^(i + j)) over Z_p"""
-
-    def __init__(self, ea):
-        p, d = ea.p, ea.getDegree()
-        F1 = ea._frobenius() % p
-        self.frob = np.zeros((d, d, d), dtype=np.int64)
-        self.frob[0] = np.eye(d, dtype=np.int64)
-        for e in range(1, d):
-            self.frob[e] = _matmod(self.frob[e - 1], F1, p)
-        tr = self.frob[:, :, 0].sum(axis=0) % p                     # Tr(X^l) = sum_e [X^0](X^(l p^e)), l < d
-        pw, x = [], np.zeros((1, 1, d), dtype=np.int64)
-        x[0, 0, 0] = 1
-        step = np.zeros((1, 1, d), dtype=np.int64)
-        if d > 1:
-            step[0, 0, 1] = 1
-        for _ in range(2 * d - 1):                                  # X^s mod G, s <= 2 d - 2
-            pw.append(x[0, 0])
-            x = ea._mul(x, step) if d > 1 else x
-        trs = _matmod(np.stack(pw), tr[:, None], p)[:, 0]
-        gram = np.array([[trs[i + j] for j in range(d)] for i in range(d)], dtype=np.int64)
-        beta = _invmod(gram, p)
-        self.K = np.stack([np.stack([_matmod(beta[j][None, :], self.frob[k], p)[0] for k in range(d)]) for j in range(d)])
-        self._T = None
-        self.ea = ea
-
-    def flat(self):
-        """T[(j, b)][(k, c)] = [X^c](X^b K[j][k] mod G), [d^2, d^2]"""
-        if self._T is None:
-            d = self.K.shape[0]
-            eye = np.eye(d, dtype=np.int64)
-            T = np.stack([self.ea._mul(eye[:, None, :], self.K[j][None, :, :]) for j in range(d)])      # [j, b, k, c]
-            self._T = np.ascontiguousarray(T.reshape(d * d, d * d))
-        return self._T
-
-
-def _tables(ea):
-    t = ea.__dict__.get("_linpoly")
-    if t is None:
-        t = ea.__dict__["_linpoly"] = _Tables(ea)
-    return t
 
 
 def _check(ea):
@@ -119,101 +50,47 @@ def _check(ea):
 def linPolyMatrix(ea):
     """(M, K) as int64 [d, d, d]: M[i][j] = (X^j)^(p^i) mod G and its inverse over GF(p^d)"""
     _check(ea)
-    t = _tables(ea)
+    t = slot_ring._tables(ea)
     return t.frob.copy(), t.K.copy()
 
 
 def linPolyTable(ea):
     """the flat d^2 x d^2 table over Z_p with C = E T"""
     _check(ea)
-    return _tables(ea).flat()
+    return slot_ring._tables(ea).flat()
 
 
 def buildLinPolyCoeffs(ea, L):
     """EncryptedArrayDerived::buildLinPolyCoeffs: L [..., d, d], row j the coefficients of the image of X^j -> C
     [..., d, d], row k the coefficients of C[k] = sum_j L[j] K[j][k]; the map is alpha -> sum_k C[k] alpha^(p^k)"""
     _check(ea)
-    p, d = ea.p, ea.getDegree()
-    L = np.asarray(L, dtype=np.int64) % p
-    if L.ndim < 2 or L.shape[-2:] != (d, d):
-        raise LogicError("buildLinPolyCoeffs takes [..., d, d] with d = %d" % d)
-    K = _tables(ea).K
-    Lf = L.reshape(-1, d, d)
-    C = np.zeros_like(Lf)
-    for k in range(d):
-        C[:, k, :] = ea._mul(Lf, K[None, :, k, :]).sum(axis=1) % p
-    return C.reshape(L.shape)
+    return slot_ring.buildLinPolyCoeffs(ea, L)
 
 
 def linPolyFlat(ea, E):
     """buildLinPolyCoeffs through the flat table: what the device computes"""
     _check(ea)
-    d = ea.getDegree()
-    E = np.asarray(E, dtype=np.int64) % ea.p
-    return _matmod(E.reshape(-1, d * d), linPolyTable(ea), ea.p).reshape(E.shape)
+    return slot_ring.linPolyFlat(ea, E)
 
 
 def evalLinPoly(ea, C, a):
     """sum_k C[k] alpha^(p^k) slot by slot: C [d, d] (one map) or [nslots, d, d], a slots -> [B, nslots, d]"""
-    return _evalLinPolyMod(ea, C, a, ea.p)
-
-
-def _evalLinPolyMod(ea, C, a, p):
-    """evalLinPoly with the modulus p of the slot words (ea.frobeniusPlain is sigma^k)"""
-    a, d = ea._slots(a) % p, ea.getDegree()
-    C = np.asarray(C, dtype=np.int64) % p
-    C = np.broadcast_to(C, (ea.size(), d, d)) if C.ndim == 2 else C
-    out = np.zeros_like(a)
-    for k in range(d):
-        out = (out + ea._mul(ea.frobeniusPlain(a, k), C[None, :, k, :])) % p
-    return out
+    _check(ea)
+    return slot_ring.evalLinPoly(ea, C, a)
 
 
 # ---- plaintext automorphisms ----
 def slotAutomorph(ea, k):
-    """X -> X^k on GF slots -> (perm, frob): the new slot j is Frob^frob[j] of the old slot perm[j].  Slot j reads the
-    plaintext at zeta^(1 / t_j) (zeta = X mod G, t_j = reps()[j]); after the automorphism that is its value at
-    zeta^(k / t_j) = zeta^(p^e / t_i) for the slot i whose coset holds t_j / k, with t_i k = t_j p^e (mod m), and H(y^(p^e))
-    = H(y)^(p^e) over Z_p."""
+    """X -> X^k on GF slots -> (perm, frob): the new slot j is Frob^frob[j] of the old slot perm[j]
+    (slot_ring.slotAutomorph has the derivation)"""
     _check(ea)
-    return _slotAutomorph(ea, k)
-
-
-def _slotAutomorph(ea, k):
-    """slotAutomorph for any array with bgv_gf's geometry (ea.p the prime): over Z_(p^r) the same holds with sigma^e for
-    the e-th power of the Frobenius, because sigma fixes the lifted F_0"""
-    m = ea.m
-    k %= m
-    cache = ea.__dict__.setdefault("_slotAut", {})
-    if k not in cache:
-        kinv, p, d = pow(k, -1, m), ea.p % m, ea.getDegree()
-        log = {pow(p, e, m): e for e in range(d)}
-        cos, reps = ea._cosets(), ea.zMStar.reps()
-        perm = np.array([cos[t * kinv % m] for t in reps], dtype=np.int64)
-        frob = np.array([log[reps[i] * k % m * pow(t, -1, m) % m] for i, t in zip(perm, reps)], dtype=np.int64)
-        cache[k] = (perm, frob)
-    return cache[k]
-
-
-def _frobEach(ea, a, e):
-    """slot s of a [B, n, d] -> its Frob^e[s]"""
-    return _frobEachMod(a, e, _tables(ea).frob, ea.p)
-
-
-def _frobEachMod(a, e, fr, p):
-    """_frobEach over the tables fr = frob [d, d, d] modulo p"""
-    out = a.copy()
-    for x in np.unique(e):
-        if x:
-            w = e == x
-            out[:, w] = _matmod(a[:, w], fr[x], p)
-    return out
+    return slot_ring.slotAutomorph(ea, k)
 
 
 def automorphPlain(ea, a, k):
     """the slots of the plaintext with X -> X^k applied -> int64 [B, nslots, d]"""
-    perm, frob = slotAutomorph(ea, k)
-    return _frobEach(ea, (ea._slots(a) % ea.p)[:, perm], frob)
+    _check(ea)
+    return slot_ring.automorphPlain(ea, a, k)
 
 
 # ---- the matrices ----
@@ -228,31 +105,20 @@ def _geometry(ea, dim):
     return D, s % st + s // (st * D) * st, s % (st * D) // st
 
 
-def _ints(ea, a):
-    return _intsMod(a, ea.p)
-
-
-def _intsMod(a, p):
+def _ints(a, P):
+    """any integers -> contiguous int64 in [0, P)"""
     a = np.asarray(a)
     if a.dtype == object or a.dtype.kind not in "iu" or a.dtype == np.uint64:
-        a = np.array([int(x) % p for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
-    return np.ascontiguousarray(a.astype(np.int64) % p)
+        a = np.array([int(x) % P for x in a.reshape(-1)], dtype=np.int64).reshape(a.shape)
+    return np.ascontiguousarray(a.astype(np.int64) % P)
 
 
 class _GfMatrix:
     block = False
     ring = False               # the device matrix is built over a table of any r (capi.BgvGfMatrix(ring=True))
 
-    # what a module over another ring of slots replaces: the check of the array, the modulus of the words, the
-    # linearized-polynomial coefficients of the blocks
+    # what a module over another class of array replaces: its check
     _checkArray = staticmethod(lambda ea: _check(ea))
-
-    @staticmethod
-    def _modulus(ea):
-        return ea.p
-
-    def _coeffs(self, dense):
-        return buildLinPolyCoeffs(self.ea, dense)
 
     def getDim(self):
         return self.dim
@@ -270,7 +136,8 @@ class _GfMatrix:
     def values(self):
         """[nb, D, D, K, d]: what a slot can hold -- K = d coefficients of every block's linearized polynomial, or K = 1"""
         if self._values is None:
-            self._values = self._coeffs(self.dense) if self.block else self.dense[:, :, :, None, :]
+            self._values = (slot_ring.buildLinPolyCoeffs(self.ea, self.dense) if self.block
+                            else self.dense[:, :, :, None, :])
         return self._values
 
     def slotValues(self, i, k):
@@ -290,11 +157,10 @@ class MatMul1D(_GfMatrix):
         self.ea, self.dim, self.multiple, d = ea, dim, False, ea.getDegree()
         self.D, self.blk, self.col = _geometry(ea, dim)
         self.callable = callable(A)
-        p = self._modulus(ea)
         if self.callable:
-            rows = [[np.atleast_1d(_intsMod(A(i, j), p)) for j in range(self.D)] for i in range(self.D)]
+            rows = [[np.atleast_1d(_ints(A(i, j), ea.P)) for j in range(self.D)] for i in range(self.D)]
             A = [[np.pad(x, (0, d - len(x))) for x in r] for r in rows]
-        a = _intsMod(A, p)
+        a = _ints(A, ea.P)
         if a.ndim >= 4:
             raise LogicError("MatMul1D with GF entries: multipleTransforms (%d axes) is not built; BlockMatMul1D takes one "
                              "matrix per transform" % a.ndim)
@@ -322,7 +188,7 @@ class BlockMatMul1D(_GfMatrix):
         self.callable = callable(A)
         if self.callable:
             raise LogicError("BlockMatMul1D takes a dense array")
-        a = _intsMod(A, self._modulus(ea))
+        a = _ints(A, ea.P)
         self.multiple = a.ndim == 5
         if dim == ea.dimension() and not self.multiple:
             raise LogicError("BlockMatMul1D along the size-1 dimension takes one block per slot: [%d, 1, 1, %d, %d]" % (n, d, d))
@@ -352,27 +218,8 @@ def mulPlain(ea, v, mat):
     """mul(PlaintextArray, MatMul1D / BlockMatMul1D) on slots v -> int64 [B, nslots, d]: along mat's dimension and for
     every transform k, w[k][j] = sum_i v[k][i] * A_k[i][j] -- the product in Z_p[X] / G for a GF entry, the coefficient
     row vector times the d x d block for a block entry"""
-    return _mulPlainMod(ea, v, mat, ea.p)
-
-
-def _mulPlainMod(ea, v, mat, p):
-    """mulPlain with the modulus p of the slot words (ea._mul is the product of the slots' ring)"""
-    v, d, D = ea._slots(v) % p, ea.getDegree(), mat.D
-    B, n = v.shape[0], ea.size()
-    order = np.argsort(mat.blk * D + mat.col, kind="stable")           # slot of (transform, coordinate)
-    x = v[:, order].reshape(B, n // D, D, d)
-    A = mat.dense if mat.multiple else np.broadcast_to(mat.dense, (n // D,) + mat.dense.shape[1:])
-    w = np.zeros_like(x)
-    if mat.block:
-        xo, Ao = (x.astype(object), A.astype(object)) if p * p * d >= 2 ** 63 else (x, A)
-        terms = (xo[:, :, :, None, None, :] @ Ao[None])[..., 0, :] % p                     # [B, k, i, j, c]
-        w = np.array(terms.sum(axis=2) % p, dtype=np.int64)
-    else:
-        for j in range(D):
-            w[:, :, j] = ea._mul(x.reshape(B, -1, d), A[:, :, j].reshape(1, -1, d)).reshape(B, n // D, D, d).sum(axis=2) % p
-    out = np.zeros_like(v)
-    out[:, order] = w.reshape(B, n, d)
-    return out
+    _check(ea)
+    return slot_ring.mulPlain(ea, v, mat)
 
 
 # ---- the constants of an exec ----
@@ -383,7 +230,7 @@ class _Maps:
         self.ea, self.rows, self.index = ea, [], {}
 
     def add(self, k, mask=None):
-        perm, frob = _slotAutomorph(self.ea, k)
+        perm, frob = slot_ring.slotAutomorph(self.ea, k)
         src = perm if mask is None else np.where(np.asarray(mask)[perm] != 0, perm, -1)
         row = np.stack([src, np.where(src >= 0, frob, 0)], axis=1).astype(np.int32)
         key = row.tobytes()
@@ -393,33 +240,20 @@ class _Maps:
         return self.index[key]
 
 
-def hostConstant(ea, mat, i, k, row):
-    """one constant on the host: slot s = Frob^e(coefficient k of the entry the slot src[s] reads on diagonal i)"""
-    return _hostConstantMod(mat, i, k, row, _tables(ea).frob, ea.p)
+hostConstant = slot_ring.hostConstant
 
 
-def _hostConstantMod(mat, i, k, row, fr, p):
-    """hostConstant over the tables fr = frob [d, d, d] modulo p"""
-    src, e = row[:, 0].astype(np.int64), row[:, 1].astype(np.int64)
-    val = mat.slotValues(i, k)
-    out = np.where((src >= 0)[:, None], val[np.maximum(src, 0)], 0)
-    return _frobEachMod(out[None], e, fr, p)[0]
-
-
-def _constants(ea, mat, reqs, maps, idx, device, fused=False, const=None, batch=None):
-    """reqs [(i, k, map)] -> [None for a zero constant | (DoubleCRT of batch 1 on idx, size)].  const(i, k, row): one
-    constant on the host (default hostConstant).  fused (device only): the constants never leave the device --
-    enc.encodeGathered gives the flags of a chunk, then the live descriptors go through it in the encoder's batches.
-    batch: constants per encode call for an encoder that is no GfEncoder and names no max_batch (None: one)"""
+def _constants(ea, mat, reqs, maps, idx, device, fused=False):
+    """reqs [(i, k, map)] -> [None for a zero constant | (DoubleCRT of batch 1 on idx, size)].  fused (device only): the
+    constants never leave the device -- enc.encodeGathered gives the flags of a chunk, then the live descriptors go
+    through it in the encoder's batches: max_batch if the encoder names one, 16 for the device encoders
+    (slot_ring.SlotEncoder), else one"""
     enc = ea.enc
-    step = max(1, int(getattr(enc, "max_batch", (batch or 16) if isinstance(enc, bgv_gf.GfEncoder) or batch else 1)))
+    step = max(1, int(getattr(enc, "max_batch", 16 if isinstance(enc, slot_ring.SlotEncoder) else 1)))
     split = getattr(enc, "split", lambda poly: [poly])
     out = [None] * len(reqs)
     table = np.stack(maps.rows) if maps.rows else None
     handle = mat.handle(enc) if device else None
-    if const is None:
-        def const(i, k, row):
-            return hostConstant(ea, mat, i, k, row)
     for lo in range(0, len(reqs), GATHER_CHUNK):
         chunk = reqs[lo:lo + GATHER_CHUNK]
         if device and fused:
@@ -428,7 +262,7 @@ def _constants(ea, mat, reqs, maps, idx, device, fused=False, const=None, batch=
         elif device:
             slots, nz = capi.bgvGfGather(handle, np.array(chunk, dtype=np.int32), table)
         else:
-            slots = np.stack([const(i, k, maps.rows[mp]) for i, k, mp in chunk])
+            slots = np.stack([slot_ring.hostConstant(ea, mat, i, k, maps.rows[mp]) for i, k, mp in chunk])
             nz = slots.reshape(len(chunk), -1).any(axis=1)
         live = [int(t) for t in np.nonzero(nz)[0]]
         for a in range(0, len(live), step):
@@ -606,48 +440,16 @@ class BlockMatMul1DExec(bgv_matmul.MatMul1DExec):
 
 
 # ---- linearized polynomials on ciphertexts ----
-def applyLinPolyLL(ct, encodedC):
-    """applyLinPolyLL (src/EncryptedArray.cpp:855-870): encodedC[j] is an EncodedPtxt (bgv_gf.EncryptedArray.encodePtxt)
-    holding C[j] of every slot's map, or (DoubleCRT, size); the Frobenius keys come from keys.addFrbMatrices"""
-    def times(c, k):
-        if isinstance(k, bgv.EncodedPtxt):
-            k.ea.multByConstant(c, k)
-        else:
-            c.multByConstant(*k)
-    linalg._cleanUp(ct)
-    tmp = ct.clone()
-    times(ct, encodedC[0])
-    for j in range(1, len(encodedC)):
-        tmp1 = tmp.clone()
-        tmp1.frobeniusAutomorph(j)
-        times(tmp1, encodedC[j])
-        ct += tmp1
-    return ct
+applyLinPolyLL = slot_ring.applyLinPolyLL
 
 
 def applyLinPoly1(ea, ct, C):
     """the same map in every slot (:802-821): C [d, d] from buildLinPolyCoeffs"""
     _check(ea)
-    return _applyLinPoly1(ea, ct, C)
-
-
-def _applyLinPoly1(ea, ct, C):
-    d = ea.getDegree()
-    C = np.asarray(C, dtype=np.int64)
-    if C.shape != (d, d):
-        raise LogicError("ea's degree does not match the size of C")
-    return applyLinPolyLL(ct, [ea.encodePtxt(np.broadcast_to(C[j], (1, ea.size(), d))) for j in range(d)])
+    return slot_ring.applyLinPoly1(ea, ct, C)
 
 
 def applyLinPolyMany(ea, ct, Cvec):
     """another map in every slot (:826-850): Cvec [nslots, d, d], row i from buildLinPolyCoeffs for slot i"""
     _check(ea)
-    return _applyLinPolyMany(ea, ct, Cvec)
-
-
-def _applyLinPolyMany(ea, ct, Cvec):
-    d = ea.getDegree()
-    Cvec = np.asarray(Cvec, dtype=np.int64)
-    if Cvec.shape != (ea.size(), d, d):
-        raise LogicError("Number of slots does not match size of Cvec, or an entry's size is unequal to the degree of ea")
-    return applyLinPolyLL(ct, [ea.encodePtxt(Cvec[None, :, j, :]) for j in range(d)])
+    return slot_ring.applyLinPolyMany(ea, ct, Cvec)

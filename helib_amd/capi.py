@@ -942,19 +942,19 @@ def bgvGfLinalgTables(p, d, G):
     """The host tables of linear maps on GF(p^d) slots (hx_bgv_gf_linalg_tables): frob [d, d, d] with frob[e][l] =
     X^(l p^e) mod G, K [d, d, d] with K[j][k] the entries of the inverse of M[i][j] = (X^j)^(p^i), and the flat table
     T [d^2, d^2] of buildLinPolyCoeffs; uint32."""
-    d = int(d)
-    g = (C.c_uint64 * (d + 1))(*[int(x) for x in G])
-    frob, K, T = (np.zeros(max(d, 1) ** e, dtype=np.uint32) for e in (3, 3, 4))
-    _chk(lib().hx_bgv_gf_linalg_tables(int(p), d, g, _p(frob), _p(K), _p(T)))
-    return frob.reshape(d, d, d), K.reshape(d, d, d), T.reshape(d * d, d * d)
+    return _linalgTables(lib().hx_bgv_gf_linalg_tables, (int(p),), d, G)
 
 
 def bgvGrLinalgTables(p, r, d, G):
     """bgvGfLinalgTables modulo p^r over the lifted G (hx_bgv_gr_linalg_tables): frob, K and T over Z_(p^r); uint32."""
+    return _linalgTables(lib().hx_bgv_gr_linalg_tables, (int(p), int(r)), d, G)
+
+
+def _linalgTables(entry, ring, d, G):
     d = int(d)
     g = (C.c_uint64 * (d + 1))(*[int(x) for x in G])
     frob, K, T = (np.zeros(max(d, 1) ** e, dtype=np.uint32) for e in (3, 3, 4))
-    _chk(lib().hx_bgv_gr_linalg_tables(int(p), int(r), d, g, _p(frob), _p(K), _p(T)))
+    _chk(entry(*ring, d, g, _p(frob), _p(K), _p(T)))
     return frob.reshape(d, d, d), K.reshape(d, d, d), T.reshape(d * d, d * d)
 
 

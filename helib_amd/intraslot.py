@@ -14,7 +14,8 @@ the call sequence or, fused, one hx_mul_add_circulant.
   normalBasisMatrices(ea, normal_element=None) -> (CB, CBi)     EncryptedArrayDerived::initNormalBasisMatrix
                       (src/EncryptedArray.cpp:488-550): CB[i] = the coordinates of sigma^i(theta), CBi its inverse mod
                       p^r (ppInvert: here Gauss-Jordan with unit pivots)
-  buildLinPolyCoeffs(ea, L)         EncryptedArrayDerived::buildLinPolyCoeffs (:740-790) over the Galois ring
+  buildLinPolyCoeffs(ea, L) / applyLinPolyPlain(ea, C, a)       EncryptedArrayDerived::buildLinPolyCoeffs (:740-790)
+                      and the map it describes, over the Galois ring: helib_amd.slot_ring's behind this module's check
   buildUnpackSlotEncoding(ea)       :34-60
   unpack / unpackMany / repack / repackMany                     :78-160, :171-230
   packConstant / packConstants / unpackSlots                    :242-372
@@ -30,17 +31,14 @@ polynomials (normal elements are dense: a failure that late means the rule does 
 LogicError (pass normal_element= then).  normal_element= injects a theta, for example the one of a genuine HElib run; one that is
 not normal is refused.  Any normal theta gives a valid unpack / repack pair; the coordinates depend on it.
 
+The arithmetic of a slot (the product mod G, sigma, matrices mod p^r, the inverse Moore matrix) is helib_amd.slot_ring.
 Keys: helib_amd.keys.addFrbMatrices.  Nothing here imports oracle/."""
 import numpy as np
 
-from . import bgv_gf, bgv_gr
+from . import bgv_gf, bgv_gr, slot_ring
 from . import ctxt as hc
 from .ckks import LogicError
-
-
-# ---- arithmetic modulo p^r ----
-def _modulus(ea):
-    return int(getattr(ea, "P", ea.p))
+from .slot_ring import _invmod, _matmod, _tables  # noqa: F401  (_tables: the tests read frob and K through this module)
 
 
 def _check(ea):
@@ -48,50 +46,10 @@ def _check(ea):
         raise LogicError("intraslot takes helib_amd.bgv_gf.EncryptedArray or helib_amd.bgv_gr.EncryptedArray")
 
 
-def _matmod(a, b, P):
-    """a @ b mod P, through Python integers when the sums could leave int64"""
-    a, b = np.asarray(a, dtype=np.int64) % P, np.asarray(b, dtype=np.int64) % P
-    if P * P * max(1, a.shape[-1]) < 2 ** 63:
-        return a @ b % P
-    return np.array((a.astype(object) @ b.astype(object)) % P, dtype=np.int64)
-
-
-def _invmod(a, p, P):
-    """the inverse of a square matrix modulo P = p^r by Gauss-Jordan on Python integers, every pivot a unit (non-zero
-    mod p: one exists in each column exactly when the matrix is invertible mod p); None when it is singular mod p"""
-    n = a.shape[0]
-    w = np.concatenate([np.asarray(a).astype(object) % P, np.eye(n, dtype=object)], axis=1)
-    for c in range(n):
-        piv = next((r for r in range(c, n) if int(w[r, c]) % p), None)
-        if piv is None:
-            return None
-        if piv != c:
-            w[[c, piv]] = w[[piv, c]]
-        w[c] = w[c] * pow(int(w[c, c]), -1, P) % P
-        for r in range(n):
-            if r != c and w[r, c]:
-                w[r] = (w[r] - w[r, c] * w[c]) % P
-    return np.array(w[:, n:], dtype=np.int64)
-
-
-def _mul(ea, a, b):
-    """the product in Z_(p^r)[X] / G of arrays [..., d] (ea._mul takes three axes)"""
-    a, b = np.asarray(a, dtype=np.int64), np.asarray(b, dtype=np.int64)
-    shape = np.broadcast_shapes(a.shape, b.shape)
-    d = shape[-1]
-    a, b = np.broadcast_to(a, shape).reshape(1, -1, d), np.broadcast_to(b, shape).reshape(1, -1, d)
-    return ea._mul(a, b).reshape(shape)
-
-
-def _sigma(ea):
-    """S [d, d]: sigma(alpha) = alpha S as row vectors (row l = X^(l p) mod G)"""
-    return np.asarray(ea._frobenius(), dtype=np.int64) % _modulus(ea)
-
-
 # ---- the normal basis ----
 def _conjugates(ea, theta):
-    P, d = _modulus(ea), ea.getDegree()
-    S = _sigma(ea)
+    P, d = ea.P, ea.getDegree()
+    S = ea._frobenius()                                             # sigma(alpha) = alpha S as row vectors
     rows = [np.asarray(theta, dtype=np.int64) % P]
     for _ in range(1, d):
         rows.append(_matmod(rows[-1][None, :], S, P)[0])
@@ -114,7 +72,7 @@ def normalBasisMatrices(ea, normal_element=None):
     first normal candidate of the module's rule: X^0, ..., X^(d-1), then the {0, 1} polynomials in increasing integer
     order.  The rule's result is cached on ea."""
     _check(ea)
-    p, P, d = ea.p, _modulus(ea), ea.getDegree()
+    p, P, d = ea.p, ea.P, ea.getDegree()
     if normal_element is not None:
         theta = [int(x) % P for x in normal_element]
         if len(theta) > d:
@@ -140,76 +98,23 @@ def normalBasisMatrices(ea, normal_element=None):
 
 
 # ---- linearized polynomials over the Galois ring ----
-class _Tables:
-    """frob[e][l] = sigma^e(X^l); M[i][j] = sigma^i(X^j) = frob[i][j] (buildLinPolyMatrix, a Moore matrix); K = M^-1 over
-    the ring, K[j][k] = sigma^k(beta_j) with beta the dual basis of the powers of X under the trace Tr = sum_e sigma^e
-    ((K M)[j][j'] = sum_k sigma^k(beta_j X^j') = Tr(beta_j X^j')); beta = the inverse of the Gram matrix Tr(X^(i + j))
-    over Z_(p^r), which is invertible because it is invertible mod p (the route of bgv_gf_matmul._Tables)"""
-
-    def __init__(self, ea):
-        p, P, d = ea.p, _modulus(ea), ea.getDegree()
-        S = _sigma(ea)
-        self.frob = np.zeros((d, d, d), dtype=np.int64)
-        self.frob[0] = np.eye(d, dtype=np.int64)
-        for e in range(1, d):
-            self.frob[e] = _matmod(self.frob[e - 1], S, P)
-        tr = self.frob[:, :, 0].sum(axis=0) % P                     # Tr(X^l) = sum_e [X^0] sigma^e(X^l), l < d
-        x = np.zeros(d, dtype=np.int64)
-        x[0] = 1
-        step = np.zeros(d, dtype=np.int64)
-        if d > 1:
-            step[1] = 1
-        pw = []
-        for _ in range(2 * d - 1):                                  # X^s mod G, s <= 2 d - 2
-            pw.append(x)
-            x = _mul(ea, x, step) if d > 1 else x
-        trs = _matmod(np.stack(pw), tr[:, None], P)[:, 0]
-        gram = np.array([[trs[i + j] for j in range(d)] for i in range(d)], dtype=np.int64)
-        beta = _invmod(gram, p, P)
-        if beta is None:
-            raise LogicError("internal: the Gram matrix of traces is singular mod p")
-        self.K = np.stack([np.stack([_matmod(beta[j][None, :], self.frob[k], P)[0] for k in range(d)]) for j in range(d)])
-
-
-def _tables(ea):
-    t = ea.__dict__.get("_intraslot_linpoly")
-    if t is None:
-        t = ea.__dict__["_intraslot_linpoly"] = _Tables(ea)
-    return t
-
-
 def buildLinPolyCoeffs(ea, L):
     """EncryptedArrayDerived::buildLinPolyCoeffs over Z_(p^r)[X] / G: L [..., d, d], row j the coefficients of the image
-    of X^j -> C [..., d, d], row k the coefficients of C[k] = sum_j L[j] K[j][k]; the Z_(p^r)-linear map is
-    alpha -> sum_k C[k] sigma^k(alpha).  At r = 1 it is helib_amd.bgv_gf_matmul.buildLinPolyCoeffs."""
+    of X^j -> C [..., d, d], row k the coefficients of C[k]; the Z_(p^r)-linear map is alpha -> sum_k C[k] sigma^k(alpha)"""
     _check(ea)
-    P, d = _modulus(ea), ea.getDegree()
-    L = np.asarray(L, dtype=np.int64) % P
-    if L.ndim < 2 or L.shape[-2:] != (d, d):
-        raise LogicError("buildLinPolyCoeffs takes [..., d, d] with d = %d" % d)
-    K = _tables(ea).K
-    Lf = L.reshape(-1, d, d)
-    C = np.zeros_like(Lf)
-    for k in range(d):
-        C[:, k, :] = _mul(ea, Lf, K[None, :, k, :]).sum(axis=1) % P
-    return C.reshape(L.shape)
+    return slot_ring.buildLinPolyCoeffs(ea, L)
 
 
 def applyLinPolyPlain(ea, C, a):
     """sum_k C[k] sigma^k(alpha) in every slot of a: C [d, d], a slots -> int64 [B, nslots, d]"""
-    P, d = _modulus(ea), ea.getDegree()
-    a = ea._slots(a) % P
-    out = np.zeros_like(a)
-    for k in range(d):
-        out = (out + _mul(ea, np.asarray(C[k], dtype=np.int64) % P, ea.frobeniusPlain(a, k))) % P
-    return out
+    return slot_ring.evalLinPoly(ea, C, a)
 
 
 # ---- the plain side ----
 def unpackPlain(ea, a, normal_element=None):
     """slots a [B, nslots, d] -> int64 [B, nslots, d]: the normal-basis coordinates c_i of every slot (alpha CBi)"""
     _check(ea)
-    P = _modulus(ea)
+    P = ea.P
     CBi = normalBasisMatrices(ea, normal_element)[1]
     return _matmod(ea._slots(a) % P, CBi, P)
 
@@ -217,7 +122,7 @@ def unpackPlain(ea, a, normal_element=None):
 def repackPlain(ea, c, normal_element=None):
     """coordinates c [B, nslots, <= d] -> the slots sum_i c_i sigma^i(theta) (c CB)"""
     _check(ea)
-    P = _modulus(ea)
+    P = ea.P
     CB = normalBasisMatrices(ea, normal_element)[0]
     return _matmod(ea._slots(c) % P, CB, P)
 
@@ -226,7 +131,7 @@ def _int2Poly(ea, CB, data, nbits):
     d = ea.getDegree()
     if not 0 <= nbits <= d:
         raise LogicError("Not enough capacity in slots or nbits less than 0 (0 <= nbits <= d = %d)" % d)
-    P = _modulus(ea)
+    P = ea.P
     acc = np.zeros(d, dtype=np.int64)
     for i in range(nbits):
         if (int(data) >> i) & 1:
