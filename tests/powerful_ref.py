@@ -140,3 +140,40 @@ def powerful_to_poly(cube, mvec, q):
     for i, x in enumerate(cube):
         tmp[ix.shortToExp[i]] = int(x) if q is None else int(x) % q
     return poly_rem(tmp, cyclotomic(ix.m), q)
+
+
+# ---- the factorisations of the device tests, and what their reductions consist of ----
+# (mvec, the prime p of the chain whose rows tests/test_evalmap_gpu.py converts): the first six are squarefree and odd;
+# then a prime power with e = 3 in a per-factor dimension, the factor 4 (m = 20: p = 3), e = 5, the factor 8 beside a
+# composite one (m = 120: p = 7), and four factors with a prime power among them (m = 4095)
+DEVICE_MVECS = [((3, 5), 2), ((3, 35), 2), ((7, 3, 65), 2), ((17, 257), 2), ((7, 3, 221), 2), ((31,), 2),
+                ((9, 5), 2), ((4, 5), 3), ((25, 3), 2), ((8, 15), 7), ((7, 5, 9, 13), 2)]
+MANY_ITEMS = [(3, 5), (7, 3, 221)]                          # converted with more items than the kernel has workgroups
+
+
+def reductions(mvec):
+    """the reductions modulo a cyclotomic polynomial that the two conversions make, from their definition:
+    (direction, n, phi(n), stride, nouter) -- to_powerful reduces, for each factor i, the fibres of length m_i and stride
+    prod_(j > i) m_j whose earlier coordinates are below their phi(m_j) (prod_(j < i) phi(m_j) x stride of them) modulo
+    Phi_(m_i); to_poly reduces one fibre of length m modulo Phi_m"""
+    ix = indexes(tuple(mvec))
+    out, stride, nouter = [], ix.m, 1
+    for n, ph in zip(ix.mvec, ix.phivec):
+        stride //= n
+        out.append(("to_powerful", n, ph, stride, nouter))
+        nouter *= ph
+    return out + [("to_poly", ix.m, ix.phim, 1, 1)]
+
+
+def remainder_steps(n):
+    """the steps of one remainder modulo Phi_n = prod_(e in num) (x^e - 1) / prod_(e in den) (x^e - 1) / (x^n - 1)^-1 of a
+    fibre of n words, as (half, op, e, L): the quotient from the reversed top n - phi(n) words, times the binomials of den
+    and divided by those of num; then quotient times Phi_n on phi(n) words, times num and divided by den, and one
+    subtraction.  A binomial whose e is not below L leaves the L words alone and is no step."""
+    num, den = binomials(n)
+    ph = phi(n)
+    Lq = n - ph
+    return ([("quotient", "REV", 0, Lq)] + [("quotient", "MUL", e, Lq) for e in den if e < Lq] +
+            [("quotient", "DIV", e, Lq) for e in num if e < Lq] + [("remainder", "REVW", n - 1 - ph, ph)] +
+            [("remainder", "MUL", e, ph) for e in num if e < ph] + [("remainder", "DIV", e, ph) for e in den if e < ph] +
+            [("remainder", "SUB", 0, ph)])

@@ -93,9 +93,9 @@ def prep_value(c, Q, q, p, p2r, p2e, ties):
     return dict(X=X, Y=Y, delta=delta, x0=x0, x=x, v=v, w=w, hit=hit)
 
 
-def prep(rows, primes, targets, q, p, p2r, p2e, seed, part):
+def prep(rows, primes, targets, q, p, p2r, p2e, seed, part, hits=None):
     """rows: [k, batch, n] residues -> x, v (int64 [batch, n]) and out ([|T|, batch, n] uint64), coefficient j of batch
-    element b taking tie_word(seed, part, b, j)"""
+    element b taking tie_word(seed, part, b, j).  hits: a dict that receives {(b, j): the branches that coefficient took}"""
     rows = np.asarray(rows)
     k, B, n = rows.shape
     Q = product(primes)
@@ -107,6 +107,8 @@ def prep(rows, primes, targets, q, p, p2r, p2e, seed, part):
             c = centred_lift([int(rows[i, b, j]) for i in range(k)], primes)
             R = prep_value(c, Q, q, p, p2r, p2e, tie_word(seed, part, b, j))
             x[b, j], v[b, j] = R["x"], R["v"]
+            if hits is not None:
+                hits[b, j] = R["hit"]
             for t, qt in enumerate(targets):
                 out[t, b, j] = R["w"] % qt
     return x, v, out
@@ -182,8 +184,9 @@ def params(key, k, nt=None):
     return src, tgt, p ** cc.e + 1, p, p ** r, p ** cc.ePrime
 
 
-def synthetic_rows(src, q, p, p2r, p2e, B, n, seed):
-    """[k, B, n] residues: the branch-hitting coefficients first, then random words over each row's whole range"""
+def synthetic_rows(src, q, p, p2r, p2e, B, n, seed, tail=False):
+    """[k, B, n] residues: the branch-hitting coefficients first, then random words over each row's whole range.
+    tail: the same coefficients once more in the last positions of the last batch element"""
     Q = product(src)
     cs = list(branch_inputs(Q, q, p, p2r, p2e).values())
     rng = np.random.default_rng(seed)
@@ -195,7 +198,94 @@ def synthetic_rows(src, q, p, p2r, p2e, B, n, seed):
     if B * n > len(cs) + 1:
         for i, s in enumerate(src):
             flat[i, len(cs)] = s - 1                                    # c = -1: the top of every row's range
+    if tail:
+        assert n >= 2 * len(cs) + 2                                     # (the two copies do not meet)
+        for pos, c in enumerate(cs):
+            for i, s in enumerate(src):
+                rows[i, B - 1, n - len(cs) + pos] = c % s
     return rows
+
+
+# ---- the tables of the kernel's tests, shared by the host replay and the device ----
+# past one workgroup of 256 threads: phi(m) = 256 (one full block), 300 (a last block of 44 words: less than one live
+# wave), 512 (two full blocks) and 576
+PAST_ONE_BLOCK = [(257, 2, 1), (341, 2, 1), (771, 2, 1), (1365, 2, 1)]
+BLOCK = 256                                                             # recrypt.hip's RC_T
+EVERY_K = tuple(range(1, 17))
+# (p, q, p2r, p2e) at the edges of what the plan admits: q and p2r just below 2^30, p2e = 1, p2e = q - 1, odd p with an
+# even q, p2r = p2e = p for a 15-bit p, and the smallest q there is
+EDGES = [(2, 2 ** 29 + 1, 2 ** 8, 2 ** 20), (2, 2 ** 29 + 1, 2 ** 29, 1), (2, 2 ** 29 + 1, 2, 2 ** 29),
+         (3, 3 ** 18 + 1, 3 ** 5, 3 ** 10), (7, 7 ** 10 + 1, 7 ** 3, 7 ** 6), (32749, 32749 ** 2 + 1, 32749, 32749), (2, 3, 2, 2)]
+EDGE_KS = (1, 4, 16)
+# the branches of prep_value that the three tables take between them.  (delta_at_half_Y_zero is not in the list: Y = 0
+# makes delta = Y Q^-1 = 0, so it cannot occur.)
+BRANCHES = {"Y_wrapped", "delta_above_half", "delta_at_half_Y_pos", "delta_at_half_Y_neg", "x_above", "x_below",
+            "x_at_plus_half_taken", "x_at_minus_half_taken", "z_above_half", "z_at_half"}
+
+
+class Case:
+    """one call of the kernel: the rows, the parameters and what tests/recryption_ref.py makes of them (computed once:
+    nobody writes to the arrays)"""
+
+    def __init__(self, cc, src_idx, tgt_idx, q, p, p2r, p2e, B, n, seed, part, rows_seed, tail=False):
+        self.cc, self.src_idx, self.tgt_idx = cc, list(src_idx), list(tgt_idx)
+        self.src, self.tgt = [cc.primes[i] for i in src_idx], [cc.primes[i] for i in tgt_idx]
+        self.q, self.p, self.p2r, self.p2e, self.B, self.n, self.seed, self.part = q, p, p2r, p2e, B, n, seed, part
+        self.rows = synthetic_rows(self.src, q, p, p2r, p2e, B, n, rows_seed, tail=tail)
+        self.hits = {}
+        self.want = prep(self.rows, self.src, self.tgt, q, p, p2r, p2e, seed, part, hits=self.hits)
+        for a in (self.rows,) + self.want:
+            a.setflags(write=False)
+
+    @property
+    def args(self):
+        return self.q, self.p, self.p2r, self.p2e, self.seed, self.part
+
+    def branches(self):
+        return set().union(*self.hits.values())
+
+
+def sixteen_rows(k=16):
+    """the chain with the most rows and the indices of its first k (ciphertext primes, then special primes)"""
+    cc = chain(85, 2, 1, True, 1000)
+    idx = (list(cc.ctxtPrimes) + list(cc.specialPrimes))[:k]
+    assert len(idx) == k
+    return cc, idx
+
+
+@functools.lru_cache(maxsize=None)
+def past_one_block_case(key, seed_offset=0):
+    """batch 2, k = 3, every prime of the chain a target; the branch inputs at the front of batch element 0 and at the end
+    of batch element 1"""
+    cc = chain(*key)
+    m, p, r = key
+    return Case(cc, list(cc.ctxtPrimes)[:3], range(len(cc.primes)), p ** cc.e + 1, p, p ** r, p ** cc.ePrime, 2, cc.phim,
+                0xB10C + m + seed_offset, m % 2, m, tail=True)
+
+
+def tie_positions(case):
+    """the (b, j) whose output a tie bit decides"""
+    return sorted(at for at, hit in case.hits.items() if hit & {"z_at_half", "x_at_half"})
+
+
+@functools.lru_cache(maxsize=None)
+def every_k_case(k):
+    """batch 2, two targets, the seed and the part varying with k"""
+    cc, idx = sixteen_rows(k)
+    return Case(cc, idx, sixteen_rows(2)[1], 2 ** cc.e + 1, 2, 2, 2 ** cc.ePrime, 2, cc.phim, 0xE7E2 + 977 * k + (k << 59), k % 3,
+                100 + k)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_case(which, k):
+    """EDGES[which] on the first k rows of the same chain, or None where Q shares a factor with q (the kernel refuses
+    that)"""
+    from math import gcd
+    cc, idx = sixteen_rows(k)
+    p, q, p2r, p2e = EDGES[which]
+    if gcd(product(cc.primes[i] for i in idx) % q, q) != 1:
+        return None
+    return Case(cc, idx, sixteen_rows(2)[1], q, p, p2r, p2e, 2, cc.phim, 0xED6E + 31 * which + k, (which + k) % 2, 1000 * which + k)
 
 
 # ---- the whole reCrypt over the CPU oracle backend ----

@@ -1,6 +1,13 @@
 """The powerful basis, the slot tables over supplied generators and EvalMap on the device (powerful_kernel,
 hx_bgv_gf_create_gens, helib_amd.powerful, helib_amd.evalmap) against tests/powerful_ref.py, the CPU tables of
-tests/evalmap_tables.py and numpy on slot arrays.  Everything here is an integer: every comparison is exact."""
+tests/evalmap_tables.py and numpy on slot arrays.  Everything here is an integer: every comparison is exact.
+
+The shapes of the conversion tests: eleven factorisations (tests/powerful_ref.py: DEVICE_MVECS -- squarefree and odd ones
+from 8 words to m = 4641, then (9, 5), (4, 5), (25, 3), (8, 15) and (7, 5, 9, 13)) at 9 rows x batch 3, one item per
+workgroup; (3, 5) and (7, 3, 221) at 3 rows x batch 100 and as 300, 1 and 301 rows of host words, where the 256
+workgroups walk to a second item with another row's modulus and the buffers of the table grow twice.
+tests/test_evalmap_host.py::test_census_of_the_division_passes_the_device_tests_run says which forms of the passes these
+reach."""
 import ctypes as C
 import functools
 
@@ -30,7 +37,10 @@ def hx():
 # (3, 5): 8 words, less than a wave; (3, 35): Phi_105 has a coefficient -2 and m - 1 - phi(m) > phi(m); (7, 3, 65): three
 # dimensions; (17, 257): the e = 1 scan over 4369 words, m - 1 - phi(m) < phi(m); (7, 3, 221): fifteen binomials, a composite
 # factor; (31): the single-factor identity
-MVECS = [(3, 5), (3, 35), (7, 3, 65), (17, 257), (7, 3, 221), (31,)]
+# (9, 5), (25, 3): e > 1 in a per-factor dimension; (4, 5), (8, 15): m even, and a factor whose reduction has no binomial
+# pass at all; (7, 5, 9, 13): m = 4095, four factors.  The chain of a row test is over p = 2 where m is odd, p = 3 at
+# m = 20 and p = 7 at m = 120.
+MVECS = [mvec for mvec, _ in PR.DEVICE_MVECS]
 WORD_MODULI = (2, 49, (1 << 62) - 57)
 
 
@@ -49,11 +59,11 @@ def _mod(rows, q):
     return np.array([[int(x) % q for x in r] for r in rows], dtype=np.uint64)
 
 
-@pytest.mark.parametrize("mvec", MVECS)
-def test_rows_of_a_poly_convert_as_the_definition_does(hx, mvec):
+@pytest.mark.parametrize("mvec,p", PR.DEVICE_MVECS, ids=["mvec%d" % i for i in range(len(PR.DEVICE_MVECS))])
+def test_rows_of_a_poly_convert_as_the_definition_does(hx, mvec, p):
     from helib_amd import ctxt as hc, powerful as PW
     m = int(np.prod(mvec))
-    cc = hc.ChainContext(m, 2, 1, bits=100, c=2)
+    cc = hc.ChainContext(m, p, 1, bits=100, c=2)
     g = hx.Context(m)
     for q in cc.primes:
         g.add_prime(q)
@@ -100,6 +110,85 @@ def test_words_modulo_any_q(hx, mvec):
     # any int64 is reduced first
     q = 49
     assert np.array_equal(dev.polyToPowerful(np.array(ins[1:2], dtype=np.int64), q), _mod(cubes[1:2], q).astype(np.int64))
+
+
+# ---- (f') more items than workgroups ----
+# 300 items on a grid of 256: workgroups 0..43 take a second item, of another row (another modulus) and other data, into
+# buffers that hold the first one's cube and ping-pong pair
+Q62 = (1 << 62) - 57
+
+
+def _bulk(mvec, primes, batch):
+    """[rows, batch, phi(m)] words over each row's whole range with the three inputs of _truth at items 0, 1, 2 and
+    256, 257, 258; -> (rows, {(row, b): which input})"""
+    n = PR.indexes(mvec).phim
+    rng = np.random.default_rng(n + batch)
+    rows = np.stack([rng.integers(0, q, size=(batch, n), dtype=np.uint64) for q in primes])
+    ins = _truth(mvec)[0]
+    where = {}
+    for item in (0, 1, 2, 256, 257, 258):
+        r, b = divmod(item, batch)
+        rows[r, b] = _mod(ins, primes[r])[item % 256]
+        where[r, b] = item % 256
+    return rows, where
+
+
+@pytest.mark.parametrize("mvec", PR.MANY_ITEMS)
+def test_more_items_than_workgroups(hx, mvec):
+    from helib_amd import ctxt as hc, powerful as PW
+    m = int(np.prod(mvec))
+    cc = hc.ChainContext(m, 2, 1, bits=100, c=2)
+    g = hx.Context(m)
+    for q in cc.primes:
+        g.add_prime(q)
+    host = PW.PowerfulConversion(mvec)                                   # the numpy form: no device
+    ins, cubes, polys = _truth(mvec)
+    pd = PW.PowerfulDCRT(g, mvec)
+    # one row first, then three, then all on the same tables: the moduli's buffer grows twice
+    one = hx.DoubleCRT(g, [1], 3, data=_mod(ins, cc.primes[1])[None])
+    pd.dcrtToPowerful(one)
+    assert np.array_equal(one.download()[0], _mod(cubes, cc.primes[1]))
+    idx, B = [0, 4, 8], 100
+    primes = [cc.primes[i] for i in idx]
+    assert len(set(primes)) == 3 and len(idx) * B == 300 > 256 and all(q < 1 << 62 for q in primes)
+    rows, where = _bulk(mvec, primes, B)
+    assert sorted(where) == [(0, 0), (0, 1), (0, 2), (2, 56), (2, 57), (2, 58)]     # items i and i + 256: rows 0 and 2
+    want_cube = np.stack([host.polyToPowerful(rows[r].astype(np.int64), q) for r, q in enumerate(primes)]).astype(np.uint64)
+    want_poly = np.stack([host.powerfulToPoly(rows[r].astype(np.int64), q) for r, q in enumerate(primes)]).astype(np.uint64)
+    assert not np.array_equal(want_cube[0, :3], want_cube[2, 56:59])
+    a = hx.DoubleCRT(g, idx, B, data=rows)
+    pd.dcrtToPowerful(a)
+    got = a.download()
+    for (r, b), i in where.items():                                      # the definition itself, on both trips
+        assert np.array_equal(got[r, b], _mod(cubes[i:i + 1], primes[r])[0]), (r, b)
+    assert np.array_equal(got, want_cube)
+    pd.powerfulToDCRT(a)
+    assert np.array_equal(a.download(), rows)                            # the round trip
+    pd.powerfulToDCRT(a)
+    got = a.download()
+    for (r, b), i in where.items():
+        assert np.array_equal(got[r, b], _mod(polys[i:i + 1], primes[r])[0]), (r, b)
+    assert np.array_equal(got, want_poly)
+    pd.dcrtToPowerful(a)
+    assert np.array_equal(a.download(), rows)
+    everything = list(range(len(cc.primes)))
+    full = hx.DoubleCRT(g, everything, 3, data=np.stack([_mod(ins, q) for q in cc.primes]))
+    pd.dcrtToPowerful(full)
+    assert np.array_equal(full.download(), np.stack([_mod(cubes, q) for q in cc.primes]))
+    # host words: batch 300, then 1, then 301 through one handle -- its buffer grows, is reused for less, grows again
+    t = hx.Powerful(g, mvec)
+    w, where = _bulk(mvec, [Q62], 301)
+    w = w[0].astype(np.int64)
+    want = host.polyToPowerful(w, Q62)
+    back = host.powerfulToPoly(w, Q62)
+    for n_items in (300, 1, 301):
+        got = hx.powerfulWords(t, w[:n_items], Q62, True)
+        assert np.array_equal(got, want[:n_items]), n_items
+        assert np.array_equal(hx.powerfulWords(t, got, Q62, False), w[:n_items]), n_items
+        assert np.array_equal(hx.powerfulWords(t, w[:n_items], Q62, False), back[:n_items]), n_items
+    for (_, b), i in where.items():
+        assert np.array_equal(want[b], _mod(cubes[i:i + 1], Q62)[0].astype(np.int64))
+        assert np.array_equal(back[b], _mod(polys[i:i + 1], Q62)[0].astype(np.int64))
 
 
 def test_powerful_refusals(hx):

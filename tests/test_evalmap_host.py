@@ -18,7 +18,9 @@ from tests import powerful_ref as PR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "powerful_dump.cpp")
-MVECS = [(3, 5), (3, 35), (3, 19), (7, 3, 65), (17, 257), (7, 3, 221), (31,)]
+# the last five are not squarefree or not odd: e > 1 in a per-factor dimension, and the factors 4 and 8, whose reduction
+# is a reversal, a copy and a subtraction (no binomial of theirs is short enough to act)
+MVECS = [(3, 5), (3, 35), (3, 19), (7, 3, 65), (17, 257), (7, 3, 221), (31,), (9, 5), (4, 5), (25, 3), (8, 15), (7, 5, 9, 13)]
 Q60 = (1 << 60) - 93                                                    # a 60-bit prime
 MODULI = (2, 49, Q60)
 
@@ -106,13 +108,66 @@ def test_the_pass_list_converts_as_the_definition_does(mvec):
 
 
 def test_the_replay_is_clean_under_the_sanitizers():
-    for mvec in ((3, 35), (7, 3, 65), (17, 257), (31,)):
+    for mvec in ((3, 35), (7, 3, 65), (17, 257), (31,), (9, 5), (4, 5), (7, 5, 9, 13)):
         q = Q60
         rows = _rows(mvec, q)
         assert _run(["tables", *mvec], sanitize=True) == _run(["tables", *mvec])
         cubes = _convert(mvec, q, True, rows, sanitize=True)
         assert cubes == [PR.poly_to_powerful(r, mvec, q) for r in rows]
         assert _convert(mvec, q, False, cubes, sanitize=True) == rows
+
+
+def test_census_of_the_division_passes_the_device_tests_run():
+    """Which forms of the "divide by 1 - x^e" pass, and which degenerate pass lists, the factorisations of
+    tests/test_evalmap_gpu.py reach between them -- derived from the definition of the conversions
+    (tests/powerful_ref.py: reductions, remainder_steps), with the kernel's figures restated: a workgroup of 1024 threads;
+    chains = fibres x e running sums; at 1024 chains or more a thread walks a chain, below that a chain is cut into
+    S = floor(1024 / chains) segments and the threads past S x chains idle."""
+    from tests import test_evalmap_gpu as G
+    T = 1024
+    assert [mv for mv, _ in PR.DEVICE_MVECS] == G.MVECS and set(MVECS) >= set(G.MVECS)
+    seen = set()
+    for mvec in G.MVECS:
+        counts = {"to_powerful": 0, "to_poly": 0}
+        for direction, n, ph, stride, nouter in PR.reductions(mvec):
+            steps = PR.remainder_steps(n)
+            counts[direction] += len(steps)
+            acting = [st for st in steps if st[1] in ("MUL", "DIV")]
+            if not any(st[1] == "DIV" for st in acting if st[0] == "quotient"):
+                seen.add("no DIV in the quotient half")
+            if not acting:
+                seen.add("a reduction without MUL or DIV: n = %d" % n)
+            for half, op, e, L in steps:
+                if op != "DIV":
+                    continue
+                assert 1 <= e < L <= n
+                chains = nouter * stride * e
+                if direction == "to_powerful" and e > 1 and len(PR.binomials(n)[1]) == 1:
+                    seen.add("e > 1 in the dimension of a prime power")
+                if chains >= T:
+                    seen.add("a thread walks a chain")
+                    continue
+                S = T // chains
+                longest = -(-L // e)                                     # the words of the longest chain
+                if S == 1 and T - chains > 0:
+                    seen.add("S = 1 with an idle tail")
+                if S > longest:
+                    seen.add("more segments than words")
+                if S == T:
+                    seen.add("one chain: the scan of a single fibre")
+                if 1 < S <= longest and T - S * chains > 0:
+                    seen.add("segments of several words with an idle tail")
+        # the pass list that the kernel runs has exactly these steps (tests/cpp/powerful_dump.cpp prints its lengths)
+        assert _run(["tables", *mvec])[-1].split() == ["passes", str(counts["to_powerful"]), str(counts["to_poly"])], mvec
+    assert seen == {"no DIV in the quotient half", "a reduction without MUL or DIV: n = 4", "a reduction without MUL or DIV: n = 8",
+                    "e > 1 in the dimension of a prime power", "a thread walks a chain", "S = 1 with an idle tail",
+                    "more segments than words", "one chain: the scan of a single fibre",
+                    "segments of several words with an idle tail"}, sorted(seen)
+    # the two that tests/test_evalmap_gpu.py converts with more items than workgroups: the smallest, and the one that
+    # walks chains
+    assert PR.MANY_ITEMS == [G.MVECS[0], (7, 3, 221)] and min(G.MVECS, key=lambda mv: PR.indexes(mv).m) == (3, 5)
+    assert any(nouter * stride * e >= T for _, n, _, stride, nouter in PR.reductions((7, 3, 221))
+               for _, op, e, _ in PR.remainder_steps(n) if op == "DIV")
 
 
 def test_bad_factorisations_are_refused():

@@ -1,7 +1,13 @@
 """The pre-processing of recryption on the device: recrypt_prep_kernel (hx_recrypt_prep) against tests/recryption_ref.py on
 synthetic rows and on the inputs built for every branch, its refusals, and helib_amd.recryption.rawModSwitch of a real
 ciphertext against the same restatement applied to the downloaded parts.  Everything here is an integer: every
-comparison is exact."""
+comparison is exact.
+
+The shapes of the kernel tests: phi(m) = 8, 36, 48 and 64 (one workgroup, partly idle) at k = 1, 3, 5 and batch 1 and 3;
+phi(m) = 256, 300, 512 and 576 at batch 2 (one full workgroup, a second one of 44 words, two and three workgroups, the
+ties of batch element 1 decided at j >= 256); every k from 1 to 16, and 17 refused; seven parameter sets at the edges of
+what the plan admits (q and p^r just below 2^30, p^e' = 1 and q - 1, odd p, q = 3) at k = 1, 4 and 16.  The tables of the
+last three are tests/recryption_ref.py's, which tests/test_recryption_host.py replays on the CPU."""
 import ctypes as C
 
 import numpy as np
@@ -79,6 +85,67 @@ def test_kernel_takes_sixteen_rows(hx):
     idx17 = (list(cc.ctxtPrimes) + list(cc.specialPrimes))[:17]
     with pytest.raises(hx.HxError, match="17 rows"):
         hx.recryptPrep(hx.DoubleCRT(g, idx17, 1), idx[:2], q, p, p2r, p2e, 5, 1)
+
+
+def _run_case(hx, g, case):
+    """one call with the debug arrays: x, v and every output row are the restatement's, and the input is left alone"""
+    a = hx.DoubleCRT(g, case.src_idx, case.B, data=case.rows)
+    out, x, v = hx.recryptPrep(a, case.tgt_idx, *case.args, debug=True)
+    assert np.array_equal(x, case.want[0]) and np.array_equal(v, case.want[1])
+    assert np.array_equal(out.download(), case.want[2])
+    assert out.getIndexSet() == case.tgt_idx and np.array_equal(a.download(), case.rows)
+    return a
+
+
+# more than one workgroup of 256 threads: blockIdx.x > 0, the guard of a partly idle last workgroup, the tie words of
+# j >= 256, and batch element 1 in a workgroup that is not the first
+@pytest.mark.parametrize("key", RR.PAST_ONE_BLOCK)
+def test_kernel_past_one_block(hx, key):
+    case = RR.past_one_block_case(key)
+    n = case.n
+    assert n == {257: 256, 341: 300, 771: 512, 1365: 576}[key[0]] and case.B == 2 and len(case.src) == 3
+    assert len(case.tgt) == len(case.cc.primes)
+    # a tie decides an output of batch element 1 past the first workgroup (at phi(m) = 256: in its last wave), and the
+    # reference there does follow the seed
+    ties = [at for at in RR.tie_positions(case) if at[0] == 1 and at[1] >= (RR.BLOCK if n > RR.BLOCK else n - 64)]
+    assert ties and ties[-1][1] >= n - 2
+    other = RR.past_one_block_case(key, 1)
+    assert np.array_equal(other.rows, case.rows) and other.seed == case.seed + 1
+    assert any(other.want[1][at] != case.want[1][at] or other.want[0][at] != case.want[0][at] for at in ties)
+    g = _context(hx, case.cc)
+    assert g.phim == n
+    a = _run_case(hx, g, case)
+    got = hx.recryptPrep(a, case.tgt_idx, *other.args, debug=True)
+    assert np.array_equal(got[1], other.want[0]) and np.array_equal(got[2], other.want[1])
+    assert np.array_equal(got[0].download(), other.want[2])
+
+
+# every instantiation of the kernel and every case of the dispatch in hx_recrypt_prep
+def test_kernel_at_every_k(hx):
+    g = _context(hx, RR.sixteen_rows()[0])
+    for k in RR.EVERY_K:
+        case = RR.every_k_case(k)
+        assert len(case.src) == k and case.B == 2 and len(case.tgt) == 2 and case.n == g.phim == 64
+        try:
+            _run_case(hx, g, case)
+        except AssertionError as e:
+            raise AssertionError("k = %d" % k) from e
+    assert len({RR.every_k_case(k).seed for k in RR.EVERY_K}) == 16 and {RR.every_k_case(k).part for k in RR.EVERY_K} == {0, 1, 2}
+
+
+# the edges of the range that build_plan admits, where the bounds of recrypt_core.h are stated
+@pytest.mark.parametrize("which", range(len(RR.EDGES)))
+def test_kernel_at_the_edges_of_the_plan(hx, which):
+    g = _context(hx, RR.sixteen_rows()[0])
+    for k in RR.EDGE_KS:
+        case = RR.edge_case(which, k)
+        if case is None:                                                 # Q shares a factor with this q: refused, and
+            continue                                                     # tests/test_recryption_host.py counts these
+        assert (case.p, case.q, case.p2r, case.p2e) == RR.EDGES[which] and len(case.src) == k and case.B == 2
+        try:
+            _run_case(hx, g, case)
+        except AssertionError as e:
+            raise AssertionError("k = %d" % k) from e
 
 
 # ---- (b) the refusals of the C entry ----

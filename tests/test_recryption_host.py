@@ -219,6 +219,65 @@ def test_the_core_header_takes_sixteen_rows():
         assert np.array_equal(g, w)
 
 
+def _replay_case(case):
+    got = replay(case.src, case.tgt, *case.args, case.rows)
+    assert not isinstance(got, str), got
+    for g, w in zip(got, case.want):
+        assert g.dtype == w.dtype and np.array_equal(g, w)
+
+
+# the tables of tests/test_recryption_gpu.py, word for word through the same header
+@pytest.mark.parametrize("key", RR.PAST_ONE_BLOCK)
+def test_the_core_header_replays_the_rows_past_one_block(key):
+    case = RR.past_one_block_case(key)
+    assert case.n >= RR.BLOCK and case.B == 2
+    _replay_case(case)
+    _replay_case(RR.past_one_block_case(key, 1))                        # the other seed
+
+
+def test_the_core_header_replays_every_k():
+    for k in RR.EVERY_K:
+        case = RR.every_k_case(k)
+        assert len(case.src) == k
+        _replay_case(case)
+
+
+@pytest.mark.parametrize("which", range(len(RR.EDGES)))
+def test_the_core_header_replays_the_edges_of_the_plan(which):
+    p, q, p2r, p2e = RR.EDGES[which]
+    assert q < 1 << 30 and p2r < 1 << 30 and (q - 1) % p2e == 0 and math.gcd(q, p2r) == 1
+    for k in RR.EDGE_KS:
+        case = RR.edge_case(which, k)
+        if case is not None:
+            _replay_case(case)
+        else:                                                            # the plan refuses it, with the figures
+            cc, idx = RR.sixteen_rows(k)
+            src = [cc.primes[i] for i in idx]
+            out = replay(src, src[:1], q, p, p2r, p2e, 1, 0, np.zeros((k, 1, 2), dtype=np.uint64))
+            assert isinstance(out, str) and "gcd(Q mod q, q)" in out
+
+
+def test_the_tables_take_every_branch():
+    """which branches of the per-coefficient arithmetic the inputs of the three tables reach, stated, not hoped for"""
+    cases = [RR.past_one_block_case(key) for key in RR.PAST_ONE_BLOCK] + [RR.every_k_case(k) for k in RR.EVERY_K]
+    edges = [RR.edge_case(which, k) for which in range(len(RR.EDGES)) for k in RR.EDGE_KS]
+    assert len(edges) == 21 and sum(c is None for c in edges) <= 1      # at most one (parameter set, k) is refused
+    taken = set().union(*(c.branches() for c in cases + edges if c is not None))
+    assert RR.BRANCHES <= taken, sorted(RR.BRANCHES - taken)
+    assert "delta_at_half_Y_zero" not in taken                          # Y = 0 makes delta = 0
+    # at the edges: q = 2^29 + 1 with p2r = 2^29 and p2e = 2^29 spread x and v over 30 bits, so |q v| nears 2^58
+    big = RR.edge_case(2, 16)
+    assert int(np.abs(big.want[0]).max()) > 2 ** 27 and int(np.abs(big.want[1]).max()) * big.q > 2 ** 56
+    # past one block, a tie decides an output of batch element 1 at j >= 256 wherever the row is that long
+    for key in RR.PAST_ONE_BLOCK:
+        case = RR.past_one_block_case(key)
+        ties = [at for at in RR.tie_positions(case) if at[0] == 1 and at[1] >= RR.BLOCK]
+        assert bool(ties) == (case.n > RR.BLOCK), key
+        if ties:
+            other = RR.past_one_block_case(key, 1)
+            assert any(other.want[1][at] != case.want[1][at] or other.want[0][at] != case.want[0][at] for at in ties), key
+
+
 def test_the_plan_refuses_with_the_figures():
     src, tgt, q, p, p2r, p2e = params((85, 2, 1), 3, 1)
     rows = np.zeros((3, 1, 2), dtype=np.uint64)
