@@ -60,7 +60,7 @@ SYMBOLS = [
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
-    "hx_lin_comb", "hx_mul_add_circulant",
+    "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -169,6 +169,7 @@ def lib():
             "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
             "hx_lin_comb": [vp, vp, vp, vp, ip, vp, vp],
             "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
+            "hx_hoisted_automorph_sum": [vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -1177,6 +1178,29 @@ def linComb(in0, in1, idx, w, addend=None):
     _chk(lib().hx_lin_comb(out0.h, out1.h if out1 is not None else None, arr(in0), arr(in1) if in1 is not None else None,
                            n, _p(wa), _p(aa) if aa is not None else None))
     return out0, out1
+
+
+def hoistedAutomorphSum(digits, c0, c1, ks, Ws, special):
+    """The ciphertext (c0, c1) plus its images under the automorphisms ks, each key-switched by its own matrix of Ws
+    from the digit block of c1 (breakIntoDigits over `special`), in one pass (hx_hoisted_automorph_sum): the loop acc +=
+    BasicAutomorphPrecon.automorph(k) of traceMap (src/matmul.cpp:2878-2887).  -> (out0, out1), new DoubleCRTs on the
+    primes of c0 followed by special."""
+    if digits is None or c0 is None or c1 is None or ks is None or Ws is None:
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedAutomorphSum: digits, c0, c1, ks and Ws are required")
+    n = len(ks)
+    if n < 1 or len(Ws) != n:
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedAutomorphSum takes at least one automorphism, and one matrix for each")
+    ka = np.array([int(k) for k in ks], dtype=np.uint64)
+    sp = _i32(list(special))
+    idx = c0.getIndexSet() + [int(i) for i in sp]
+    out0 = DoubleCRT(c0.context, idx, c0.batch, zero=False)
+    out1 = DoubleCRT(c0.context, idx, c0.batch, zero=False)
+    wa = (C.c_void_p * n)(*[W.h for W in Ws])
+    _chk(lib().hx_hoisted_automorph_sum(digits.h, c0.h, c1.h, _p(ka), wa, n, _p(sp), len(sp), out0.h, out1.h))
+    return out0, out1
+
+
+hoistedSum = hoistedAutomorphSum    # the name helib_amd.ctxt looks for on a backend's ops
 
 
 def constantLike(poly, idx, num):

@@ -24,6 +24,9 @@ struct CtxView {
   void (**recrypt_free)(void*);
   const void* d_primes;       // the per-prime constants (hx::PrimeDev[], dev_common.h) on the device
   int device;
+  bool pow2;                  // m is a power of two
+  const uint32_t* d_zms;      // Z_m^* in increasing order, [phi(m)] (device) ...
+  const int32_t* d_zms_index; // ... and the position of every t in Z_m^* in it, [m] (device; -1 elsewhere)
 };
 // sets the device and fills v; the caller then takes *v->mu
 int ctx_enter(hx_ctx* c, CtxView* v);
@@ -33,6 +36,17 @@ int poly_rows_write(hx_poly* p, uint64_t** d);
 // p's rows are about to be read and rewritten in place: a shared slab is copied first
 int poly_rows_update(hx_poly* p, uint64_t** d);
 const uint64_t* poly_rows_read(const hx_poly* p);
+// p becomes a poly on the n primes idx whose rows are all about to be overwritten (the old rows are not kept)
+int poly_rows_reshape(hx_poly* p, const int* idx, int n, uint64_t** d);
+// a key-switching matrix: b and a are [ndig][nrows][phi(m)] words on the device, row r on prime row_idx[r]
+struct KskView {
+  hx_ctx* ctx;
+  int ndig, nrows;
+  const int* row_idx;
+  const uint64_t* d_b;
+  const uint64_t* d_a;
+};
+void ksk_view(const hx_ksk* k, KskView* v);
 // hx_poly_rem's arithmetic (toPoly + PolyRed(t), exact) with the result kept on the device: *d_out = [batch][phi(m)]
 // words in [0, t) in the context's scratch, valid until the next call on that context (hold its lock); a has rows
 int poly_rem_device(const hx_poly* a, uint64_t t, const uint64_t** d_out);

@@ -5310,6 +5310,9 @@ int ctx_enter(hx_ctx* c, CtxView* v)
   v->recrypt_free = &c->recrypt_free;
   v->d_primes = c->d_primes;
   v->device = c->device;
+  v->pow2 = c->pow2;
+  v->d_zms = c->d_zms;
+  v->d_zms_index = c->d_zms_index;
   return HX_OK;
 }
 hx_ctx* poly_ctx(const hx_poly* p) { return p ? p->ctx : nullptr; }
@@ -5328,6 +5331,24 @@ int poly_rows_update(hx_poly* p, uint64_t** d)
   return HX_OK;
 }
 const uint64_t* poly_rows_read(const hx_poly* p) { return p->d; }
+int poly_rows_reshape(hx_poly* p, const int* idx, int n, uint64_t** d)
+{
+  const uint64_t* old;
+  CHK(poly_fresh(p, &old));
+  CHK(poly_reserve(p, n, /*keep=*/false));
+  p->prime_idx.assign(idx, idx + n);
+  *d = p->d;
+  return HX_OK;
+}
+void ksk_view(const hx_ksk* k, KskView* v)
+{
+  v->ctx = k->ctx;
+  v->ndig = k->ndig;
+  v->nrows = (int)k->row_idx.size();
+  v->row_idx = k->row_idx.data();
+  v->d_b = k->d_b;
+  v->d_a = k->d_a;
+}
 int poly_rem_device(const hx_poly* a, uint64_t t, const uint64_t** d_out)
 {
   if (!a || !d_out || a->nrows() == 0 || t < 2 || t >= (1ull << 60))

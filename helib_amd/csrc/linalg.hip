@@ -17,8 +17,13 @@
 // term and one write of the sum; and of the inner loop of unpack (hx_mul_add_circulant):
 //   out[i] = sum_j c[(i + j) mod d] * in[j],  i < nout <= d
 // (src/intraSlot.cpp:108-115: unpacked[i] = frob[0] * C[i]; then += frob[j] * C[(i + j) mod d]), the d Frobenius images
-// read once per block of outputs instead of once per output.  The unit
-// reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows).
+// read once per block of outputs instead of once per output; and of the hoisted loop of traceMap
+// (hx_hoisted_automorph_sum):
+//   out = ctxt + sum_t keySwitch(sigma_k[t](ctxt)),  the digits of the s-part broken once
+// (src/matmul.cpp:2878-2887: acc += *precon.automorph(p^i)), every digit word and key word read once per term and the two
+// outputs written once.  The unit
+// reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
+// key-switching matrix's rows, the tables of Z_m^*).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -486,6 +491,102 @@ lin_comb_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, ro_u64
   }
 }
 
+// The hoisted trace sum (hx_hoisted_automorph_sum): per output row r, with sigma_t the gather of DoubleCRT::automorph
+// by k[t] (out[j] = in[perm_t[j]]),
+//   out0 = Psp (c0 + sum_t sigma_t(c0)) + sum_t sum_d sigma_t(dig_d) b[t][d],   out1 = Psp c1 + sum_t sum_d sigma_t(dig_d) a[t][d]
+// on the ciphertext's rows (r < L) and the two double sums alone on the special rows.
+//
+// hoisted_perm_kernel writes the n gather tables [n][N] uint32 once per call: perm_build_kernel's rule
+// (zms_index[zms[j] k mod m]) for a general m, gather_kernel's closed form for a power of two.  They are shared by every
+// row and batch element.
+__global__ void __launch_bounds__(256)
+hoisted_perm_kernel(uint32_t* __restrict__ perm, const uint32_t* __restrict__ zms, const int32_t* __restrict__ zms_index,
+                    uint32_t N, uint64_t m, ro_u64 ks, int pow2)
+{
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= N)
+    return;
+  const uint64_t k = ks[blockIdx.y];
+  uint32_t s;
+  if (pow2)
+    s = (uint32_t)(((((uint64_t)(2 * j + 1)) * k) & (m - 1)) >> 1);
+  else
+    s = (uint32_t)zms_index[((uint64_t)zms[j] * k) % m];
+  perm[(size_t)blockIdx.y * N + j] = s;
+}
+
+// Table (device, uint64 words): [0, n) the k[t] (hoisted_perm_kernel's); then per output row r and term t three words at
+// n + 3 (r n + t): the address of row r's words of digit 0 in b[t] and in a[t] and the words between two digits of that
+// matrix; behind them, at n + 3 rows n + r, Psp modulo the prime of row r.  It is read through the constant address space:
+// the entries are wave-uniform, so they are scalar loads.
+//
+// One thread owns one output coefficient j of one prime row for BP batch elements.  Per term it reads its gather index
+// once, per term and digit the two key words once (at j: coalesced, and kept for all BP elements) and BP digit words at
+// the gathered index (element-granular, through L2, as gather_kernel reads), and multiplies into 128-bit accumulators:
+// 1 + n + n ndig <= MAD_CHUNK products in out0's, so one reduction at the end is enough (the host checks the count).
+// No LDS: nothing is shared between threads.
+template <int BP>
+__global__ void __launch_bounds__(256)
+hoisted_sum_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, const uint64_t* __restrict__ dig,
+                   const uint64_t* __restrict__ c0, const uint64_t* __restrict__ c1, const uint32_t* __restrict__ perm,
+                   ro_u64 tab, int n, int ndig, int L, int nall, int batch, uint32_t N, MadRows map,
+                   const PrimeDev* __restrict__ primes)
+{
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t k = pd.k;
+  const size_t rw = (size_t)batch * N;
+  const size_t row_off = (size_t)row * rw;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N;
+  const bool own = row < L;
+  const uint64_t psp = tab[n + 3 * (size_t)nall * n + row];
+  u128 a0[BP], a1[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    a0[b] = own ? (u128)psp * c0[row_off + boff[b] + j] : (u128)0;
+    a1[b] = own ? (u128)psp * c1[row_off + boff[b] + j] : (u128)0;
+  }
+  ro_u64 e = tab + n + 3 * (size_t)row * n;
+  const size_t dstride = (size_t)nall * rw;   // words between two digits of the block
+  for (int t = 0; t < n; t++) {
+    const uint32_t s = perm[(size_t)t * N + j];
+    const uint64_t* kb = reinterpret_cast<const uint64_t*>(e[3 * t]);
+    const uint64_t* ka = reinterpret_cast<const uint64_t*>(e[3 * t + 1]);
+    const size_t kstride = e[3 * t + 2];
+    if (own) {
+#pragma unroll
+      for (int b = 0; b < BP; b++)
+        a0[b] += (u128)psp * c0[row_off + boff[b] + s];
+    }
+    for (int d = 0; d < ndig; d++) {
+      const uint64_t wb = kb[d * kstride + j], wa = ka[d * kstride + j];
+      const uint64_t* dp = dig + d * dstride + row_off + s;
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        const uint64_t x = dp[boff[b]];
+        a0[b] += (u128)x * wb;
+        a1[b] += (u128)x * wa;
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    st_stream1(out0 + row_off + boff[b] + j, mad_reduce(a0[b], q, mu, mu64, k));
+    st_stream1(out1 + row_off + boff[b] + j, mad_reduce(a1[b], q, mu, mu64, k));
+  }
+}
+
 }  // namespace hx
 
 namespace {
@@ -501,6 +602,8 @@ struct LinState {
   int next = 0;
   uint64_t* d_tab = nullptr;
   size_t d_cap = 0;
+  uint32_t* d_perm = nullptr;   // hx_hoisted_automorph_sum's gather tables
+  size_t perm_cap = 0;          // (words)
 };
 void state_free(void* p)
 {
@@ -514,6 +617,7 @@ void state_free(void* p)
       hipEventDestroy(s->copied[i]);
   }
   hipFree(s->d_tab);
+  hipFree(s->d_perm);
   delete s;
 }
 
@@ -1301,6 +1405,148 @@ extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* i
     launch_lin_comb<2>(bp, grid, st, o0, o1, s->d_tab, n, rows, batch, N, map, primes);
   else
     launch_lin_comb<1>(bp, grid, st, o0, nullptr, s->d_tab, n, rows, batch, N, map, primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0, const hx_poly* c1, const uint64_t* k,
+                                        const hx_ksk* const* W, int n, const int* sp_idx, int nsp, hx_poly* out0,
+                                        hx_poly* out1)
+{
+  if (!digits || !c0 || !c1 || !k || !W || !out0 || !out1 || (nsp > 0 && !sp_idx) || nsp < 0)
+    return err(HX_ERR_INVALID, "null argument");
+  if (n < 1)
+    return err(HX_ERR_INVALID, "hx_hoisted_automorph_sum needs at least one term (n = %d)", n);
+  if (out0 == out1 || out0 == digits || out0 == c0 || out0 == c1 || out1 == digits || out1 == c0 || out1 == c1)
+    return err(HX_ERR_INVALID, "an output is also an input, or out0 and out1 are the same poly");
+  hx_ctx* ctx = hxi::poly_ctx(c0);
+  if (hxi::poly_ctx(digits) != ctx || hxi::poly_ctx(c1) != ctx || hxi::poly_ctx(out0) != ctx || hxi::poly_ctx(out1) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  std::vector<hxi::KskView> kv(n);
+  for (int t = 0; t < n; t++) {
+    if (!W[t])
+      return err(HX_ERR_INVALID, "null key-switching matrix (term %d)", t);
+    hxi::ksk_view(W[t], &kv[t]);
+    if (kv[t].ctx != ctx)
+      return err(HX_ERR_INVALID, "the key-switching matrix of term %d belongs to another context", t);
+  }
+  hxi::CtxView v{};
+  RC(hxi::ctx_enter(ctx, &v));
+  std::unique_lock<std::recursive_mutex> lk(*v.mu);
+  if (v.capturing)
+    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_automorph_sum uploads a table of key rows and cannot be captured in a graph");
+  for (int t = 0; t < n; t++)
+    if (hxh::gcd(k[t] % v.m, v.m) != 1)
+      return err(HX_ERR_INVALID, "DoubleCRT::automorph: k[%d] = %llu is not in Zm*", t, (unsigned long long)k[t]);
+  int batch = 0, b2 = 0, nprimes = 0;
+  std::vector<int> all, other;
+  RC(shape_of(c0, &batch, &all));
+  RC(shape_of(c1, &b2, &other));
+  if (b2 != batch || other != all)
+    return err(HX_ERR_INVALID, "c0 and c1 differ in batch or prime set");
+  const int L = (int)all.size();
+  if (L == 0)
+    return err(HX_ERR_INVALID, "c0 has no rows");
+  RC(hx_ctx_num_primes(ctx, &nprimes));
+  for (int i = 0; i < nsp; i++) {
+    if (sp_idx[i] < 0 || sp_idx[i] >= nprimes || std::find(all.begin(), all.end(), sp_idx[i]) != all.end())
+      return err(HX_ERR_INVALID, "special prime %d is not a prime of the context, or is listed twice or among c0's", sp_idx[i]);
+    all.push_back(sp_idx[i]);
+  }
+  const int nall = (int)all.size();
+  if (nall > hx::MAX_ROWS)
+    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  RC(shape_of(digits, &b2, &other));
+  if (b2 != batch || other.empty() || other.size() % nall != 0)
+    return err(HX_ERR_INVALID, "the digit block differs in batch, or is not a whole number of digits on %d rows", nall);
+  const int ndig = (int)other.size() / nall;
+  for (int d = 0; d < ndig; d++)
+    for (int r = 0; r < nall; r++)
+      if (other[(size_t)d * nall + r] != all[r])
+        return err(HX_ERR_INVALID, "digit rows do not match the ciphertext's primes followed by the special primes");
+  for (hx_poly* o : {out0, out1}) {
+    RC(shape_of(o, &b2, &other));
+    if (b2 != batch)
+      return err(HX_ERR_INVALID, "an output has batch %d, the operands %d", b2, batch);
+  }
+  // wrow[r n + t]: the row of W[t] on the prime of output row r (rows by prime index, the leading ndig digits)
+  std::vector<int> wrow((size_t)nall * n);
+  for (int t = 0; t < n; t++) {
+    if (kv[t].ndig < ndig)
+      return err(HX_ERR_INVALID, "W must have as many columns as there are digits (term %d: %d, the block has %d)", t,
+                 kv[t].ndig, ndig);
+    for (int r = 0; r < nall; r++) {
+      const int* at = std::find(kv[t].row_idx, kv[t].row_idx + kv[t].nrows, all[r]);
+      if (at == kv[t].row_idx + kv[t].nrows)
+        return err(HX_ERR_PRIMESET, "No key-switching matrix row for prime %d (term %d)", all[r], t);
+      wrow[(size_t)r * n + t] = (int)(at - kv[t].row_idx);
+    }
+  }
+  // out0's accumulator takes Psp c0, n times Psp sigma(c0) and n ndig products of a digit word by a key word
+  if ((long long)n * (ndig + 1) + 1 > hx::MAD_CHUNK)
+    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_automorph_sum: n (ndig + 1) + 1 = %lld products per word, the accumulators take %d",
+               (long long)n * (ndig + 1) + 1, hx::MAD_CHUNK);
+  const uint32_t N = v.phim;
+  if (!*v.linalg) {
+    *v.linalg = new LinState();
+    *v.linalg_free = state_free;
+  }
+  LinState* s = static_cast<LinState*>(*v.linalg);
+  const hipStream_t st = v.stream;
+  const size_t words = (size_t)n + (size_t)nall * (3 * (size_t)n + 1), bytes = words * 8;
+  int slot = 0;
+  RC(stage_table(s, st, bytes, &slot));
+  if (s->perm_cap < (size_t)n * N) {
+    CK(hipStreamSynchronize(st));   // an earlier launch may still read the old tables
+    hipFree(s->d_perm);
+    s->d_perm = nullptr;
+    s->perm_cap = 0;
+    CK(hipMalloc((void**)&s->d_perm, (size_t)n * N * 4));
+    s->perm_cap = (size_t)n * N;
+  }
+  uint64_t *o0 = nullptr, *o1 = nullptr;
+  RC(hxi::poly_rows_reshape(out0, all.data(), nall, &o0));
+  RC(hxi::poly_rows_reshape(out1, all.data(), nall, &o1));
+  uint64_t* h = s->h_tab[slot];
+  for (int t = 0; t < n; t++)
+    h[t] = k[t] % v.m;
+  for (int r = 0; r < nall; r++) {
+    uint64_t q = 0;
+    RC(hx_ctx_prime(ctx, all[r], &q, nullptr));
+    for (int t = 0; t < n; t++) {
+      uint64_t* e = h + n + 3 * ((size_t)r * n + t);
+      const size_t at = (size_t)wrow[(size_t)r * n + t] * N;
+      e[0] = (uint64_t)(uintptr_t)(kv[t].d_b + at);
+      e[1] = (uint64_t)(uintptr_t)(kv[t].d_a + at);
+      e[2] = (uint64_t)kv[t].nrows * N;
+    }
+    uint64_t psp = 1 % q;
+    for (int i = 0; i < nsp; i++) {
+      uint64_t qs = 0;
+      RC(hx_ctx_prime(ctx, sp_idx[i], &qs, nullptr));
+      psp = hxh::mulmod(psp, qs % q, q);
+    }
+    h[n + 3 * (size_t)nall * n + r] = psp;
+  }
+  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
+  CK(hipEventRecord(s->copied[slot], st));
+  s->pending[slot] = true;
+  HX_LAUNCH(hx::hoisted_perm_kernel, dim3((N + 255) / 256, (unsigned)n), dim3(256), 0, st, s->d_perm, v.d_zms, v.d_zms_index, N,
+            v.m, hx::as_ro(s->d_tab), (int)v.pow2);
+  CK(hipGetLastError());
+  hx::MadRows map;
+  for (int r = 0; r < nall; r++)
+    map.p[r] = (uint16_t)all[r];
+  const int bp = batch == 1 ? 1 : 4;
+  const dim3 grid((N + 255) / 256, (unsigned)nall, (unsigned)((batch + bp - 1) / bp));
+  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  const uint64_t *dg = hxi::poly_rows_read(digits), *p0 = hxi::poly_rows_read(c0), *p1 = hxi::poly_rows_read(c1);
+  if (bp == 1)
+    HX_LAUNCH((hx::hoisted_sum_kernel<1>), grid, dim3(256), 0, st, o0, o1, dg, p0, p1, s->d_perm, hx::as_ro(s->d_tab), n, ndig,
+              L, nall, batch, N, map, primes);
+  else
+    HX_LAUNCH((hx::hoisted_sum_kernel<4>), grid, dim3(256), 0, st, o0, o1, dg, p0, p1, s->d_perm, hx::as_ro(s->d_tab), n, ndig,
+              L, nall, batch, N, map, primes);
   CK(hipGetLastError());
   return HX_OK;
 }

@@ -1619,6 +1619,10 @@ class Ctxt:
         return self
 
     fuseLinComb = False  # fused=None: the call sequence until hx_lin_comb has been measured as the faster form
+    # fused=None in BasicAutomorphPrecon.automorphSum: one hx_hoisted_automorph_sum wherever it applies.  True because the
+    # fused form won every alternated pair against the loop (tools/bench_thin_recrypt.py, profiles/thin_recrypt.json,
+    # DESIGN 3.9p); set it to False to get the loop back
+    fuseHoistedSum = True
 
     @staticmethod
     def linearCombination(terms, free=0, fused=None):
@@ -2002,6 +2006,55 @@ class BasicAutomorphPrecon:
         res.ksw_map = c.ksw_map
         if amt != k:                   # more automorphisms to do: the usual smartAutomorph (:177-181)
             res.smartAutomorph(k * pow(amt, -1, ctx.m) % ctx.m)
+        return res
+
+    def automorphSum(self, ks, fused=None):
+        """The ciphertext plus its images under the automorphisms ks, as a new ciphertext: the hoisted loop of traceMap
+        (src/matmul.cpp:2878-2887), acc = ctxt; acc += *precon.automorph(k) for every k.  Fused: one ops.hoistedSum
+        (hx_hoisted_automorph_sum) over the digit block, with the loop's bookkeeping -- the mod-up of acc by the special
+        primes at the first sum, then logaddexp per term -- float operation for float operation.  It applies to a BGV
+        ciphertext with the parts {1, s} when every k has a matrix of its own (_firstStep(k) = k) and the terms fit the
+        kernel's accumulators; otherwise, and with fused=False, the loop runs as it is.  fused=True insists on a backend
+        with hoistedSum; fused=None follows Ctxt.fuseHoistedSum.  Words, lnNoise, primeSet, ptxtSpace, intFactor and the
+        part handles are the same either way."""
+        c = self.ctxt
+        has = hasattr(c.ops, "hoistedSum")
+        if fused and not has:
+            raise RuntimeError("BasicAutomorphPrecon::automorphSum: fused=True, but this backend has no hoistedSum")
+        if (Ctxt.fuseHoistedSum if fused is None else fused) and has:
+            ret = self._sumFused(ks)
+            if ret is not None:
+                return ret
+        acc = c.clone()
+        for k in ks:
+            acc += self.automorph(k)
+        return acc
+
+    def _sumFused(self, ks):
+        """automorphSum's fused form, or None where it does not apply (nothing has been touched then)"""
+        c = self.ctxt
+        ctx = c.context
+        sp = list(ctx.specialPrimes)
+        if ctx.ckks or self.polyDigits is None or set(c.parts) != {"1", "s"} or c.primeSet & frozenset(sp):
+            return None
+        ks = [k % ctx.m for k in ks]
+        if not ks or any(k == 1 or math.gcd(k, ctx.m) != 1 or c._firstStep(k) != k for k in ks):
+            return None
+        if len(ks) * (len(self.digits) + 1) + 1 > 256:          # the accumulators of hx_hoisted_automorph_sum
+            return None
+        out0, out1 = c.ops.hoistedSum(self.polyDigits, c.parts["1"], c.parts["s"], ks, [c.ksw_auto[k] for k in ks], sp)
+        res = Ctxt(ctx, c.ops, c.ksw, c.ksw_ptxtSpace, c.ksw_lnNoise)
+        res.ksw_auto, res.ksw_pow, res.ksw_map, res._like = c.ksw_auto, c.ksw_pow, c.ksw_map, c._like
+        res.ptxtSpace, res.intFactor = c.ptxtSpace, c.intFactor
+        res.parts = {"1": out0, "s": out1}
+        logProd = ctx.logOfProduct(sorted(sp))
+        ln, mag = c.lnNoise + logProd, c.ptxtMag                # acc.modUpToSet at the first sum
+        for _ in ks:                                            # addCtxt: equal spaces, prime sets and intFactors
+            mag += res.ptxtMag                                  # (a term's ptxtMag is the constructor's)
+            ln = logaddexp(ln, self.lnNoise)
+        res.ptxtMag, res.lnRatFactor = mag, c.lnRatFactor + logProd
+        res.lnNoise = ln
+        res.primeSet = c.primeSet | frozenset(sp)
         return res
 
 

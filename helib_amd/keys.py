@@ -729,3 +729,7 @@ class HxBackend:
 
     def keySwitch(self, row_idx, b, a):
         return self.hx.KeySwitch(self.gctx, list(row_idx), b, a)
+
+    def hoistedSum(self, digits, c0, c1, ks, Ws, special):
+        """capi.hoistedAutomorphSum: the hoisted sum of traceMap in one device call"""
+        return self.hx.hoistedAutomorphSum(digits, c0, c1, ks, Ws, special)

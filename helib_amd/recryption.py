@@ -33,7 +33,14 @@ What a backend supplies: ops.recryptPrep(poly, out_set, q, p, p2r, p2ePrime, see
 (helib_amd.capi's on the device; the tests' oracle backend states it in Python integers), and the conversions through
 the p2dConv object RecryptData is given or builds.
 
-Not built: thinReCrypt, packedRecrypt, the dummy-ciphertext branch of reCrypt (helib_amd.evalmap.reCrypt keeps its
+  ThinRecryptData(cc, g, mvec, gens, ords, alsoThick=False)
+                                    (:773-787) RecryptData with coeffToSlot / slotToCoeff, the two
+                                    helib_amd.thin_evalmap.ThinEvalMap; the packed maps only with alsoThick
+  thinReCrypt(ct, pk, rc, seed)     (:940-1128) for slots that hold integers modulo p^r: drop to three primes,
+                                    slotToCoeff, the shared tail of preProcess, coeffToSlot (with traceMap),
+                                    extractDigitsThin once -- inside the reference's named timers
+
+Not built: packedRecrypt, the dummy-ciphertext branch of reCrypt and thinReCrypt (helib_amd.evalmap.reCrypt keeps its
 refusal).  Nothing here imports oracle/."""
 import copy
 import math
@@ -244,55 +251,118 @@ def extractDigitsPacked(rc, ct, botHigh, r, ePrime, fused=None):
     return ct.assign(out)
 
 
+def _bootKeySwitch(ct, pk, rc, seed, stats):
+    """what reCrypt and thinReCrypt share (src/recryption.cpp:420-502, :1012-1099), in place: canonical form, at most
+    three ciphertext primes, the switch to the recryption key, preProcess and the product with recryptEkey (the
+    intFactor is lost here: the callers restore it)"""
+    cc = rc.cc
+    if set(ct.parts) - {"1", "s"}:                      # make sure that this ciphertext is in canonical form
+        ct.reLinearize()
+        ct.dropSmallAndSpecialPrimes()
+    s3 = ct.primeSet - frozenset(cc.specialPrimes)
+    if not s3 <= frozenset(cc.ctxtPrimes):
+        raise LogicError("prime set is messed up")
+    if len(s3) > 3:                                     # leave only the first three ciphertext primes
+        first = min(s3)
+        s3 = s3 & frozenset(range(first, first + 3))
+    ct.modDownToSet(s3)
+    ct.switchToKey(pk.keySwitchingTo[(1, 1, 0, pk.recryptKeyID)])
+    zz = preProcess(ct, rc, seed, sorted(pk.recryptEkey.primeSet), stats)
+    batch = getattr(zz[0], "batch", 1)
+    new = pk.recryptEkey.replicated(batch)              # NOTE: here we lose the intFactor; it is restored by the caller
+    # the reference measures embeddingLargestCoeff of each constant on the host; the constants stay on the device
+    # here, so the size is the high-probability bound for coefficients of magnitude |w| <= (q / 2 + q p^e' / 2) / p^e'
+    bound = cc.noiseBoundForUniform(rc.q / (2.0 * rc.p2ePrime) + rc.q / 2.0, cc.phim)
+    new.multByConstant(zz[1], bound)
+    new.addConstant(zz[0], bound)
+    return ct.assign(new)
+
+
+def _checked(ct, pk, rc, have_maps, who):
+    """the checks at the head of reCrypt and thinReCrypt -> (ptxtSpace, intFactor), or None for an empty ciphertext"""
+    if not ct.parts:
+        return None
+    if pk.recryptKeyID < 0:
+        raise LogicError("No bootstrapping data")
+    if not have_maps:
+        raise LogicError("%s: this RecryptData holds no maps (%s)" % (who, "RecryptData(..., maps=True)" if who == "reCrypt"
+                                                                      else "ThinRecryptData"))
+    ct._materializeTensor()
+    if set(ct.parts) == {"1"}:
+        raise LogicError("%s: a dummy encryption (one part pointing at 1) is not handled" % who)
+    if rc.p2r % ct.ptxtSpace != 0:
+        raise LogicError("ptxtSpace must divide p^r when bootstrapping")
+    return ct.ptxtSpace, ct.intFactor
+
+
 def reCrypt(ct, pk, rc, seed=None, stats=None):
     """PubKey::reCrypt (src/recryption.cpp:367-545), in place.  pk: the key holding genRecryptData's results and the
     matrices the two EvalMaps walk through; rc: a RecryptData with its maps; seed: of the tie bits (None: 64 bits from
     the key's sampler)."""
-    cc = rc.cc
-    if not ct.parts:
+    head = _checked(ct, pk, rc, rc.firstMap is not None, "reCrypt")
+    if head is None:
         return ct
-    if pk.recryptKeyID < 0:
-        raise LogicError("No bootstrapping data")
-    if rc.firstMap is None:
-        raise LogicError("reCrypt: this RecryptData holds no maps (RecryptData(..., maps=True))")
-    ct._materializeTensor()
-    if set(ct.parts) == {"1"}:
-        raise LogicError("reCrypt: a dummy encryption (one part pointing at 1) is not handled")
-    ptxtSpace, intFactor = ct.ptxtSpace, ct.intFactor
-    p, r, p2r = rc.p, rc.r, rc.p2r
-    e, ePrime = rc.e, rc.ePrime
-    if p2r % ptxtSpace != 0:
-        raise LogicError("ptxtSpace must divide p^r when bootstrapping")
+    ptxtSpace, intFactor = head
     if seed is None:
         seed = int(pk.sampler.rng.integers(0, 1 << 62))
     ct.dropSmallAndSpecialPrimes()
     with timing.NTIMER_START("AAA_preProcess"):
-        if set(ct.parts) - {"1", "s"}:                  # make sure that this ciphertext is in canonical form
-            ct.reLinearize()
-            ct.dropSmallAndSpecialPrimes()
-        s3 = ct.primeSet - frozenset(cc.specialPrimes)
-        if not s3 <= frozenset(cc.ctxtPrimes):
-            raise LogicError("prime set is messed up")
-        if len(s3) > 3:                                 # leave only the first three ciphertext primes
-            first = min(s3)
-            s3 = s3 & frozenset(range(first, first + 3))
-        ct.modDownToSet(s3)
-        ct.switchToKey(pk.keySwitchingTo[(1, 1, 0, pk.recryptKeyID)])
-        zz = preProcess(ct, rc, seed, sorted(pk.recryptEkey.primeSet), stats)
-        batch = getattr(zz[0], "batch", 1)
-        new = pk.recryptEkey.replicated(batch)          # NOTE: here we lose the intFactor; it is restored below
-        # the reference measures embeddingLargestCoeff of each constant on the host; the constants stay on the device
-        # here, so the size is the high-probability bound for coefficients of magnitude |w| <= (q / 2 + q p^e' / 2) / p^e'
-        bound = cc.noiseBoundForUniform(rc.q / (2.0 * rc.p2ePrime) + rc.q / 2.0, cc.phim)
-        new.multByConstant(zz[1], bound)
-        new.addConstant(zz[0], bound)
-        ct.assign(new)
+        _bootKeySwitch(ct, pk, rc, seed, stats)
     with timing.NTIMER_START("AAA_LinearTransform1"):
         rc.firstMap.apply(ct, pk=pk)
     with timing.NTIMER_START("AAA_extractDigitsPacked"):
-        extractDigitsPacked(rc, ct, e - ePrime, r, ePrime)
+        extractDigitsPacked(rc, ct, rc.e - rc.ePrime, rc.r, rc.ePrime)
     with timing.NTIMER_START("AAA_LinearTransform2"):
         rc.secondMap.apply(ct, pk=pk)
+    if intFactor != 1:
+        ct.intFactor = ct.intFactor * intFactor % ptxtSpace
+    return ct
+
+
+THIN_RECRYPT_NLEVELS = 3        # src/recryption.cpp:989: the ciphertext primes kept before the first linear map
+
+
+class ThinRecryptData(RecryptData):
+    """ThinRecryptData::init (src/recryption.cpp:773-787): RecryptData -- with the packed maps only when alsoThick is set
+    -- and the two thin maps, coeffToSlot = ThinEvalMap(ea_boot, mvec, invert) over the array at p^(e - e' + r) and
+    slotToCoeff = ThinEvalMap(ea, mvec).  The arrays are handed in, or built on the device over gens / ords."""
+
+    def __init__(self, cc, g, mvec, gens=None, ords=None, alsoThick=False, ea=None, ea_boot=None, p2dConv=None, minimal=False):
+        from . import thin_evalmap
+        RecryptData.__init__(self, cc, g, mvec, gens=gens, ords=ords, p2dConv=p2dConv)
+        self.ea, self.ea_boot = ea, ea_boot
+        if alsoThick:
+            self.buildMaps()
+        if self.ea is None:
+            self.ea = arrayAt(cc, g, self.r, gens=gens, ords=ords)
+        if self.ea_boot is None:
+            self.ea_boot = arrayAt(cc, g, self.e - self.ePrime + self.r, gens=gens, ords=ords)
+        self.coeffToSlot = thin_evalmap.ThinEvalMap(self.ea_boot, self.mvec, invert=True, minimal=minimal)
+        self.slotToCoeff = thin_evalmap.ThinEvalMap(self.ea, self.mvec, minimal=minimal)
+
+
+def thinReCrypt(ct, pk, rc, seed=None, stats=None):
+    """PubKey::thinReCrypt (src/recryption.cpp:940-1128), in place, for a ciphertext whose slots hold integers modulo
+    p^r.  pk: the key holding genRecryptData's results, the matrices the two ThinEvalMaps walk through and those of the
+    Frobenius (traceMap); rc: a ThinRecryptData; seed: of the tie bits (None: 64 bits from the key's sampler)."""
+    cc = rc.cc
+    head = _checked(ct, pk, rc, getattr(rc, "coeffToSlot", None) is not None, "thinReCrypt")
+    if head is None:
+        return ct
+    ptxtSpace, intFactor = head
+    if seed is None:
+        seed = int(pk.sampler.rng.integers(0, 1 << 62))
+    ct.dropSmallAndSpecialPrimes()
+    first = min(cc.ctxtPrimes)                          # drop to a low level before the first linear map
+    ct.bringToSet(frozenset(range(first, min(max(cc.ctxtPrimes), first + THIN_RECRYPT_NLEVELS - 1) + 1)))
+    with timing.NTIMER_START("AAA_slotToCoeff"):
+        rc.slotToCoeff.apply(ct, pk=pk)
+    with timing.NTIMER_START("AAA_bootKeySwitch"):
+        _bootKeySwitch(ct, pk, rc, seed, stats)
+    with timing.NTIMER_START("AAA_coeffToSlot"):
+        rc.coeffToSlot.apply(ct, pk=pk)
+    with timing.NTIMER_START("AAA_extractDigitsThin"):
+        extractDigitsThin(rc.ea_boot, ct, rc.e - rc.ePrime, rc.r, rc.ePrime)
     if intFactor != 1:
         ct.intFactor = ct.intFactor * intFactor % ptxtSpace
     return ct

@@ -644,6 +644,33 @@ int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1
  * HX_ERR_UNSUPPORTED before touching the device.  Asynchronous on the context's stream. */
 int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* in0, const hx_poly* const* in1, int n,
                 const uint64_t* w, const uint64_t* addend);
+/* The hoisted sum of traceMap (src/matmul.cpp:2878-2887 over BasicAutomorphPrecon, :48-184:
+ *   BasicAutomorphPrecon precon(ctxt);  acc = ctxt;  for each t  acc += *precon.automorph(k[t]);)
+ * in one pass: the ciphertext plus its images under the n automorphisms k[t], each key-switched by its own matrix W[t]
+ * from the digits the ciphertext's s-part was broken into once.  digits: the block of hx_break_into_digits (ndig digits,
+ * each on the primes of c0 followed by sp_idx); c0, c1: the parts pointing at 1 and at s, unscaled, on one prime set.
+ * Per row, with Psp the product of the special primes modulo the row's prime and sigma_k the gather hx_automorph
+ * performs on evaluation rows (out[j] = in[index of Z_m^*[j] k mod m]):
+ *   ctxt rows:     out0 = Psp (c0 + sum_t sigma_k[t](c0)) + sum_t sum_j sigma_k[t](dig_j) b[t][j]
+ *                  out1 = Psp c1                          + sum_t sum_j sigma_k[t](dig_j) a[t][j]
+ *   special rows:  the two double sums alone
+ * out0 / out1 end up on the primes of c0 followed by sp_idx, as in hx_relinearize; they are overwritten, not read, and
+ * must not be among the inputs.  A W[t] made for a higher level is matched as hx_key_switch_digits matches it: its
+ * leading ndig digits, its rows found by prime index.  Every word written is canonical in [0, q) and equals what the
+ * loop leaves -- per term a copy and hx_automorph of the digit block and of c0, hx_add_primes_and_scale, a zero part,
+ * hx_key_switch_digits and two hx_add -- since all of it is exact arithmetic modulo the row's prime, whatever the order
+ * of the terms.  A word of out0 is one 128-bit sum of 1 + n + n ndig products of residues below 2^60, reduced once:
+ * n (ndig + 1) + 1 <= 256 (the bound of hx_lin_comb: 256 (2^60 - 2)^2 + 2^60 < 2^128); beyond that, and past 160 rows,
+ * HX_ERR_UNSUPPORTED.  Null arguments, n < 1, a k[t] outside Z_m^*, a poly or matrix of another context, mismatched
+ * batches or prime sets (c1 against c0, the digit rows against c0's primes and sp_idx, an sp_idx entry that is no prime
+ * of the context or already among c0's), an output among the inputs and a W[t] with fewer digits than the block are
+ * HX_ERR_INVALID; a prime that a W[t] lacks is HX_ERR_PRIMESET; a refused call touches no output.  The call uploads a
+ * table of key-row addresses, so it cannot be recorded: under an open graph capture it returns HX_ERR_UNSUPPORTED
+ * before touching the device.  Asynchronous on the context's stream.  Per term the loop makes about 3 ndig + 14 passes
+ * over a part in some ten launches; this call reads every digit word and key word once per term and writes the two
+ * outputs once, in two launches. */
+int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0, const hx_poly* c1, const uint64_t* k,
+                             const hx_ksk* const* W, int n, const int* sp_idx, int nsp, hx_poly* out0, hx_poly* out1);
 
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
