@@ -29,7 +29,7 @@ UNITS = [("ntt_kernels.hip", ["-DHX_NTT_ONLY=13", "-DHX_NTT_PART=1"], "ntt_kerne
          ("engine.hip", [], "engine.o")]
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["ntt_core.h", "dev_common.h", "rns_kernels.h", "rns_types.h", "hostmath.h", "conv_core.h", "bluestein.h", "norm_kernels.h",
-           "prg_kernels.h", "arena.h", "prof.h", "conv_dev.h", "ntt_kernel_util.h", "norm_r16.h", "fft_lds.h", "work_map.h",
+           "prg_kernels.h", "arena.h", "prof.h", "conv_dev.h", "ntt_kernel_util.h", "norm_r16.h", "fft_lds.h", "work_map.h", "ks_proth.h",
            os.path.join("..", "..", "include", "helib_amd.h")]
 # headers only some units include (a change there does not rebuild the row kernels: minutes)
 UNIT_HEADERS = {"pfa_kernels.hip": ["pfa_core.h", "pfa_dev.h"], "rns_mfma_kernels.hip": ["mfma_ext.h", "rns_mfma_dev.h"],
@@ -107,5 +107,45 @@ def build_host(force=False, verbose=False, link_dir=None, link_lib="helib_amd", 
     return out
 
 
+def build_variant(name, flags, verbose=False):
+    """A/B builds: the engine and the C++ host compiled with extra -D flags into lib/variants/NAME/ (run with
+    HX_LIB / HX_HOST_LIB pointing there).  A unit none of whose sources names one of the macros is not compiled
+    again: the default build's object is linked."""
+    build(verbose=verbose)
+    vdir = os.path.join(LIBDIR, "variants", name)
+    os.makedirs(vdir, exist_ok=True)
+    macros = [f[2:].split("=")[0] for f in flags if f.startswith("-D")]
+    cc = hipcc()
+    objs, jobs = [], []
+    for s, unit_flags, o in UNITS:
+        files = [s] + HEADERS + UNIT_HEADERS.get(s, [])
+        text = "".join(open(os.path.join(CSRC, f)).read() for f in files)
+        if any(m in text for m in macros):
+            objs.append(os.path.join(vdir, o))
+            jobs.append([cc, *FLAGS, *unit_flags, *flags, "-c", os.path.join(CSRC, s), "-o", objs[-1]])
+        else:
+            objs.append(os.path.join(LIBDIR, o))
+
+    def run(cmd):
+        if verbose:
+            print(" ".join(cmd), file=sys.stderr)
+        subprocess.check_call(cmd)
+
+    with ThreadPoolExecutor(max_workers=max(1, len(jobs))) as ex:
+        list(ex.map(run, jobs))
+    so = os.path.join(vdir, "libhelib_amd.so")
+    run([cc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", so, *objs])
+    inc = os.path.join(HERE, "..", "include")
+    run(["g++", "-std=c++17", "-O2", "-fPIC", "-shared", "-I" + inc, os.path.join(CSRC, "host_session.cpp"), "-L" + vdir,
+         "-lhelib_amd", "-Wl,-rpath,$ORIGIN", "-o", os.path.join(vdir, "libhelib_amd_host.so")])
+    for j in jobs:
+        os.remove(j[-1])
+    return so
+
+
 if __name__ == "__main__":
-    print(build(force="--force" in sys.argv, verbose=True))
+    if "--variant" in sys.argv:
+        i = sys.argv.index("--variant")
+        print(build_variant(sys.argv[i + 1], sys.argv[i + 2:], verbose=True))
+    else:
+        print(build(force="--force" in sys.argv, verbose=True))

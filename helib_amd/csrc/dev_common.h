@@ -193,6 +193,11 @@ struct KsFix {
   int64_t owner;        // digit owning this row, -1 for special primes
   TW pinv[KS_MAXD];     // P_e^-1 mod q_row for e < owner
   TW pscale;            // product of the special primes mod q_row (addPrimesAndScale factor)
+  // rows of Proth-form primes only (else 0): the same constants times 2^64 mod q_row, single words, for the Montgomery
+  // store loop of ntt_keyswitch_last_kernel (ks_proth.h)
+  uint64_t pinv_m[KS_MAXD];
+  uint64_t pscale_m;
+  uint64_t one_m;       // 2^64 mod q_row
 };
 // ntt_keyswitch_last_kernel: the key switch of output row j with the forward transform of ONE of its extension rows
 // -- digit fd[j], the last digit that does not own the row -- done in the same workgroup
@@ -204,6 +209,8 @@ struct KsLastArgs {
   const uint64_t* dig_ev;   // the same block where the other extension rows stand transformed (may be dig_in)
   const uint64_t* kb;       // [ndig][wrows][N] key rows, shared by the batch
   const uint64_t* ka;
+  const uint64_t* kbm;      // the same rows times 2^64 mod q (hx_ksk::d_bm, d_am): what rows of Proth-form primes read;
+  const uint64_t* kam;      // null when the matrix has no such row
   uint64_t* out0;           // [nall][batch][N]
   uint64_t* out1;
   const uint64_t* own_src;  // [L][batch][N] evaluation rows of the s^2 part (own-row rebuild)

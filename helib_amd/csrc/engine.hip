@@ -20,6 +20,7 @@
 #include "prof.h"
 #include "switches.h"
 #include "dev_common.h"
+#include "ks_proth.h"
 #include "hostmath.h"
 #include "bluestein.h"
 #include "pfa_dev.h"
@@ -318,6 +319,11 @@ struct hx_ksk {
   std::vector<int> row_idx;
   uint64_t* d_b;
   uint64_t* d_a;
+  // the same rows times 2^64 mod q on the rows of Proth-form primes (the other rows: a plain copy), built once when the
+  // matrix is made: what the Montgomery store loop of ntt_keyswitch_last_kernel reads (ks_proth.h).  Null where
+  // that route cannot apply (ksk_wants_mont)
+  uint64_t* d_bm = nullptr;
+  uint64_t* d_am = nullptr;
 };
 
 static int use(hx_ctx* c)
@@ -4627,6 +4633,58 @@ extern "C" int hx_break_into_digits_norms(const hx_poly* a, const int* dig_idx, 
 // ------------------------------------------------------------------
 // key-switch matrices, tensor, key switch, multiply
 // ------------------------------------------------------------------
+// k -> k 2^64 mod q over row `row` of every digit of both halves of a key-switching matrix ([ndig][nrows][N]); r2 = 0:
+// not a Proth-form prime, the words are copied
+namespace hx {
+__global__ void __launch_bounds__(256)
+ksk_mont_kernel(const uint64_t* __restrict__ b, const uint64_t* __restrict__ a, uint64_t* __restrict__ bm,
+                uint64_t* __restrict__ am, int row, int nrows, int ndig, unsigned n, uint64_t q, uint64_t r2)
+{
+  const unsigned i = blockIdx.x * 256u + threadIdx.x;
+  const int d = (int)blockIdx.y;
+  if (i >= n || d >= ndig)
+    return;
+  const size_t at = ((size_t)d * (size_t)nrows + (size_t)row) * (size_t)n + i;
+  const QC qc = make_qc(q, 0);
+  const uint64_t kb = b[at], ka = a[at];
+  bm[at] = r2 ? ksp_to_mont(kb, r2, qc) : kb;
+  am[at] = r2 ? ksp_to_mont(ka, r2, qc) : ka;
+}
+}  // namespace hx
+// the Montgomery-form copy is worth its memory only where the fused last-digit key switch can run (ks_last_ok) and
+// some row is a Proth-form prime's
+static bool ksk_wants_mont(const hx_ctx* c, const hx_ksk* k)
+{
+#ifdef HX_KS_BARRETT
+  return false;
+#else
+  if (c->sw.no_ks_last_fuse || !c->pow2 || c->logn < 13 || c->logn > 15)
+    return false;
+  for (int r : k->row_idx)
+    if (c->primes[(size_t)r].proth)
+      return true;
+  return false;
+#endif
+}
+// (called once per matrix, from hx_ksk_create: never from a multiply -- it allocates)
+static int ksk_build_mont(hx_ctx* c, hx_ksk* k)
+{
+  if (!ksk_wants_mont(c, k))
+    return HX_OK;
+  const int nrows = (int)k->row_idx.size();
+  const size_t bytes = (size_t)k->ndig * nrows * c->phim * 8;
+  HIPCHK(hipMalloc((void**)&k->d_bm, bytes));
+  HIPCHK(hipMalloc((void**)&k->d_am, bytes));
+  for (int r = 0; r < nrows; r++) {
+    const PrimeHost& ph = c->primes[(size_t)k->row_idx[r]];
+    const uint64_t r2 = ph.proth ? hx::tw_mont_form(hx::tw_mont_form(1, ph.q), ph.q) : 0;
+    HX_LAUNCH(hx::ksk_mont_kernel, dim3(((unsigned)c->phim + 255u) / 256u, (unsigned)k->ndig), dim3(256), 0, c->stream, k->d_b,
+              k->d_a, k->d_bm, k->d_am, r, nrows, k->ndig, (unsigned)c->phim, ph.q, r2);
+  }
+  HIPCHK(hipGetLastError());
+  return HX_OK;
+}
+
 extern "C" int hx_ksk_create(hx_ctx* c, int ndig, const int* row_idx, int nrows, const uint64_t* b,
                              const uint64_t* a, hx_ksk** out)
 {
@@ -4642,6 +4700,8 @@ extern "C" int hx_ksk_create(hx_ctx* c, int ndig, const int* row_idx, int nrows,
       if (k) {
         hipFree(k->d_b);
         hipFree(k->d_a);
+        hipFree(k->d_bm);
+        hipFree(k->d_am);
         delete k;
       }
     }
@@ -4654,6 +4714,7 @@ extern "C" int hx_ksk_create(hx_ctx* c, int ndig, const int* row_idx, int nrows,
   HIPCHK(hipMalloc((void**)&k->d_a, bytes));
   HIPCHK(hipMemcpy(k->d_b, b, bytes, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(k->d_a, a, bytes, hipMemcpyHostToDevice));
+  CHK(ksk_build_mont(c, k));
   c->refs++;
   guard.k = nullptr;
   *out = k;
@@ -4691,6 +4752,8 @@ extern "C" int hx_ksk_destroy(hx_ksk* k)
   hipStreamSynchronize(k->ctx->stream);
   hipFree(k->d_b);
   hipFree(k->d_a);
+  hipFree(k->d_bm);
+  hipFree(k->d_am);
   ctx_release(k->ctx);
   delete k;
   return HX_OK;
@@ -4782,6 +4845,12 @@ static int ks_fix_table(hx_ctx* c, const std::vector<int>& all, const std::vecto
           ps = hxh::mulmod(ps, c->primes[all[t]].q % q, q);
       h[r].pscale.w = ps;
       h[r].pscale.wp = hxh::shoup(ps, q);
+      if (c->primes[all[r]].proth) {
+        for (int e = 0; e < (int)digit_primes.size(); e++)
+          h[r].pinv_m[e] = hx::tw_mont_form(h[r].pinv[e].w, q);
+        h[r].pscale_m = hx::tw_mont_form(ps, q);
+        h[r].one_m = hx::tw_mont_form(1, q);
+      }
     }
     ExtPlan* pl = new ExtPlan();
     memset(&pl->dev, 0, sizeof pl->dev);
@@ -4863,6 +4932,11 @@ static bool ks_last_ok(const hx_ctx* c, const hx_ksk* W, const std::vector<int>&
     const uint64_t q = c->primes[(size_t)all[r]].q;
     if (hxh::bitlen(q) > 60 || (q >> 32) == 0 || (owner[r] >= 0) != ((int)r < L) || owner[r] >= ndig)
       return false;
+#ifndef HX_KS_BARRETT
+    // (a Proth-form row reads the Montgomery-form key rows; a matrix made without them takes the two-launch route)
+    if (c->primes[(size_t)all[r]].proth && !W->d_bm)
+      return false;
+#endif
   }
   return true;
 }
@@ -4889,6 +4963,8 @@ static int keyswitch_last_launch(hx_ctx* c, const uint64_t* dig_in, const uint64
   A.dig_ev = dig_ev;
   A.kb = W->d_b;
   A.ka = W->d_a;
+  A.kbm = W->d_bm;
+  A.kam = W->d_am;
   A.out0 = out0;
   A.out1 = out1;
   A.own_src = own_src;

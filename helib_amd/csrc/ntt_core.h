@@ -1016,7 +1016,15 @@ template <int LOGN, class AR = ArShoup>
 struct RowNTT {
   using G = Geo<LOGN>;
   static constexpr int NPHASE = 8;
-
+  // bound, in whole q, of what the forward transform hands its store for a load bound of LB q (the FC of fwd below:
+  // a fused store's replay asks for it by name)
+  template <int LB>
+  static constexpr int fwd_store_bound()
+  {
+    constexpr int FA = pass_bound_out<AR, 5, false, 31, LB * AR::U>();
+    constexpr int FB = pass_bound_out<AR, 5, false, 31, FA>();
+    return (pass_bound_out<AR, G::LC, false, G::GC - 1, FB>() + AR::U - 1) / AR::U;
+  }
 
   // -------- forward: coefficients (natural) -> evaluations (natural) -----
   template <int PH, class IO, class TWS>
@@ -1032,6 +1040,7 @@ struct RowNTT {
     constexpr int FB = pass_bound_out<AR, 5, false, 31, FA>();
     constexpr int FCU = pass_bound_out<AR, G::LC, false, G::GC - 1, FB>();
     constexpr int FC = (FCU + AR::U - 1) / AR::U;
+    static_assert(FC == fwd_store_bound<LB>(), "fwd_store_bound restates FC");
     static_assert(LB <= AR::FWD_LOAD_MAX && FA <= 16 * AR::U && FB <= 16 * AR::U && FCU <= 16 * AR::U, "lazy bounds");
     if constexpr (PH == 0) {
       if constexpr (IO::PIPELINED) {

@@ -12,6 +12,7 @@
 
 #include "ntt_kernel_util.h"
 #include "norm_r16.h"
+#include "ks_proth.h"
 
 // One translation unit per ring size.  The row kernels are straight-line code of ~7000 instructions each, in
 // 3 ring sizes x 2 arithmetics x a dozen IO functors: compiled as one unit this file takes nine minutes.  Built
@@ -974,8 +975,12 @@ ntt_row_kernel(const uint64_t* in, uint64_t* out, NttRows rows, int batch,
 // phase is the whole key-switch arithmetic of the row: the other digits' words, the s^2 row of the own-row rebuild,
 // the parts (1) and (s) and the 2 D key words are streamed in, out0[j] and out1[j] are written.  That extension row is
 // neither written nor read back: 16 N bytes per (row, element) less, and no accumulator has to survive a transform.
-//   * every output word is the canonical residue the two-launch route computes (exact integer arithmetic: the same
-//     128-bit sum of D products plus the accumulator through the same reduction), so the routes agree word for word;
+//   * every output word is the canonical residue the two-launch route computes (exact integer arithmetic), so the
+//     routes agree word for word.  Rows of Proth-form primes run the Montgomery store loop of ks_proth.h on the key
+//     rows in Montgomery form (KsLastArgs::kbm / kam): half the Barrett / Shoup loop's instructions (DESIGN.md 3.3b:
+//     what that bought and what it did not); any other row -- and every row of a -DHX_KS_BARRETT build, the control
+//     arm -- forms the same 128-bit sum of D products plus the accumulator through the same reduction as
+//     keyswitch_kernel.  A launch may mix the two kinds of row;
 //   * operand words come through pinned loads and explicit vmcnt waits, as in ModDownTensorIO::store_part.  Beside the
 //     64-register coefficient file and ~35 registers of 128-bit arithmetic, 128 VGPRs leave room for about 14 operand
 //     words.  D = 2 (7 words per coefficient) requests them one coefficient AHEAD in a double buffer; D = 3 (10 words;
@@ -1004,28 +1009,26 @@ struct KsLastIO {
   const KsLastArgs& A;
   unsigned row, b, brow, fd;
   int owner;
-  uint64_t q, mu63, mu64;
-  uint32_t k;
-  TW ps;            // addPrimesAndScale factor of the parts (1), (s) -- or the identity when they come scaled
-  TW pinv[ND - 1];  // P_e^-1 of the digits before the owner (own-row rebuild)
-  __device__ KsLastIO(const KsLastArgs& A_, unsigned row_, unsigned b_, unsigned brow_, unsigned fd_, unsigned bytes,
-                      const PrimeDev* pd)
-      : rin(make_rsrc(A_.dig_in + (((size_t)fd_ * (size_t)A_.nall + row_) * (size_t)A_.batch + b_) * (size_t)(bytes / 8u), bytes)),
-        A(A_), row(row_), b(b_), brow(brow_), fd(fd_), q(pd->q), mu63(pd->mu63), mu64(pd->mu64), k(pd->k)
+  const PrimeDev* pd;
+  // MONT: the store loop of a Proth-form row runs the Montgomery arithmetic of ks_proth.h on the key rows in Montgomery
+  // form; any other row, and every row of a -DHX_KS_BARRETT build (the control arm), the Barrett / Shoup loop
+  template <class AR>
+  static constexpr bool mont()
   {
-    ro_u64 fw = as_ro(reinterpret_cast<const uint64_t*>(A_.fix + row_));
-    constexpr unsigned PINV = offsetof(KsFix, pinv) / 8u, PSC = offsetof(KsFix, pscale) / 8u;
-    owner = (int)(int64_t)fw[0];
-    // (x 1 with the companion floor(2^64 / q) is the identity on canonical words: what a branch would skip is
-    // multiplied through instead -- a branch per coefficient fragments the schedule of the store loop)
-    ps.w = A_.scale_parts ? fw[PSC] : 1;
-    ps.wp = A_.scale_parts ? fw[PSC + 1] : mu64;
-#pragma unroll
-    for (int e = 0; e < ND - 1; e++) {
-      const bool in = e < owner;
-      pinv[e].w = in ? fw[PINV + 2 * e] : 1;
-      pinv[e].wp = in ? fw[PINV + 2 * e + 1] : mu64;
-    }
+#ifdef HX_KS_BARRETT
+    return false;
+#else
+    return AR::PROTH;
+#endif
+  }
+  __device__ KsLastIO(const KsLastArgs& A_, unsigned row_, unsigned b_, unsigned brow_, unsigned fd_, unsigned bytes,
+                      const PrimeDev* pd_)
+      : rin(make_rsrc(A_.dig_in + (((size_t)fd_ * (size_t)A_.nall + row_) * (size_t)A_.batch + b_) * (size_t)(bytes / 8u), bytes)),
+        A(A_), row(row_), b(b_), brow(brow_), fd(fd_), pd(pd_)
+  {
+    // (the loop's other per-row constants are fetched by store_rows, which knows the row's arithmetic: none of them
+    // has to live through the transform)
+    owner = (int)(int64_t)as_ro(reinterpret_cast<const uint64_t*>(A_.fix + row_))[0];
   }
   __device__ __forceinline__ uint64_t load(unsigned tid, unsigned c) const
   {
@@ -1081,6 +1084,51 @@ struct KsLastIO {
     const size_t eoff = ((size_t)row * (size_t)A.batch + b) * N;       // (row, element) of a [rows][batch][N] block
     const size_t dstride = (size_t)A.nall * (size_t)A.batch * N;       // words between two digits' blocks
     const unsigned kstride = (unsigned)A.wrows * bytes;                // bytes between two digits' key rows
+    // the row's constants, through the scalar cache (KsFix: the Shoup pairs, or the single words times 2^64)
+    constexpr bool MONT = mont<AR>();
+    using KP = KsProth<ND, OWNED, B>;
+    const ro_u64 fw = as_ro(reinterpret_cast<const uint64_t*>(A.fix + row));
+    const uint64_t q = qc.q;
+    uint64_t mu63 = 0;
+    uint32_t k = 0;
+    TW ps = {0, 0};   // addPrimesAndScale factor of the parts (1), (s) -- or the identity when they come scaled
+    TW pinv[ND - 1];  // P_e^-1 of the digits before the owner (own-row rebuild)
+    typename KP::Consts kc;
+    if constexpr (MONT) {
+      constexpr unsigned PINV = offsetof(KsFix, pinv_m) / 8u, PSC = offsetof(KsFix, pscale_m) / 8u, ONE = offsetof(KsFix, one_m) / 8u;
+      // (x 2^64 mod q is the identity of the Montgomery product: what a branch would skip is multiplied through)
+      const uint64_t one = fw[ONE];
+#pragma unroll
+      for (int e = 0; e < ND - 1; e++)
+        kc.pinv[e] = e < owner ? fw[PINV + e] : one;
+      kc.ps0 = A.scale_parts ? fw[PSC] : one;
+      kc.ps1 = A.acc1 ? kc.ps0 : 0;   // (no (s) part: its product vanishes)
+      kc.xoff = KP::xoff(qc);
+    } else {
+      constexpr unsigned PINV = offsetof(KsFix, pinv) / 8u, PSC = offsetof(KsFix, pscale) / 8u;
+      const ro_u64 pw = as_ro(reinterpret_cast<const uint64_t*>(pd));
+      const uint64_t mu64 = pw[offsetof(PrimeDev, mu64) / 8u];
+      mu63 = pw[offsetof(PrimeDev, mu63) / 8u];
+      k = (uint32_t)pw[offsetof(PrimeDev, k) / 8u];
+      // (x 1 with the companion floor(2^64 / q) is the identity on canonical words: what a branch would skip is
+      // multiplied through instead -- a branch per coefficient fragments the schedule of the store loop)
+      ps.w = A.scale_parts ? fw[PSC] : 1;
+      ps.wp = A.scale_parts ? fw[PSC + 1] : mu64;
+#pragma unroll
+      for (int e = 0; e < ND - 1; e++) {
+        const bool in = e < owner;
+        pinv[e].w = in ? fw[PINV + 2 * e] : 1;
+        pinv[e].wp = in ? fw[PINV + 2 * e + 1] : mu64;
+      }
+    }
+    // a row's two sums: lazy words that every Montgomery product adds onto, or the Barrett loop's 128-bit sums
+    using Sum = std::conditional_t<MONT, uint64_t, u128>;
+    auto red = [&](Sum S) {
+      if constexpr (MONT)
+        return KP::reduce(S, qc);
+      else
+        return tensor_red128(S, q, mu63, k);
+    };
     // memory slot s holds digit s, or s + 1 from the owner on (the fused digit is the last one or, on the rows the
     // last digit owns, the one before it: it never lies between two memory digits)
     v4i32 rm[NMEM > 0 ? NMEM : 1];
@@ -1094,8 +1142,9 @@ struct KsLastIO {
     kd[NMEM] = (int)(fd * kstride);
     if constexpr (OWNED)
       kd[NMEM + 1] = (int)((unsigned)owner * kstride);
-    const v4i32 rkb = make_rsrc(A.kb + (size_t)brow * N, (unsigned)(ND - 1) * kstride + bytes);
-    const v4i32 rka = make_rsrc(A.ka + (size_t)brow * N, (unsigned)(ND - 1) * kstride + bytes);
+    // (a Proth-form row reads the matrix's Montgomery-form copy, any other the plain one: same layout)
+    const v4i32 rkb = make_rsrc((MONT ? A.kbm : A.kb) + (size_t)brow * N, (unsigned)(ND - 1) * kstride + bytes);
+    const v4i32 rka = make_rsrc((MONT ? A.kam : A.ka) + (size_t)brow * N, (unsigned)(ND - 1) * kstride + bytes);
     const v4i32 ro0 = make_rsrc(A.out0 + eoff, bytes), ro1 = make_rsrc(A.out1 + eoff, bytes);
     // (no (s) part: the (1) row stands in for it and its product is masked away)
     const v4i32 rown = make_rsrc(OWNED ? A.own_src + eoff : A.out0 + eoff, bytes);
@@ -1139,40 +1188,63 @@ struct KsLastIO {
         // (the stores of coefficient i-1 that were issued after these loads: both, or the out1 store alone)
         pinned_wait<(i > 0 ? (SPLIT ? 1 : 2) : 0)>(w);
       }
-      // the word ntt_row_kernel<., false, 8> would have stored: canonical (the rebuild and the 128-bit sums assume it)
-      const uint64_t xf = norm_from<B, true>(v[i], qc);
+      // the word ntt_row_kernel<., false, 8> would have stored: canonical (the Shoup rebuild and the Barrett sums assume
+      // it), or left lazy where the Montgomery forms take it so (ks_proth.h: the bounds)
+      uint64_t xf;
+      if constexpr (MONT)
+        xf = KP::fused_word(v[i], qc);
+      else
+        xf = norm_from<B, true>(v[i], qc);
       const unsigned c = eval_const<LOGN>(i);
       uint64_t x[ND];   // the digit words in key order: the memory slots, the fused digit, the owner's rebuilt word
       static_for<0, NMEM>([&](auto S) { x[decltype(S)::value] = w[decltype(S)::value]; });
       x[NMEM] = xf;
-      u128 s0 = 0, s1 = 0;
+      Sum s0 = 0, s1 = 0;
+      auto mac = [&](auto S, Sum& s, uint64_t kw) {   // s += x[S] * key word
+        constexpr int d = decltype(S)::value;
+        if constexpr (MONT)
+          s = KP::template term<d>(x[d], kw, s, qc);
+        else
+          s += (u128)x[d] * kw;
+      };
       if constexpr (OWNED) {
         uint64_t own = w[NMEM];
-        static_for<0, NMEM>([&](auto S) {
-          constexpr int s = decltype(S)::value;
-          own = mul_shoup(own + q - masked(w[s], cm[s]), pinv[s].w, pinv[s].wp, q);
-        });
-        x[NMEM + 1] = mul_shoup(own + q - masked(xf, cmf), pinv[ND - 2].w, pinv[ND - 2].wp, q);
-        s0 = mul_shoup(w[NMEM + 1], ps.w, ps.wp, q);
-        s1 = mul_shoup(w[NMEM + 2], ps.w, ps.wp, q) & m1;
+        if constexpr (MONT) {
+          static_for<0, NMEM>([&](auto S) {
+            constexpr int s = decltype(S)::value;
+            own = KP::rebuild_mem(own, masked(w[s], cm[s]), kc.pinv[s], qc);
+          });
+          x[NMEM + 1] = KP::rebuild_last(own, masked(xf, cmf), kc, qc);   // (may stay lazy: below 2q)
+          // the parts (1), (s) enter the sums as one more product each, normalised with them
+          s0 = KP::part(w[NMEM + 1], kc.ps0, qc);
+          s1 = KP::part(w[NMEM + 2], kc.ps1, qc);
+        } else {
+          static_for<0, NMEM>([&](auto S) {
+            constexpr int s = decltype(S)::value;
+            own = mul_shoup(own + q - masked(w[s], cm[s]), pinv[s].w, pinv[s].wp, q);
+          });
+          x[NMEM + 1] = mul_shoup(own + q - masked(xf, cmf), pinv[ND - 2].w, pinv[ND - 2].wp, q);
+          s0 = mul_shoup(w[NMEM + 1], ps.w, ps.wp, q);
+          s1 = mul_shoup(w[NMEM + 2], ps.w, ps.wp, q) & m1;
+        }
       }
-      // (D q^2 + q stays far inside the reduction's domain, S < 8 q^2, for D <= 4)
-      static_for<0, ND>([&](auto S) { s0 += (u128)x[decltype(S)::value] * w[KB0 + decltype(S)::value]; });
+      // (D q^2 + q stays far inside the Barrett reduction's domain, S < 8 q^2, for D <= 4; KsProth states its own)
+      static_for<0, ND>([&](auto S) { mac(S, s0, w[KB0 + decltype(S)::value]); });
       if constexpr (SPLIT) {
         const int c8 = (int)(c * 8u);
         static_for<0, ND>([&](auto S) { k2[decltype(S)::value] = ld_pinned<false>(rka, tid, kd[decltype(S)::value] + c8); });
-        put(ro0, tid, c, tensor_red128(s0, q, mu63, k));
+        put(ro0, tid, c, red(s0));
         pinned_wait<1>(k2);   // (behind them: the out0 store)
-        static_for<0, ND>([&](auto S) { s1 += (u128)x[decltype(S)::value] * k2[decltype(S)::value]; });
+        static_for<0, ND>([&](auto S) { mac(S, s1, k2[decltype(S)::value]); });
         if constexpr (more)
           request(std::integral_constant<int, i + 1>{}, wb[0]);
-        put(ro1, tid, c, tensor_red128(s1, q, mu63, k));
+        put(ro1, tid, c, red(s1));
       } else {
-        static_for<0, ND>([&](auto S) { s1 += (u128)x[decltype(S)::value] * w[KA0 + decltype(S)::value]; });
+        static_for<0, ND>([&](auto S) { mac(S, s1, w[KA0 + decltype(S)::value]); });
         if constexpr (DEPTH == 1 && more)
           request(std::integral_constant<int, i + 1>{}, wb[0]);   // (this coefficient's words are consumed)
-        put(ro0, tid, c, tensor_red128(s0, q, mu63, k));
-        put(ro1, tid, c, tensor_red128(s1, q, mu63, k));
+        put(ro0, tid, c, red(s0));
+        put(ro1, tid, c, red(s1));
       }
       HX_SCHED_FENCE();
     });

@@ -231,7 +231,9 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
 /* KeySwitch matrix W (include/helib/keySwitching.h:86-101) with the a-column
  * expanded once by the host (HElib regenerates it from W.prgSeed on every key
  * switch, src/Ctxt.cpp:196-206).  b, a: host arrays [ndig][nrows][phim] on
- * primes row_idx[nrows] (ctxt primes followed by special primes). */
+ * primes row_idx[nrows] (ctxt primes followed by special primes).
+ * On a power-of-two ring with log N in 13 .. 15 the matrix also holds its rows times 2^64 mod q (the fused key
+ * switch's Montgomery store loop reads them): twice the device memory, converted here, once. */
 int hx_ksk_create(hx_ctx* ctx, int ndig, const int* row_idx, int nrows, const uint64_t* b,
                   const uint64_t* a, hx_ksk** out);
 int hx_ksk_destroy(hx_ksk* k);
