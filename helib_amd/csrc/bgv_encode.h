@@ -30,30 +30,8 @@ struct SlotBase {
   size_t cap[4] = {0, 0, 0, 0};
 };
 
-inline int err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-inline int err(int code, const char* fmt, ...)
-{
-  char b[400];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  return hxi::fail_msg(code, b);
-}
-#define CK(expr)                                                                                               \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) {                                                                                    \
-      (void)hipGetLastError();                                                                                 \
-      return err(HX_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-    }                                                                                                          \
-  } while (0)
-#define RC(expr)        \
-  do {                  \
-    int _rc = (expr);   \
-    if (_rc != HX_OK)   \
-      return _rc;       \
-  } while (0)
+using hxi::err;           // (with CK and RC: ckks_bridge.h)
+using hxi::DrainOnExit;   // every return waits for the stream: no copy still reads a host buffer, no kernel a temporary
 
 inline int ensure_buf(SlotBase* t, hipStream_t st, int slot, size_t bytes)
 {
@@ -80,10 +58,6 @@ struct Enter {
       return err(HX_ERR_INVALID, "%s waits for the device and cannot be captured in a graph", what);
     return t->side ? hx_ctx_set_stream(t->side, (void*)v.stream) : HX_OK;
   }
-};
-struct DrainOnExit {   // every return waits for the stream: no copy still reads a host buffer, no kernel a temporary
-  hipStream_t st;
-  ~DrainOnExit() { (void)hipStreamSynchronize(st); }
 };
 struct Drop {
   hx_poly* t;

@@ -1,9 +1,12 @@
 // ckks_bridge.h -- what ckks_slots.hip, bgv_slots.hip and linalg.hip need of engine.hip's objects (hx_ctx / hx_poly stay private
-// to engine.hip; everything else those units do goes through the C ABI, include/helib_amd.h)
+// to engine.hip; everything else those units do goes through the C ABI, include/helib_amd.h), and the error plumbing
+// they share (err, CK, RC, DrainOnExit)
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <cstdarg>
+#include <cstdio>
 #include <mutex>
 
 #include "../../include/helib_amd.h"
@@ -50,4 +53,38 @@ void ksk_view(const hx_ksk* k, KskView* v);
 // hx_poly_rem's arithmetic (toPoly + PolyRed(t), exact) with the result kept on the device: *d_out = [batch][phi(m)]
 // words in [0, t) in the context's scratch, valid until the next call on that context (hold its lock); a has rows
 int poly_rem_device(const hx_poly* a, uint64_t t, const uint64_t** d_out);
+
+// error plumbing of those units (they say `using hxi::err;`): a formatted hx_last_error, and early returns
+inline int err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+inline int err(int code, const char* fmt, ...)
+{
+  char b[400];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof b, fmt, ap);
+  va_end(ap);
+  return fail_msg(code, b);
+}
+// Declared once work may be enqueued: every return -- an error one included -- waits for the stream, so that no
+// copy still reads a host buffer (the constant tables, the caller's arrays) and no kernel a temporary poly that the
+// return releases.  (Declared after those objects: destroyed, and so run, before them.)
+struct DrainOnExit {
+  hipStream_t st;
+  ~DrainOnExit() { (void)hipStreamSynchronize(st); }
+};
 }  // namespace hxi
+
+#define CK(expr)                                                                                                    \
+  do {                                                                                                              \
+    hipError_t _e = (expr);                                                                                         \
+    if (_e != hipSuccess) {                                                                                         \
+      (void)hipGetLastError();                                                                                      \
+      return hxi::err(HX_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
+    }                                                                                                               \
+  } while (0)
+#define RC(expr)        \
+  do {                  \
+    int _rc = (expr);   \
+    if (_rc != HX_OK)   \
+      return _rc;       \
+  } while (0)

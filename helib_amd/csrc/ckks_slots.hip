@@ -44,30 +44,8 @@ void state_free(void* p)
   delete s;
 }
 
-int err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int err(int code, const char* fmt, ...)
-{
-  char b[400];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  return hxi::fail_msg(code, b);
-}
-#define CK(expr)                                                                                               \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) {                                                                                    \
-      (void)hipGetLastError();                                                                                 \
-      return err(HX_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-    }                                                                                                          \
-  } while (0)
-#define RC(expr)        \
-  do {                  \
-    int _rc = (expr);   \
-    if (_rc != HX_OK)   \
-      return _rc;       \
-  } while (0)
+using hxi::err;   // (with CK, RC and DrainOnExit: ckks_bridge.h)
+using hxi::DrainOnExit;
 
 // the range of the slot kernels: CKKS needs m a power of two (PAlgebra, src/PAlgebra.cpp:463-467); the device
 // transforms cover N = phi(m) <= 2^16 (the norm kernels' range)
@@ -181,14 +159,6 @@ int launch_embed(Enter& E, const double* d_f, int batch, double2* d_slots)
   CK(hipGetLastError());
   return HX_OK;
 }
-
-// Declared once work may be enqueued: every return -- an error one included -- waits for the stream, so that no
-// copy still reads a host buffer (the constant tables, the caller's arrays) and no kernel a temporary poly that the
-// return releases.  (Declared after those objects: destroyed, and so run, before them.)
-struct DrainOnExit {
-  hipStream_t st;
-  ~DrainOnExit() { (void)hipStreamSynchronize(st); }
-};
 
 uint64_t powmod(uint64_t a, uint64_t e, uint64_t q)
 {

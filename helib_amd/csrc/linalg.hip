@@ -591,6 +591,8 @@ hoisted_sum_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, con
 
 namespace {
 
+using hxi::err;
+
 constexpr int RING = 4;  // calls whose table copy may still be in flight
 
 // per-context state: pinned staging buffers for the pointer table (one per call in flight) and its device copy
@@ -603,7 +605,7 @@ struct LinState {
   uint64_t* d_tab = nullptr;
   size_t d_cap = 0;
   uint32_t* d_perm = nullptr;   // hx_hoisted_automorph_sum's gather tables
-  size_t perm_cap = 0;          // (words)
+  size_t perm_cap = 0;          // (bytes)
 };
 void state_free(void* p)
 {
@@ -621,62 +623,8 @@ void state_free(void* p)
   delete s;
 }
 
-int err(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
-int err(int code, const char* fmt, ...)
-{
-  char b[400];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof b, fmt, ap);
-  va_end(ap);
-  return hxi::fail_msg(code, b);
-}
-#define CK(expr)                                                                                               \
-  do {                                                                                                         \
-    hipError_t _e = (expr);                                                                                    \
-    if (_e != hipSuccess) {                                                                                    \
-      (void)hipGetLastError();                                                                                 \
-      return err(HX_ERR_DEVICE, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__);   \
-    }                                                                                                          \
-  } while (0)
-#define RC(expr)        \
-  do {                  \
-    int _rc = (expr);   \
-    if (_rc != HX_OK)   \
-      return _rc;       \
-  } while (0)
-
-// the next staging buffer of the ring and the device table, both of at least `bytes`: waits for the copy that last read
-// the staging buffer, and for the stream before a smaller device table is replaced
-int stage_table(LinState* s, hipStream_t st, size_t bytes, int* slot_out)
-{
-  const int slot = s->next;
-  s->next = (slot + 1) % RING;
-  if (s->pending[slot]) {   // the copy that last read this staging buffer
-    CK(hipEventSynchronize(s->copied[slot]));
-    s->pending[slot] = false;
-  }
-  if (s->h_cap[slot] < bytes) {
-    if (s->h_tab[slot])
-      CK(hipHostFree(s->h_tab[slot]));
-    s->h_tab[slot] = nullptr;
-    s->h_cap[slot] = 0;
-    CK(hipHostMalloc((void**)&s->h_tab[slot], bytes, hipHostMallocDefault));
-    s->h_cap[slot] = bytes;
-  }
-  if (!s->copied[slot])
-    CK(hipEventCreateWithFlags(&s->copied[slot], hipEventDisableTiming));
-  if (s->d_cap < bytes) {
-    CK(hipStreamSynchronize(st));   // an earlier launch may still read the old table
-    hipFree(s->d_tab);
-    s->d_tab = nullptr;
-    s->d_cap = 0;
-    CK(hipMalloc((void**)&s->d_tab, bytes));
-    s->d_cap = bytes;
-  }
-  *slot_out = slot;
-  return HX_OK;
-}
+// The pieces an entry point is put together from: its own argument checks, then a Frame, the shared
+// checks of its operands, what is particular to it, a Table where it uploads one, and HX_LAUNCH_PW.
 
 int shape_of(const hx_poly* p, int* batch, std::vector<int>* idx)
 {
@@ -688,17 +636,305 @@ int shape_of(const hx_poly* p, int* batch, std::vector<int>* idx)
   return HX_OK;
 }
 
-template <int PARTS>
-void launch(int bp, dim3 grid, hipStream_t st, uint64_t* o0, uint64_t* o1, const uint64_t* tab, int n, int batch,
-            uint32_t N, int accumulate, const hx::MadRows& map, const hx::PrimeDev* primes)
+// the position of `prime` among the n of list, or -1
+int row_of(const int* list, size_t n, int prime)
 {
-  if (bp == 1)
-    HX_LAUNCH((hx::mul_add_many_kernel<PARTS, 1>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, batch, N,
-              accumulate, map, primes);
-  else
-    HX_LAUNCH((hx::mul_add_many_kernel<PARTS, 4>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, batch, N,
-              accumulate, map, primes);
+  const int* at = std::find(list, list + n, prime);
+  return at == list + n ? -1 : (int)(at - list);
 }
+
+// every address given is 16-byte aligned (a null one passes)
+template <class... P>
+bool aligned16(const P*... p)
+{
+  return ((... | (uintptr_t)p) & 15) == 0;
+}
+
+// What a call works in: the context's view under its lock, and the shape every operand is held against -- that of the
+// reference poly (the first output).
+struct Frame {
+  hx_ctx* ctx = nullptr;
+  hxi::CtxView v{};
+  std::unique_lock<std::recursive_mutex> lk;
+  int batch = 0, rows = 0, bp = 1;   // bp: the batch elements one thread takes (the kernels' BP)
+  std::vector<int> idx;              // the prime of every row
+  uint32_t N = 0;
+  const hx::PrimeDev* primes = nullptr;
+  hx::MadRows map{};                 // idx for the kernels
+
+  // no_capture: the sentence that refuses an open graph capture; nullptr for a call that can be captured (it then
+  // waits for nothing and allocates nothing)
+  int enter(hx_ctx* c, const char* no_capture)
+  {
+    ctx = c;
+    RC(hxi::ctx_enter(c, &v));
+    lk = std::unique_lock<std::recursive_mutex>(*v.mu);
+    if (no_capture && v.capturing)
+      return err(HX_ERR_UNSUPPORTED, "%s", no_capture);
+    N = v.phim;
+    primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+    return HX_OK;
+  }
+  int set_rows(const std::vector<int>& primes_of_rows)
+  {
+    if (primes_of_rows.size() > (size_t)hx::MAX_ROWS)
+      return err(HX_ERR_UNSUPPORTED, "too many rows");
+    if (&idx != &primes_of_rows)
+      idx = primes_of_rows;
+    rows = (int)idx.size();
+    for (int r = 0; r < rows; r++)
+      map.p[r] = (uint16_t)idx[r];
+    bp = batch == 1 ? 1 : 4;
+    return HX_OK;
+  }
+  int open(hx_ctx* c, const hx_poly* ref, const char* no_capture)
+  {
+    RC(enter(c, no_capture));
+    RC(shape_of(ref, &batch, &idx));
+    return set_rows(idx);
+  }
+  // the kernels take two coefficients per thread
+  int even(const char* who) const
+  {
+    if (N < 2 || (N & 1))
+      return err(HX_ERR_UNSUPPORTED, "%s needs an even number of coefficients", who);
+    return HX_OK;
+  }
+  // the prime of every row
+  int moduli(std::vector<uint64_t>* qs) const
+  {
+    qs->resize(rows);
+    for (int r = 0; r < rows; r++)
+      RC(hx_ctx_prime(ctx, idx[r], &(*qs)[r], nullptr));
+    return HX_OK;
+  }
+  // one thread per two coefficients, one row, bp batch elements
+  dim3 grid() const { return dim3((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp)); }
+};
+
+// refuses, with the caller's sentence, a poly whose batch or prime set is not the frame's
+int same_shape(const hx_poly* p, const Frame& f, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+int same_shape(const hx_poly* p, const Frame& f, const char* fmt, ...)
+{
+  int b = 0;
+  std::vector<int> idx;
+  RC(shape_of(p, &b, &idx));
+  if (b == f.batch && idx == f.idx)
+    return HX_OK;
+  char msg[400];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(msg, sizeof msg, fmt, ap);
+  va_end(ap);
+  return err(HX_ERR_INVALID, "%s", msg);
+}
+
+// The terms (c[t], in0[t], in1[t]) of hx_mul_add_many and hx_mul_add_circulant, checked against the frame: in0[t] and
+// in1[t] have its shape (`outs`: what the refusal calls it), c[t] has batch 1 or the frame's, and a row for every prime.
+struct Terms {
+  const hx_poly* const* c;
+  const hx_poly* const* in0;
+  const hx_poly* const* in1;   // null for one-part operands
+  int n;
+  std::vector<int> crow;       // [r n + t]: the row of c[t] on the prime of output row r
+  std::vector<int> cper;       // [t]: c[t] has one row per batch element
+};
+int check_terms(const Frame& f, const char* outs, Terms* T)
+{
+  const int n = T->n;
+  T->crow.resize((size_t)f.rows * n);
+  T->cper.resize(n);
+  for (int t = 0; t < n; t++) {
+    RC(same_shape(T->in0[t], f, "in0[%d] differs from %s in batch or prime set", t, outs));
+    if (T->in1)
+      RC(same_shape(T->in1[t], f, "in1[%d] differs from %s in batch or prime set", t, outs));
+    int b = 0;
+    std::vector<int> cidx;
+    RC(shape_of(T->c[t], &b, &cidx));
+    if (b != f.batch && b != 1)
+      return err(HX_ERR_INVALID, "c[%d]: batch %d is neither 1 nor %d", t, b, f.batch);
+    T->cper[t] = b == f.batch && f.batch > 1;
+    for (int r = 0; r < f.rows; r++) {
+      const int at = row_of(cidx.data(), cidx.size(), f.idx[r]);
+      if (at < 0)
+        return err(HX_ERR_INVALID, "c[%d] has no row for prime %d", t, f.idx[r]);
+      T->crow[(size_t)r * n + t] = at;
+    }
+  }
+  return HX_OK;
+}
+// The terms' words of a pointer table (read after the outputs own their rows): in[t] and in[n + t] the bases of in0[t]
+// and in1[t], crows[r n + t] the base of c[t]'s row for output row r, bit 0 set when c[t] has one row per batch
+// element.  -> the first term with a base that is not 16-byte aligned, or -1
+int fill_terms(const Frame& f, const Terms& T, uint64_t* in, uint64_t* crows)
+{
+  const int n = T.n;
+  const size_t rw = (size_t)f.batch * f.N;
+  int bad = -1;
+  for (int t = 0; t < n; t++) {
+    const uint64_t* p0 = hxi::poly_rows_read(T.in0[t]);
+    const uint64_t* p1 = T.in1 ? hxi::poly_rows_read(T.in1[t]) : nullptr;
+    const uint64_t* cb = hxi::poly_rows_read(T.c[t]);
+    in[t] = (uint64_t)(uintptr_t)p0;
+    in[n + t] = (uint64_t)(uintptr_t)p1;
+    const size_t crw = T.cper[t] ? rw : (size_t)f.N;
+    for (int r = 0; r < f.rows; r++)
+      crows[(size_t)r * n + t] = (uint64_t)(uintptr_t)(cb + (size_t)T.crow[(size_t)r * n + t] * crw) | (uint64_t)T.cper[t];
+    if (bad < 0 && !aligned16(p0, p1, cb))
+      bad = t;
+  }
+  return bad;
+}
+
+// The mask of hx_mask_split and hx_mask_blend: batch 1 or the frame's, and a row for every prime (map->brow).
+int check_mask(const Frame& f, const hx_poly* mask, int* per_elem, hx::RowMap2* map)
+{
+  int b = 0;
+  std::vector<int> midx;
+  RC(shape_of(mask, &b, &midx));
+  if (b != f.batch && b != 1)
+    return err(HX_ERR_INVALID, "mask: batch %d is neither 1 nor %d", b, f.batch);
+  *per_elem = b == f.batch && f.batch > 1;
+  for (int r = 0; r < f.rows; r++) {
+    const int at = row_of(midx.data(), midx.size(), f.idx[r]);
+    if (at < 0)
+      return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the mask has no row for prime %d)", f.idx[r]);
+    map->p[r] = (uint16_t)f.idx[r];
+    map->brow[r] = (uint16_t)at;
+  }
+  return HX_OK;
+}
+
+// Which of the four operands may not be the mask as well.
+enum MaskAlias { NO_MASK, OUTPUTS_NOT_MASK, NOTHING_IS_MASK };
+
+// The opening of a call on the one or two parts of a ciphertext, op = (c0, t0, c1, t1) or (keep0, take0, keep1, take1)
+// with their names: the second pair is there or not as one, the handles are distinct (and not the mask, as `alias`
+// says), everything belongs to one context; then the frame of op[0], whose shape the others have.  Nothing is written.
+int open_four(Frame* f, const hx_poly* const op[4], const char* const name[4], const hx_poly* mask, MaskAlias alias)
+{
+  if (!op[0] || !op[1] || (alias != NO_MASK && !mask))
+    return err(HX_ERR_INVALID, "null argument");
+  if ((op[2] == nullptr) != (op[3] == nullptr))
+    return err(HX_ERR_INVALID, "%s and %s go together (both null for a one-part ciphertext)", name[2], name[3]);
+  const int nops = op[2] ? 4 : 2;
+  for (int a = 0; a < nops; a++) {
+    if (op[a] == mask && (alias == NOTHING_IS_MASK || (alias == OUTPUTS_NOT_MASK && (a & 1) == 0)))
+      return err(HX_ERR_INVALID, "an output is also the mask");
+    for (int b = a + 1; b < nops; b++)
+      if (op[a] == op[b])
+        return err(HX_ERR_INVALID, "%s, %s, %s and %s must be different polys", name[0], name[2], name[1], name[3]);
+  }
+  hx_ctx* ctx = hxi::poly_ctx(op[0]);
+  for (int a = 1; a < nops; a++)
+    if (hxi::poly_ctx(op[a]) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  if (alias != NO_MASK && hxi::poly_ctx(mask) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  RC(f->open(ctx, op[0], nullptr));
+  for (int a = 1; a < nops; a++)
+    RC(same_shape(op[a], *f, "%s differs from %s in batch or prime set", name[a], name[0]));
+  return HX_OK;
+}
+
+// c first: one that still shares t's rows (a lazy hx_poly_copy) takes its own copy, and t's rows stay where they are
+int update_c_then_read_t(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, uint64_t* c[2], const uint64_t* t[2])
+{
+  c[0] = c[1] = nullptr;
+  RC(hxi::poly_rows_update(c0, &c[0]));
+  if (c1)
+    RC(hxi::poly_rows_update(c1, &c[1]));
+  t[0] = hxi::poly_rows_read(t0);
+  t[1] = t1 ? hxi::poly_rows_read(t1) : nullptr;
+  return HX_OK;
+}
+
+// the device buffer *p of at least `bytes`: the stream is waited for before a smaller one is replaced
+int grow(hipStream_t st, void** p, size_t* cap, size_t bytes)
+{
+  if (*cap >= bytes)
+    return HX_OK;
+  CK(hipStreamSynchronize(st));   // an earlier launch may still read the old buffer
+  hipFree(*p);
+  *p = nullptr;
+  *cap = 0;
+  CK(hipMalloc(p, bytes));
+  *cap = bytes;
+  return HX_OK;
+}
+
+// The table a call uploads.  acquire: the next staging buffer of the context's ring (h, to be filled) and the device
+// table (d), both of at least `words`; it waits for the copy that last read the staging buffer.  commit: the copy, the
+// event that marks it done, and the buffer's `pending` flag.  An entry point acquires after its last check and before
+// it takes an output, so that a failure here touches none.
+struct Table {
+  LinState* s = nullptr;
+  int slot = 0;
+  size_t bytes = 0;
+  uint64_t* h = nullptr;
+  uint64_t* d = nullptr;
+  int acquire(const Frame& f, size_t words)
+  {
+    if (!*f.v.linalg) {
+      *f.v.linalg = new LinState();
+      *f.v.linalg_free = state_free;
+    }
+    s = static_cast<LinState*>(*f.v.linalg);
+    bytes = words * 8;
+    slot = s->next;
+    s->next = (slot + 1) % RING;
+    if (s->pending[slot]) {   // the copy that last read this staging buffer
+      CK(hipEventSynchronize(s->copied[slot]));
+      s->pending[slot] = false;
+    }
+    if (s->h_cap[slot] < bytes) {
+      if (s->h_tab[slot])
+        CK(hipHostFree(s->h_tab[slot]));
+      s->h_tab[slot] = nullptr;
+      s->h_cap[slot] = 0;
+      CK(hipHostMalloc((void**)&s->h_tab[slot], bytes, hipHostMallocDefault));
+      s->h_cap[slot] = bytes;
+    }
+    if (!s->copied[slot])
+      CK(hipEventCreateWithFlags(&s->copied[slot], hipEventDisableTiming));
+    RC(grow(f.v.stream, (void**)&s->d_tab, &s->d_cap, bytes));
+    h = s->h_tab[slot];
+    d = s->d_tab;
+    return HX_OK;
+  }
+  // hx_hoisted_automorph_sum's gather tables, `words` of 32 bits
+  int perm(const Frame& f, size_t words, uint32_t** out)
+  {
+    RC(grow(f.v.stream, (void**)&s->d_perm, &s->perm_cap, words * 4));
+    *out = s->d_perm;
+    return HX_OK;
+  }
+  int commit(hipStream_t st)
+  {
+    CK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
+    CK(hipEventRecord(s->copied[slot], st));
+    s->pending[slot] = true;
+    return HX_OK;
+  }
+};
+
+// One launch of 256 threads per workgroup on one of two kernels, and on one of K<PARTS, X> for PARTS in {1, 2} and X
+// in {NARROW, WIDE}.  HX_LAUNCH names a kernel to the profiler by the text of its argument, so every case is written
+// out with literal template arguments.
+#define HX_LAUNCH_W(wide, KN, KW, grid, st, ...)               \
+  do {                                                         \
+    if (!(wide))                                               \
+      HX_LAUNCH(KN, grid, dim3(256), 0, st, __VA_ARGS__);      \
+    else                                                       \
+      HX_LAUNCH(KW, grid, dim3(256), 0, st, __VA_ARGS__);      \
+  } while (0)
+#define HX_LAUNCH_PW(K, parts, wide, NARROW, WIDE, grid, st, ...)                                  \
+  do {                                                                                             \
+    if ((parts) == 2)                                                                              \
+      HX_LAUNCH_W(wide, (hx::K<2, NARROW>), (hx::K<2, WIDE>), grid, st, __VA_ARGS__);              \
+    else                                                                                           \
+      HX_LAUNCH_W(wide, (hx::K<1, NARROW>), (hx::K<1, WIDE>), grid, st, __VA_ARGS__);              \
+  } while (0)
 
 }  // namespace
 
@@ -713,7 +949,6 @@ extern "C" int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* cons
     return err(HX_ERR_INVALID, "hx_mul_add_many needs at least one term (n = %d)", n);
   if (out0 == out1)
     return err(HX_ERR_INVALID, "out0 and out1 are the same poly");
-  const int parts = out1 ? 2 : 1;
   hx_ctx* ctx = hxi::poly_ctx(out0);
   for (int t = 0; t < n; t++) {
     if (!c[t] || !in0[t] || (in1 && !in1[t]))
@@ -726,115 +961,34 @@ extern "C" int hx_mul_add_many(hx_poly* out0, hx_poly* out1, const hx_poly* cons
   }
   if (out1 && hxi::poly_ctx(out1) != ctx)
     return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  if (v.capturing)
-    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_many uploads a pointer table and cannot be captured in a graph");
-  int batch = 0, b2 = 0;
-  std::vector<int> idx, other;
-  RC(shape_of(out0, &batch, &idx));
-  const int rows = (int)idx.size();
-  if (rows > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
-  if (out1) {
-    RC(shape_of(out1, &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "out0 and out1 differ in batch or prime set");
-  }
-  const uint32_t N = v.phim;
-  if (N < 2 || (N & 1))
-    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_many needs an even number of coefficients");
-  // host table: the shapes are checked while it is filled; device addresses go in after the outputs own their rows
-  std::vector<int> crow((size_t)rows * n), cper(n);
-  for (int t = 0; t < n; t++) {
-    RC(shape_of(in0[t], &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "in0[%d] differs from the output in batch or prime set", t);
-    if (in1) {
-      RC(shape_of(in1[t], &b2, &other));
-      if (b2 != batch || other != idx)
-        return err(HX_ERR_INVALID, "in1[%d] differs from the output in batch or prime set", t);
-    }
-    RC(shape_of(c[t], &b2, &other));
-    if (b2 != batch && b2 != 1)
-      return err(HX_ERR_INVALID, "c[%d]: batch %d is neither 1 nor %d", t, b2, batch);
-    cper[t] = b2 == batch && batch > 1;
-    for (int r = 0; r < rows; r++) {
-      int at = -1;
-      for (size_t j = 0; j < other.size(); j++)
-        if (other[j] == idx[r]) {
-          at = (int)j;
-          break;
-        }
-      if (at < 0)
-        return err(HX_ERR_INVALID, "c[%d] has no row for prime %d", t, idx[r]);
-      crow[(size_t)r * n + t] = at;
-    }
-  }
-  if (rows == 0)
+  Frame f;
+  RC(f.open(ctx, out0, "hx_mul_add_many uploads a pointer table and cannot be captured in a graph"));
+  if (out1)
+    RC(same_shape(out1, f, "out0 and out1 differ in batch or prime set"));
+  RC(f.even("hx_mul_add_many"));
+  Terms T{c, in0, in1, n, {}, {}};
+  RC(check_terms(f, "the output", &T));
+  if (f.rows == 0)
     return HX_OK;
-  if (!*v.linalg) {
-    *v.linalg = new LinState();
-    *v.linalg_free = state_free;
-  }
-  LinState* s = static_cast<LinState*>(*v.linalg);
-  const hipStream_t st = v.stream;
-  const size_t words = (size_t)n * (2 + rows), bytes = words * 8;
-  int slot = 0;
-  RC(stage_table(s, st, bytes, &slot));
+  // table (kernel's layout): the bases of in0, of in1, then the rows of c
+  Table tab;
+  RC(tab.acquire(f, (size_t)n * (2 + f.rows)));
+  // the outputs first: one that still shares an input's rows (a lazy hx_poly_copy) owns its rows before the inputs'
+  // addresses are read into the table
   uint64_t *o0 = nullptr, *o1 = nullptr;
-  if (accumulate) {
-    RC(hxi::poly_rows_update(out0, &o0));
-    if (out1)
-      RC(hxi::poly_rows_update(out1, &o1));
-  } else {
-    RC(hxi::poly_rows_write(out0, &o0));
-    if (out1)
-      RC(hxi::poly_rows_write(out1, &o1));
-  }
-  uint64_t* h = s->h_tab[slot];
-  const size_t rw = (size_t)batch * N;
-  for (int t = 0; t < n; t++) {
-    h[t] = (uint64_t)(uintptr_t)hxi::poly_rows_read(in0[t]);
-    h[n + t] = in1 ? (uint64_t)(uintptr_t)hxi::poly_rows_read(in1[t]) : 0;
-    const uint64_t* cb = hxi::poly_rows_read(c[t]);
-    const size_t crw = cper[t] ? rw : (size_t)N;
-    for (int r = 0; r < rows; r++)
-      h[2 * (size_t)n + (size_t)r * n + t] =
-          (uint64_t)(uintptr_t)(cb + (size_t)crow[(size_t)r * n + t] * crw) | (uint64_t)cper[t];
-    if ((h[t] | h[n + t] | (uint64_t)(uintptr_t)cb) & 15)
-      return err(HX_ERR_INVALID, "term %d: rows are not 16-byte aligned", t);
-  }
-  if (((uint64_t)(uintptr_t)o0 | (uint64_t)(uintptr_t)o1) & 15)
+  RC(accumulate ? hxi::poly_rows_update(out0, &o0) : hxi::poly_rows_write(out0, &o0));
+  if (out1)
+    RC(accumulate ? hxi::poly_rows_update(out1, &o1) : hxi::poly_rows_write(out1, &o1));
+  const int bad = fill_terms(f, T, tab.h, tab.h + 2 * (size_t)n);
+  if (bad >= 0)
+    return err(HX_ERR_INVALID, "term %d: rows are not 16-byte aligned", bad);
+  if (!aligned16(o0, o1))
     return err(HX_ERR_INVALID, "output rows are not 16-byte aligned");
-  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
-  CK(hipEventRecord(s->copied[slot], st));
-  s->pending[slot] = true;
-  hx::MadRows map;
-  for (int r = 0; r < rows; r++)
-    map.p[r] = (uint16_t)idx[r];
-  const int bp = batch == 1 ? 1 : 4;
-  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
-  if (parts == 2)
-    launch<2>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
-  else
-    launch<1>(bp, grid, st, o0, o1, s->d_tab, n, batch, N, accumulate ? 1 : 0, map, primes);
+  RC(tab.commit(f.v.stream));
+  HX_LAUNCH_PW(mul_add_many_kernel, out1 ? 2 : 1, f.bp != 1, 1, 4, f.grid(), f.v.stream, o0, o1, hx::as_ro(tab.d), n, f.batch,
+               f.N, accumulate ? 1 : 0, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
-}
-
-template <int PARTS>
-static void launch_circulant(int ob, dim3 grid, hipStream_t st, const uint64_t* tab, int d, int nout, int nblocks, int batch,
-                             uint32_t N, const hx::MadRows& map, const hx::PrimeDev* primes)
-{
-  if (ob == 4)
-    HX_LAUNCH((hx::mul_add_circulant_kernel<PARTS, 4>), grid, dim3(256), 0, st, hx::as_ro(tab), d, nout, nblocks, batch, N, map,
-              primes);
-  else
-    HX_LAUNCH((hx::mul_add_circulant_kernel<PARTS, 8>), grid, dim3(256), 0, st, hx::as_ro(tab), d, nout, nblocks, batch, N, map,
-              primes);
 }
 
 extern "C" int hx_mul_add_circulant(hx_poly* const* out0, hx_poly* const* out1, int nout, const hx_poly* const* c,
@@ -848,7 +1002,6 @@ extern "C" int hx_mul_add_circulant(hx_poly* const* out0, hx_poly* const* out1, 
     return err(d < 1 ? HX_ERR_INVALID : HX_ERR_UNSUPPORTED, "hx_mul_add_circulant takes 1 <= d <= %d (d = %d)", hx::CIRC_MAX_D, d);
   if (nout < 1 || nout > d)
     return err(HX_ERR_INVALID, "hx_mul_add_circulant takes 1 <= nout <= d (nout = %d, d = %d)", nout, d);
-  const int parts = out1 ? 2 : 1;
   // every poly, null checks and aliasing first: a refused call touches no output
   std::vector<const hx_poly*> outs, ins;
   for (int i = 0; i < nout; i++) {
@@ -883,397 +1036,148 @@ extern "C" int hx_mul_add_circulant(hx_poly* const* out0, hx_poly* const* out1, 
   for (const hx_poly* p : ins)
     if (hxi::poly_ctx(p) != ctx)
       return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  if (v.capturing)
-    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_circulant uploads a pointer table and cannot be captured in a graph");
-  int batch = 0, b2 = 0;
-  std::vector<int> idx, other;
-  RC(shape_of(out0[0], &batch, &idx));
-  const int rows = (int)idx.size();
-  if (rows > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
-  for (size_t i = 1; i < outs.size(); i++) {
-    RC(shape_of(outs[i], &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "the outputs differ in batch or prime set");
-  }
-  const uint32_t N = v.phim;
-  if (N < 2 || (N & 1))
-    return err(HX_ERR_UNSUPPORTED, "hx_mul_add_circulant needs an even number of coefficients");
-  std::vector<int> crow((size_t)rows * d), cper(d);
-  for (int t = 0; t < d; t++) {
-    RC(shape_of(in0[t], &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "in0[%d] differs from the outputs in batch or prime set", t);
-    if (in1) {
-      RC(shape_of(in1[t], &b2, &other));
-      if (b2 != batch || other != idx)
-        return err(HX_ERR_INVALID, "in1[%d] differs from the outputs in batch or prime set", t);
-    }
-    RC(shape_of(c[t], &b2, &other));
-    if (b2 != batch && b2 != 1)
-      return err(HX_ERR_INVALID, "c[%d]: batch %d is neither 1 nor %d", t, b2, batch);
-    cper[t] = b2 == batch && batch > 1;
-    for (int r = 0; r < rows; r++) {
-      int at = -1;
-      for (size_t j = 0; j < other.size(); j++)
-        if (other[j] == idx[r]) {
-          at = (int)j;
-          break;
-        }
-      if (at < 0)
-        return err(HX_ERR_INVALID, "c[%d] has no row for prime %d", t, idx[r]);
-      crow[(size_t)r * d + t] = at;
-    }
-  }
-  if (rows == 0)
+  Frame f;
+  RC(f.open(ctx, out0[0], "hx_mul_add_circulant uploads a pointer table and cannot be captured in a graph"));
+  for (size_t i = 1; i < outs.size(); i++)
+    RC(same_shape(outs[i], f, "the outputs differ in batch or prime set"));
+  RC(f.even("hx_mul_add_circulant"));
+  Terms T{c, in0, in1, d, {}, {}};
+  RC(check_terms(f, "the outputs", &T));
+  if (f.rows == 0)
     return HX_OK;
-  const int ob = nout <= 4 ? 4 : 8;
+  const int ob = nout <= 4 ? 4 : 8;   // the kernel's OB: outputs per block
   const int nblocks = (nout + ob - 1) / ob;
-  if ((size_t)batch * nblocks > 65535)
-    return err(HX_ERR_UNSUPPORTED, "batch %d x %d output blocks exceeds the grid", batch, nblocks);
-  if (!*v.linalg) {
-    *v.linalg = new LinState();
-    *v.linalg_free = state_free;
-  }
-  LinState* s = static_cast<LinState*>(*v.linalg);
-  const hipStream_t st = v.stream;
-  const size_t words = 2 * (size_t)d + 2 * (size_t)nout + (size_t)rows * d, bytes = words * 8;
-  int slot = 0;
-  RC(stage_table(s, st, bytes, &slot));
-  uint64_t* h = s->h_tab[slot];
-  uint64_t align = 0;
+  if ((size_t)f.batch * nblocks > 65535)
+    return err(HX_ERR_UNSUPPORTED, "batch %d x %d output blocks exceeds the grid", f.batch, nblocks);
+  // table (kernel's layout): the bases of in0, of in1, of out0, of out1, then the rows of c
+  Table tab;
+  RC(tab.acquire(f, 2 * (size_t)d + 2 * (size_t)nout + (size_t)f.rows * d));
+  uint64_t* ho = tab.h + 2 * (size_t)d;
+  bool aligned = true;
   for (int i = 0; i < nout; i++) {
     uint64_t *o0 = nullptr, *o1 = nullptr;
     RC(hxi::poly_rows_write(out0[i], &o0));
     if (out1)
       RC(hxi::poly_rows_write(out1[i], &o1));
-    h[2 * (size_t)d + i] = (uint64_t)(uintptr_t)o0;
-    h[2 * (size_t)d + nout + i] = (uint64_t)(uintptr_t)o1;
-    align |= h[2 * (size_t)d + i] | h[2 * (size_t)d + nout + i];
+    ho[i] = (uint64_t)(uintptr_t)o0;
+    ho[nout + i] = (uint64_t)(uintptr_t)o1;
+    aligned = aligned && aligned16(o0, o1);
   }
-  const size_t rw = (size_t)batch * N;
-  for (int t = 0; t < d; t++) {
-    h[t] = (uint64_t)(uintptr_t)hxi::poly_rows_read(in0[t]);
-    h[d + t] = in1 ? (uint64_t)(uintptr_t)hxi::poly_rows_read(in1[t]) : 0;
-    const uint64_t* cb = hxi::poly_rows_read(c[t]);
-    const size_t crw = cper[t] ? rw : (size_t)N;
-    for (int r = 0; r < rows; r++)
-      h[2 * (size_t)d + 2 * (size_t)nout + (size_t)r * d + t] =
-          (uint64_t)(uintptr_t)(cb + (size_t)crow[(size_t)r * d + t] * crw) | (uint64_t)cper[t];
-    align |= h[t] | h[d + t] | (uint64_t)(uintptr_t)cb;
-  }
-  if (align & 15)
+  if (fill_terms(f, T, tab.h, ho + 2 * (size_t)nout) >= 0 || !aligned)
     return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
-  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
-  CK(hipEventRecord(s->copied[slot], st));
-  s->pending[slot] = true;
-  hx::MadRows map;
-  for (int r = 0; r < rows; r++)
-    map.p[r] = (uint16_t)idx[r];
-  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)(batch * nblocks));
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
-  if (parts == 2)
-    launch_circulant<2>(ob, grid, st, s->d_tab, d, nout, nblocks, batch, N, map, primes);
-  else
-    launch_circulant<1>(ob, grid, st, s->d_tab, d, nout, nblocks, batch, N, map, primes);
+  RC(tab.commit(f.v.stream));
+  const dim3 grid((f.N / 2 + 255) / 256, (unsigned)f.rows, (unsigned)(f.batch * nblocks));
+  HX_LAUNCH_PW(mul_add_circulant_kernel, out1 ? 2 : 1, ob == 8, 4, 8, grid, f.v.stream, hx::as_ro(tab.d), d, nout, nblocks,
+               f.batch, f.N, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
 }
 
-template <int PARTS>
-static void launch_split(int bp, dim3 grid, hipStream_t st, uint64_t* k0, uint64_t* k1, uint64_t* t0, uint64_t* t1,
-                         const uint64_t* mask, int per_elem, int batch, uint32_t N, const hx::RowMap2& map,
-                         const hx::PrimeDev* primes)
-{
-  if (bp == 1)
-    HX_LAUNCH((hx::mask_split_kernel<PARTS, 1>), grid, dim3(256), 0, st, k0, k1, t0, t1, mask, per_elem, batch, N, map,
-              primes);
-  else
-    HX_LAUNCH((hx::mask_split_kernel<PARTS, 4>), grid, dim3(256), 0, st, k0, k1, t0, t1, mask, per_elem, batch, N, map,
-              primes);
-}
-
 extern "C" int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_poly* take1, const hx_poly* mask)
 {
-  if (!keep0 || !take0 || !mask)
-    return err(HX_ERR_INVALID, "null argument");
-  if ((keep1 == nullptr) != (take1 == nullptr))
-    return err(HX_ERR_INVALID, "keep1 and take1 go together (both null for a one-part ciphertext)");
-  const int parts = keep1 ? 2 : 1;
-  hx_poly* outs[4] = {keep0, take0, keep1, take1};
-  for (int a = 0; a < 2 * parts; a++) {
-    if (outs[a] == mask)
-      return err(HX_ERR_INVALID, "an output is also the mask");
-    for (int b = a + 1; b < 2 * parts; b++)
-      if (outs[a] == outs[b])
-        return err(HX_ERR_INVALID, "keep0, keep1, take0 and take1 must be different polys");
-  }
-  hx_ctx* ctx = hxi::poly_ctx(keep0);
-  for (int a = 1; a < 2 * parts; a++)
-    if (hxi::poly_ctx(outs[a]) != ctx)
-      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  if (hxi::poly_ctx(mask) != ctx)
-    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  int batch = 0, b2 = 0;
-  std::vector<int> idx, other;
-  RC(shape_of(keep0, &batch, &idx));
-  const int rows = (int)idx.size();
-  if (rows > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  const hx_poly* const ops[4] = {keep0, take0, keep1, take1};
   static const char* const name[4] = {"keep0", "take0", "keep1", "take1"};
-  for (int a = 1; a < 2 * parts; a++) {
-    RC(shape_of(outs[a], &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "%s differs from keep0 in batch or prime set", name[a]);
-  }
-  RC(shape_of(mask, &b2, &other));
-  if (b2 != batch && b2 != 1)
-    return err(HX_ERR_INVALID, "mask: batch %d is neither 1 nor %d", b2, batch);
-  const int per_elem = b2 == batch && batch > 1;
+  Frame f;
+  RC(open_four(&f, ops, name, mask, NOTHING_IS_MASK));
+  int per_elem = 0;
   hx::RowMap2 map;
-  for (int r = 0; r < rows; r++) {
-    int at = -1;
-    for (size_t j = 0; j < other.size(); j++)
-      if (other[j] == idx[r]) {
-        at = (int)j;
-        break;
-      }
-    if (at < 0)
-      return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the mask has no row for prime %d)", idx[r]);
-    map.p[r] = (uint16_t)idx[r];
-    map.brow[r] = (uint16_t)at;
-  }
-  const uint32_t N = v.phim;
-  if (N < 2 || (N & 1))
-    return err(HX_ERR_UNSUPPORTED, "hx_mask_split needs an even number of coefficients");
-  if (rows == 0)
+  RC(check_mask(f, mask, &per_elem, &map));
+  RC(f.even("hx_mask_split"));
+  if (f.rows == 0)
     return HX_OK;
-  if (v.no_mask_split) {   // HX_NO_MASK_SPLIT: the sequence the kernel replaces
+  const int parts = keep1 ? 2 : 1;
+  hx_poly* const keep[2] = {keep0, keep1};
+  hx_poly* const take[2] = {take0, take1};
+  if (f.v.no_mask_split) {   // HX_NO_MASK_SPLIT: the sequence the kernel replaces
     for (int a = 0; a < parts; a++) {
-      RC(hx_poly_copy(outs[2 * a + 1], outs[2 * a]));
-      RC(hx_mul(outs[2 * a + 1], mask));
-      RC(hx_sub(outs[2 * a], outs[2 * a + 1]));
+      RC(hx_poly_copy(take[a], keep[a]));
+      RC(hx_mul(take[a], mask));
+      RC(hx_sub(keep[a], take[a]));
     }
     return HX_OK;
   }
   // take first: one that still shares keep's rows (a lazy hx_poly_copy) lets go of them, and keep is then updated in
   // place without a copy
-  uint64_t* d[4] = {nullptr, nullptr, nullptr, nullptr};
+  uint64_t *k[2] = {nullptr, nullptr}, *t[2] = {nullptr, nullptr};
   for (int a = 0; a < parts; a++)
-    RC(hxi::poly_rows_write(outs[2 * a + 1], &d[2 * a + 1]));
+    RC(hxi::poly_rows_write(take[a], &t[a]));
   for (int a = 0; a < parts; a++)
-    RC(hxi::poly_rows_update(outs[2 * a], &d[2 * a]));
+    RC(hxi::poly_rows_update(keep[a], &k[a]));
   const uint64_t* mp = hxi::poly_rows_read(mask);
-  if (((uint64_t)(uintptr_t)d[0] | (uint64_t)(uintptr_t)d[1] | (uint64_t)(uintptr_t)d[2] | (uint64_t)(uintptr_t)d[3] |
-       (uint64_t)(uintptr_t)mp) & 15)
+  if (!aligned16(k[0], k[1], t[0], t[1], mp))
     return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
-  const int bp = batch == 1 ? 1 : 4;
-  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
-  if (parts == 2)
-    launch_split<2>(bp, grid, v.stream, d[0], d[2], d[1], d[3], mp, per_elem, batch, N, map, primes);
-  else
-    launch_split<1>(bp, grid, v.stream, d[0], nullptr, d[1], nullptr, mp, per_elem, batch, N, map, primes);
+  HX_LAUNCH_PW(mask_split_kernel, parts, f.bp != 1, 1, 4, f.grid(), f.v.stream, k[0], k[1], t[0], t[1], mp, per_elem, f.batch,
+               f.N, map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
-}
-
-template <int PARTS>
-static void launch_blend(int bp, dim3 grid, hipStream_t st, uint64_t* c0, uint64_t* c1, const uint64_t* t0,
-                         const uint64_t* t1, const uint64_t* mask, int per_elem, int batch, uint32_t N,
-                         const hx::RowMap2& map, const hx::PrimeDev* primes)
-{
-  if (bp == 1)
-    HX_LAUNCH((hx::mask_blend_kernel<PARTS, 1>), grid, dim3(256), 0, st, c0, c1, t0, t1, mask, per_elem, batch, N, map,
-              primes);
-  else
-    HX_LAUNCH((hx::mask_blend_kernel<PARTS, 4>), grid, dim3(256), 0, st, c0, c1, t0, t1, mask, per_elem, batch, N, map,
-              primes);
 }
 
 extern "C" int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const hx_poly* mask)
 {
-  if (!c0 || !t0 || !mask)
-    return err(HX_ERR_INVALID, "null argument");
-  if ((c1 == nullptr) != (t1 == nullptr))
-    return err(HX_ERR_INVALID, "c1 and t1 go together (both null for a one-part ciphertext)");
-  const int parts = c1 ? 2 : 1;
-  const hx_poly* ops[4] = {c0, t0, c1, t1};
-  for (int a = 0; a < 2 * parts; a++) {
-    if (ops[a] == mask && (a & 1) == 0)
-      return err(HX_ERR_INVALID, "an output is also the mask");
-    for (int b = a + 1; b < 2 * parts; b++)
-      if (ops[a] == ops[b])
-        return err(HX_ERR_INVALID, "c0, c1, t0 and t1 must be different polys");
-  }
-  hx_ctx* ctx = hxi::poly_ctx(c0);
-  for (int a = 1; a < 2 * parts; a++)
-    if (hxi::poly_ctx(ops[a]) != ctx)
-      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  if (hxi::poly_ctx(mask) != ctx)
-    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  int batch = 0, b2 = 0;
-  std::vector<int> idx, other;
-  RC(shape_of(c0, &batch, &idx));
-  const int rows = (int)idx.size();
-  if (rows > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  const hx_poly* const ops[4] = {c0, t0, c1, t1};
   static const char* const name[4] = {"c0", "t0", "c1", "t1"};
-  for (int a = 1; a < 2 * parts; a++) {
-    RC(shape_of(ops[a], &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "%s differs from c0 in batch or prime set", name[a]);
-  }
-  RC(shape_of(mask, &b2, &other));
-  if (b2 != batch && b2 != 1)
-    return err(HX_ERR_INVALID, "mask: batch %d is neither 1 nor %d", b2, batch);
-  const int per_elem = b2 == batch && batch > 1;
+  Frame f;
+  RC(open_four(&f, ops, name, mask, OUTPUTS_NOT_MASK));   // (t is read only: it may be the mask)
+  int per_elem = 0;
   hx::RowMap2 map;
-  for (int r = 0; r < rows; r++) {
-    int at = -1;
-    for (size_t j = 0; j < other.size(); j++)
-      if (other[j] == idx[r]) {
-        at = (int)j;
-        break;
-      }
-    if (at < 0)
-      return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the mask has no row for prime %d)", idx[r]);
-    map.p[r] = (uint16_t)idx[r];
-    map.brow[r] = (uint16_t)at;
-  }
-  const uint32_t N = v.phim;
-  if (N < 2 || (N & 1))
-    return err(HX_ERR_UNSUPPORTED, "hx_mask_blend needs an even number of coefficients");
-  if (rows == 0)
+  RC(check_mask(f, mask, &per_elem, &map));
+  RC(f.even("hx_mask_blend"));
+  if (f.rows == 0)
     return HX_OK;
-  // c first: one that still shares t's rows (a lazy hx_poly_copy) takes its own copy, and t's rows stay where they are
-  uint64_t* d[2] = {nullptr, nullptr};
-  RC(hxi::poly_rows_update(c0, &d[0]));
-  if (c1)
-    RC(hxi::poly_rows_update(c1, &d[1]));
-  const uint64_t* s0 = hxi::poly_rows_read(t0);
-  const uint64_t* s1 = t1 ? hxi::poly_rows_read(t1) : nullptr;
+  uint64_t* c[2];
+  const uint64_t* t[2];
+  RC(update_c_then_read_t(c0, c1, t0, t1, c, t));
   const uint64_t* mp = hxi::poly_rows_read(mask);
-  if (((uint64_t)(uintptr_t)d[0] | (uint64_t)(uintptr_t)d[1] | (uint64_t)(uintptr_t)s0 | (uint64_t)(uintptr_t)s1 |
-       (uint64_t)(uintptr_t)mp) & 15)
+  if (!aligned16(c[0], c[1], t[0], t[1], mp))
     return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
-  const int bp = batch == 1 ? 1 : 4;
-  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
-  if (parts == 2)
-    launch_blend<2>(bp, grid, v.stream, d[0], d[1], s0, s1, mp, per_elem, batch, N, map, primes);
-  else
-    launch_blend<1>(bp, grid, v.stream, d[0], nullptr, s0, nullptr, mp, per_elem, batch, N, map, primes);
+  HX_LAUNCH_PW(mask_blend_kernel, c1 ? 2 : 1, f.bp != 1, 1, 4, f.grid(), f.v.stream, c[0], c[1], t[0], t[1], mp, per_elem,
+               f.batch, f.N, map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
-}
-
-template <int PARTS>
-static void launch_scaled_sub(int bp, dim3 grid, hipStream_t st, uint64_t* c0, uint64_t* c1, const uint64_t* t0,
-                              const uint64_t* t1, int batch, uint32_t N, int row_base, const hx::ScaledSubRows& rows,
-                              const hx::PrimeDev* primes)
-{
-  if (bp == 1)
-    HX_LAUNCH((hx::scaled_sub_kernel<PARTS, 1>), grid, dim3(256), 0, st, c0, c1, t0, t1, batch, N, row_base, rows, primes);
-  else
-    HX_LAUNCH((hx::scaled_sub_kernel<PARTS, 4>), grid, dim3(256), 0, st, c0, c1, t0, t1, batch, N, row_base, rows, primes);
 }
 
 extern "C" int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const uint64_t* u_per_row,
                              const uint64_t* v_per_row)
 {
-  if (!c0 || !t0 || !u_per_row || !v_per_row)
+  if (!u_per_row || !v_per_row)
     return err(HX_ERR_INVALID, "null argument");
-  if ((c1 == nullptr) != (t1 == nullptr))
-    return err(HX_ERR_INVALID, "c1 and t1 go together (both null for a one-part ciphertext)");
-  const int parts = c1 ? 2 : 1;
-  const hx_poly* ops[4] = {c0, t0, c1, t1};
-  for (int a = 0; a < 2 * parts; a++)
-    for (int b = a + 1; b < 2 * parts; b++)
-      if (ops[a] == ops[b])
-        return err(HX_ERR_INVALID, "c0, c1, t0 and t1 must be different polys");
-  hx_ctx* ctx = hxi::poly_ctx(c0);
-  for (int a = 1; a < 2 * parts; a++)
-    if (hxi::poly_ctx(ops[a]) != ctx)
-      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  int batch = 0, b2 = 0;
-  std::vector<int> idx, other;
-  RC(shape_of(c0, &batch, &idx));
-  const int rows = (int)idx.size();
-  if (rows > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  const hx_poly* const ops[4] = {c0, t0, c1, t1};
   static const char* const name[4] = {"c0", "t0", "c1", "t1"};
-  for (int a = 1; a < 2 * parts; a++) {
-    RC(shape_of(ops[a], &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "%s differs from c0 in batch or prime set", name[a]);
-  }
-  const uint32_t N = v.phim;
-  if (N < 2 || (N & 1))
-    return err(HX_ERR_UNSUPPORTED, "hx_scaled_sub needs an even number of coefficients");
-  std::vector<uint64_t> qs(rows);
-  for (int r = 0; r < rows; r++) {
-    RC(hx_ctx_prime(ctx, idx[r], &qs[r], nullptr));
+  Frame f;
+  RC(open_four(&f, ops, name, nullptr, NO_MASK));
+  RC(f.even("hx_scaled_sub"));
+  std::vector<uint64_t> qs;
+  RC(f.moduli(&qs));
+  for (int r = 0; r < f.rows; r++)
     if (u_per_row[r] >= qs[r] || v_per_row[r] >= qs[r])
       return err(HX_ERR_INVALID, "row %d: the scalars are not reduced modulo the row's prime %llu", r,
                  (unsigned long long)qs[r]);
-  }
-  if (rows == 0)
+  if (f.rows == 0)
     return HX_OK;
-  // c first: one that still shares t's rows (a lazy hx_poly_copy) takes its own copy, and t's rows stay where they are
-  uint64_t* d[2] = {nullptr, nullptr};
-  RC(hxi::poly_rows_update(c0, &d[0]));
-  if (c1)
-    RC(hxi::poly_rows_update(c1, &d[1]));
-  const uint64_t* s0 = hxi::poly_rows_read(t0);
-  const uint64_t* s1 = t1 ? hxi::poly_rows_read(t1) : nullptr;
-  if (((uint64_t)(uintptr_t)d[0] | (uint64_t)(uintptr_t)d[1] | (uint64_t)(uintptr_t)s0 | (uint64_t)(uintptr_t)s1) & 15)
+  uint64_t* c[2];
+  const uint64_t* t[2];
+  RC(update_c_then_read_t(c0, c1, t0, t1, c, t));
+  if (!aligned16(c[0], c[1], t[0], t[1]))
     return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
-  const int bp = batch == 1 ? 1 : 4;
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
-  for (int base = 0; base < rows; base += hx::SS_ROWS) {
-    const int nr = std::min(rows - base, (int)hx::SS_ROWS);
+  // the scalars travel in the kernel's argument block, SS_ROWS rows of them per launch
+  dim3 grid = f.grid();
+  for (int base = 0; base < f.rows; base += hx::SS_ROWS) {
+    const int nr = std::min(f.rows - base, (int)hx::SS_ROWS);
     hx::ScaledSubRows sr{};
     for (int r = 0; r < nr; r++) {
       const uint64_t q = qs[base + r];
-      sr.p[r] = (uint16_t)idx[base + r];
+      sr.p[r] = (uint16_t)f.idx[base + r];
       sr.u[r] = u_per_row[base + r];
       sr.up[r] = hxh::shoup(sr.u[r], q);
       sr.v[r] = v_per_row[base + r];
       sr.vp[r] = hxh::shoup(sr.v[r], q);
     }
-    const dim3 grid((N / 2 + 255) / 256, (unsigned)nr, (unsigned)((batch + bp - 1) / bp));
-    if (parts == 2)
-      launch_scaled_sub<2>(bp, grid, v.stream, d[0], d[1], s0, s1, batch, N, base, sr, primes);
-    else
-      launch_scaled_sub<1>(bp, grid, v.stream, d[0], nullptr, s0, nullptr, batch, N, base, sr, primes);
+    grid.y = (unsigned)nr;
+    HX_LAUNCH_PW(scaled_sub_kernel, c1 ? 2 : 1, f.bp != 1, 1, 4, grid, f.v.stream, c[0], c[1], t[0], t[1], f.batch, f.N, base,
+                 sr, f.primes);
     CK(hipGetLastError());
   }
   return HX_OK;
-}
-
-template <int PARTS>
-static void launch_lin_comb(int bp, dim3 grid, hipStream_t st, uint64_t* o0, uint64_t* o1, const uint64_t* tab, int n,
-                            int rows, int batch, uint32_t N, const hx::MadRows& map, const hx::PrimeDev* primes)
-{
-  if (bp == 1)
-    HX_LAUNCH((hx::lin_comb_kernel<PARTS, 1>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, rows, batch, N, map,
-              primes);
-  else
-    HX_LAUNCH((hx::lin_comb_kernel<PARTS, 4>), grid, dim3(256), 0, st, o0, o1, hx::as_ro(tab), n, rows, batch, N, map,
-              primes);
 }
 
 extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* in0, const hx_poly* const* in1, int n,
@@ -1289,7 +1193,6 @@ extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* i
     return err(HX_ERR_UNSUPPORTED, "hx_lin_comb takes at most %d terms (n = %d)", hx::MAD_CHUNK, n);
   if (out0 == out1)
     return err(HX_ERR_INVALID, "out0 and out1 are the same poly");
-  const int parts = out1 ? 2 : 1;
   hx_ctx* ctx = hxi::poly_ctx(out0);
   for (int t = 0; t < n; t++) {
     if (!in0[t] || (in1 && !in1[t]))
@@ -1301,28 +1204,15 @@ extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* i
   }
   if (out1 && hxi::poly_ctx(out1) != ctx)
     return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  if (v.capturing)
-    return err(HX_ERR_UNSUPPORTED, "hx_lin_comb uploads a table of pointers and weights and cannot be captured in a graph");
-  int batch = 0, b2 = 0;
-  std::vector<int> idx, other, other1;
-  RC(shape_of(out0, &batch, &idx));
-  const int rows = (int)idx.size();
-  if (rows > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
-  if (out1) {
-    RC(shape_of(out1, &b2, &other));
-    if (b2 != batch || other != idx)
-      return err(HX_ERR_INVALID, "out0 and out1 differ in batch or prime set");
-  }
-  const uint32_t N = v.phim;
-  if (N < 2 || (N & 1))
-    return err(HX_ERR_UNSUPPORTED, "hx_lin_comb needs an even number of coefficients");
-  std::vector<uint64_t> qs(rows);
+  Frame f;
+  RC(f.open(ctx, out0, "hx_lin_comb uploads a table of pointers and weights and cannot be captured in a graph"));
+  if (out1)
+    RC(same_shape(out1, f, "out0 and out1 differ in batch or prime set"));
+  RC(f.even("hx_lin_comb"));
+  const int rows = f.rows;
+  std::vector<uint64_t> qs;
+  RC(f.moduli(&qs));
   for (int r = 0; r < rows; r++) {
-    RC(hx_ctx_prime(ctx, idx[r], &qs[r], nullptr));
     if (addend && addend[r] >= qs[r])
       return err(HX_ERR_INVALID, "row %d: the addend is not reduced modulo the row's prime %llu", r,
                  (unsigned long long)qs[r]);
@@ -1331,80 +1221,61 @@ extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* i
         return err(HX_ERR_INVALID, "term %d, row %d: the weight is not reduced modulo the row's prime %llu", t, r,
                    (unsigned long long)qs[r]);
   }
-  // trow[r n + t]: the row of term t that holds the prime of output row r, or -1
+  // trow[r n + t]: the row of term t that holds the prime of output row r, or -1 (a term has a prime set of its own)
   std::vector<int> trow((size_t)rows * n, -1);
   for (int t = 0; t < n; t++) {
-    RC(shape_of(in0[t], &b2, &other));
-    if (b2 != batch)
-      return err(HX_ERR_INVALID, "in0[%d]: batch %d, the output has %d", t, b2, batch);
+    int b = 0, b1 = 0;
+    std::vector<int> tidx, tidx1;
+    RC(shape_of(in0[t], &b, &tidx));
+    if (b != f.batch)
+      return err(HX_ERR_INVALID, "in0[%d]: batch %d, the output has %d", t, b, f.batch);
     if (in1) {
-      RC(shape_of(in1[t], &b2, &other1));
-      if (b2 != batch || other1 != other)
+      RC(shape_of(in1[t], &b1, &tidx1));
+      if (b1 != f.batch || tidx1 != tidx)
         return err(HX_ERR_INVALID, "in1[%d] differs from in0[%d] in batch or prime set", t, t);
     }
-    for (size_t j = 0; j < other.size(); j++) {
-      int at = -1;
-      for (int r = 0; r < rows; r++)
-        if (idx[r] == other[j]) {
-          at = r;
-          break;
-        }
+    for (size_t j = 0; j < tidx.size(); j++) {
+      const int at = row_of(f.idx.data(), f.idx.size(), tidx[j]);
       if (at < 0)
         return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the output has no row for prime %d of term %d)",
-                   other[j], t);
+                   tidx[j], t);
       if (trow[(size_t)at * n + t] >= 0)
-        return err(HX_ERR_INVALID, "term %d lists prime %d twice", t, other[j]);
+        return err(HX_ERR_INVALID, "term %d lists prime %d twice", t, tidx[j]);
       trow[(size_t)at * n + t] = (int)j;
     }
-    if (((uint64_t)(uintptr_t)hxi::poly_rows_read(in0[t]) | (in1 ? (uint64_t)(uintptr_t)hxi::poly_rows_read(in1[t]) : 0)) & 15)
+    if (!aligned16(hxi::poly_rows_read(in0[t]), in1 ? hxi::poly_rows_read(in1[t]) : nullptr))
       return err(HX_ERR_INVALID, "term %d: rows are not 16-byte aligned", t);
   }
   if (rows == 0)
     return HX_OK;
-  if (!*v.linalg) {
-    *v.linalg = new LinState();
-    *v.linalg_free = state_free;
-  }
-  LinState* s = static_cast<LinState*>(*v.linalg);
-  const hipStream_t st = v.stream;
-  const size_t words = (size_t)rows * (3 * (size_t)n + 1), bytes = words * 8;
-  int slot = 0;
-  RC(stage_table(s, st, bytes, &slot));
-  // the outputs first: one that still shares an input's rows (a lazy hx_poly_copy) lets go of them
+  // table (kernel's layout): per output row and term the two row bases and the weight, then the addends
+  Table tab;
+  RC(tab.acquire(f, (size_t)rows * (3 * (size_t)n + 1)));
+  // the outputs first: one that still shares an input's rows (a lazy hx_poly_copy) lets go of them before the inputs'
+  // addresses are read into the table
   uint64_t *o0 = nullptr, *o1 = nullptr;
   RC(hxi::poly_rows_write(out0, &o0));
   if (out1)
     RC(hxi::poly_rows_write(out1, &o1));
-  if (((uint64_t)(uintptr_t)o0 | (uint64_t)(uintptr_t)o1) & 15)
+  if (!aligned16(o0, o1))
     return err(HX_ERR_INVALID, "output rows are not 16-byte aligned");
-  uint64_t* h = s->h_tab[slot];
-  const size_t rw = (size_t)batch * N;
+  const size_t rw = (size_t)f.batch * f.N;
   for (int t = 0; t < n; t++) {
     const uint64_t* p0 = hxi::poly_rows_read(in0[t]);
     const uint64_t* p1 = in1 ? hxi::poly_rows_read(in1[t]) : nullptr;
     for (int r = 0; r < rows; r++) {
       const int at = trow[(size_t)r * n + t];
-      uint64_t* e = h + 3 * ((size_t)r * n + t);
+      uint64_t* e = tab.h + 3 * ((size_t)r * n + t);
       e[0] = at < 0 ? 0 : (uint64_t)(uintptr_t)(p0 + (size_t)at * rw);
       e[1] = at < 0 || !p1 ? 0 : (uint64_t)(uintptr_t)(p1 + (size_t)at * rw);
       e[2] = w[(size_t)t * rows + r];
     }
   }
   for (int r = 0; r < rows; r++)
-    h[3 * (size_t)rows * n + r] = addend ? addend[r] : 0;
-  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
-  CK(hipEventRecord(s->copied[slot], st));
-  s->pending[slot] = true;
-  hx::MadRows map;
-  for (int r = 0; r < rows; r++)
-    map.p[r] = (uint16_t)idx[r];
-  const int bp = batch == 1 ? 1 : 4;
-  const dim3 grid((N / 2 + 255) / 256, (unsigned)rows, (unsigned)((batch + bp - 1) / bp));
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
-  if (parts == 2)
-    launch_lin_comb<2>(bp, grid, st, o0, o1, s->d_tab, n, rows, batch, N, map, primes);
-  else
-    launch_lin_comb<1>(bp, grid, st, o0, nullptr, s->d_tab, n, rows, batch, N, map, primes);
+    tab.h[3 * (size_t)rows * n + r] = addend ? addend[r] : 0;
+  RC(tab.commit(f.v.stream));
+  HX_LAUNCH_PW(lin_comb_kernel, out1 ? 2 : 1, f.bp != 1, 1, 4, f.grid(), f.v.stream, o0, o1, hx::as_ro(tab.d), n, rows, f.batch,
+               f.N, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
 }
@@ -1430,34 +1301,32 @@ extern "C" int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0
     if (kv[t].ctx != ctx)
       return err(HX_ERR_INVALID, "the key-switching matrix of term %d belongs to another context", t);
   }
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  if (v.capturing)
-    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_automorph_sum uploads a table of key rows and cannot be captured in a graph");
+  // the frame's rows are the outputs': c0's primes followed by the special primes (set once those are checked)
+  Frame f;
+  RC(f.enter(ctx, "hx_hoisted_automorph_sum uploads a table of key rows and cannot be captured in a graph"));
+  const uint64_t m = f.v.m;
   for (int t = 0; t < n; t++)
-    if (hxh::gcd(k[t] % v.m, v.m) != 1)
+    if (hxh::gcd(k[t] % m, m) != 1)
       return err(HX_ERR_INVALID, "DoubleCRT::automorph: k[%d] = %llu is not in Zm*", t, (unsigned long long)k[t]);
-  int batch = 0, b2 = 0, nprimes = 0;
-  std::vector<int> all, other;
-  RC(shape_of(c0, &batch, &all));
-  RC(shape_of(c1, &b2, &other));
-  if (b2 != batch || other != all)
-    return err(HX_ERR_INVALID, "c0 and c1 differ in batch or prime set");
-  const int L = (int)all.size();
+  RC(shape_of(c0, &f.batch, &f.idx));
+  RC(same_shape(c1, f, "c0 and c1 differ in batch or prime set"));
+  const int L = (int)f.idx.size();
   if (L == 0)
     return err(HX_ERR_INVALID, "c0 has no rows");
+  int nprimes = 0;
   RC(hx_ctx_num_primes(ctx, &nprimes));
+  std::vector<int> all(f.idx);
   for (int i = 0; i < nsp; i++) {
-    if (sp_idx[i] < 0 || sp_idx[i] >= nprimes || std::find(all.begin(), all.end(), sp_idx[i]) != all.end())
+    if (sp_idx[i] < 0 || sp_idx[i] >= nprimes || row_of(all.data(), all.size(), sp_idx[i]) >= 0)
       return err(HX_ERR_INVALID, "special prime %d is not a prime of the context, or is listed twice or among c0's", sp_idx[i]);
     all.push_back(sp_idx[i]);
   }
-  const int nall = (int)all.size();
-  if (nall > hx::MAX_ROWS)
-    return err(HX_ERR_UNSUPPORTED, "too many rows");
+  RC(f.set_rows(all));
+  const int nall = f.rows;
+  int b2 = 0;
+  std::vector<int> other;
   RC(shape_of(digits, &b2, &other));
-  if (b2 != batch || other.empty() || other.size() % nall != 0)
+  if (b2 != f.batch || other.empty() || other.size() % nall != 0)
     return err(HX_ERR_INVALID, "the digit block differs in batch, or is not a whole number of digits on %d rows", nall);
   const int ndig = (int)other.size() / nall;
   for (int d = 0; d < ndig; d++)
@@ -1466,8 +1335,8 @@ extern "C" int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0
         return err(HX_ERR_INVALID, "digit rows do not match the ciphertext's primes followed by the special primes");
   for (hx_poly* o : {out0, out1}) {
     RC(shape_of(o, &b2, &other));
-    if (b2 != batch)
-      return err(HX_ERR_INVALID, "an output has batch %d, the operands %d", b2, batch);
+    if (b2 != f.batch)
+      return err(HX_ERR_INVALID, "an output has batch %d, the operands %d", b2, f.batch);
   }
   // wrow[r n + t]: the row of W[t] on the prime of output row r (rows by prime index, the leading ndig digits)
   std::vector<int> wrow((size_t)nall * n);
@@ -1476,40 +1345,30 @@ extern "C" int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0
       return err(HX_ERR_INVALID, "W must have as many columns as there are digits (term %d: %d, the block has %d)", t,
                  kv[t].ndig, ndig);
     for (int r = 0; r < nall; r++) {
-      const int* at = std::find(kv[t].row_idx, kv[t].row_idx + kv[t].nrows, all[r]);
-      if (at == kv[t].row_idx + kv[t].nrows)
+      const int at = row_of(kv[t].row_idx, kv[t].nrows, all[r]);
+      if (at < 0)
         return err(HX_ERR_PRIMESET, "No key-switching matrix row for prime %d (term %d)", all[r], t);
-      wrow[(size_t)r * n + t] = (int)(at - kv[t].row_idx);
+      wrow[(size_t)r * n + t] = at;
     }
   }
   // out0's accumulator takes Psp c0, n times Psp sigma(c0) and n ndig products of a digit word by a key word
   if ((long long)n * (ndig + 1) + 1 > hx::MAD_CHUNK)
     return err(HX_ERR_UNSUPPORTED, "hx_hoisted_automorph_sum: n (ndig + 1) + 1 = %lld products per word, the accumulators take %d",
                (long long)n * (ndig + 1) + 1, hx::MAD_CHUNK);
-  const uint32_t N = v.phim;
-  if (!*v.linalg) {
-    *v.linalg = new LinState();
-    *v.linalg_free = state_free;
-  }
-  LinState* s = static_cast<LinState*>(*v.linalg);
-  const hipStream_t st = v.stream;
-  const size_t words = (size_t)n + (size_t)nall * (3 * (size_t)n + 1), bytes = words * 8;
-  int slot = 0;
-  RC(stage_table(s, st, bytes, &slot));
-  if (s->perm_cap < (size_t)n * N) {
-    CK(hipStreamSynchronize(st));   // an earlier launch may still read the old tables
-    hipFree(s->d_perm);
-    s->d_perm = nullptr;
-    s->perm_cap = 0;
-    CK(hipMalloc((void**)&s->d_perm, (size_t)n * N * 4));
-    s->perm_cap = (size_t)n * N;
-  }
+  const uint32_t N = f.N;
+  const hipStream_t st = f.v.stream;
+  // table (kernels' layout): k[t] mod m; per output row and term the two key row bases and the digit stride; Psp per row
+  Table tab;
+  RC(tab.acquire(f, (size_t)n + (size_t)nall * (3 * (size_t)n + 1)));
+  uint32_t* perm = nullptr;
+  RC(tab.perm(f, (size_t)n * N, &perm));
+  // all checks have passed: the outputs take their shape
   uint64_t *o0 = nullptr, *o1 = nullptr;
   RC(hxi::poly_rows_reshape(out0, all.data(), nall, &o0));
   RC(hxi::poly_rows_reshape(out1, all.data(), nall, &o1));
-  uint64_t* h = s->h_tab[slot];
+  uint64_t* h = tab.h;
   for (int t = 0; t < n; t++)
-    h[t] = k[t] % v.m;
+    h[t] = k[t] % m;
   for (int r = 0; r < nall; r++) {
     uint64_t q = 0;
     RC(hx_ctx_prime(ctx, all[r], &q, nullptr));
@@ -1528,25 +1387,15 @@ extern "C" int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0
     }
     h[n + 3 * (size_t)nall * n + r] = psp;
   }
-  CK(hipMemcpyAsync(s->d_tab, h, bytes, hipMemcpyHostToDevice, st));
-  CK(hipEventRecord(s->copied[slot], st));
-  s->pending[slot] = true;
-  HX_LAUNCH(hx::hoisted_perm_kernel, dim3((N + 255) / 256, (unsigned)n), dim3(256), 0, st, s->d_perm, v.d_zms, v.d_zms_index, N,
-            v.m, hx::as_ro(s->d_tab), (int)v.pow2);
+  RC(tab.commit(st));
+  HX_LAUNCH(hx::hoisted_perm_kernel, dim3((N + 255) / 256, (unsigned)n), dim3(256), 0, st, perm, f.v.d_zms, f.v.d_zms_index, N, m,
+            hx::as_ro(tab.d), (int)f.v.pow2);
   CK(hipGetLastError());
-  hx::MadRows map;
-  for (int r = 0; r < nall; r++)
-    map.p[r] = (uint16_t)all[r];
-  const int bp = batch == 1 ? 1 : 4;
-  const dim3 grid((N + 255) / 256, (unsigned)nall, (unsigned)((batch + bp - 1) / bp));
-  const hx::PrimeDev* primes = static_cast<const hx::PrimeDev*>(v.d_primes);
+  dim3 grid = f.grid();
+  grid.x = (N + 255) / 256;   // one coefficient per thread
   const uint64_t *dg = hxi::poly_rows_read(digits), *p0 = hxi::poly_rows_read(c0), *p1 = hxi::poly_rows_read(c1);
-  if (bp == 1)
-    HX_LAUNCH((hx::hoisted_sum_kernel<1>), grid, dim3(256), 0, st, o0, o1, dg, p0, p1, s->d_perm, hx::as_ro(s->d_tab), n, ndig,
-              L, nall, batch, N, map, primes);
-  else
-    HX_LAUNCH((hx::hoisted_sum_kernel<4>), grid, dim3(256), 0, st, o0, o1, dg, p0, p1, s->d_perm, hx::as_ro(s->d_tab), n, ndig,
-              L, nall, batch, N, map, primes);
+  HX_LAUNCH_W(f.bp != 1, (hx::hoisted_sum_kernel<1>), (hx::hoisted_sum_kernel<4>), grid, st, o0, o1, dg, p0, p1, perm,
+              hx::as_ro(tab.d), n, ndig, L, nall, f.batch, N, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
 }
@@ -1558,24 +1407,23 @@ extern "C" int hx_poly_extract(hx_poly* dst, const hx_poly* src, int b)
   hx_ctx* ctx = hxi::poly_ctx(src);
   if (hxi::poly_ctx(dst) != ctx)
     return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
-  hxi::CtxView v{};
-  RC(hxi::ctx_enter(ctx, &v));
-  std::unique_lock<std::recursive_mutex> lk(*v.mu);
-  int sb = 0, db = 0;
-  std::vector<int> sidx, didx;
-  RC(shape_of(src, &sb, &sidx));
+  Frame f;   // (src's shape: any number of rows, any N)
+  RC(f.enter(ctx, nullptr));
+  int db = 0;
+  std::vector<int> didx;
+  RC(shape_of(src, &f.batch, &f.idx));
   RC(shape_of(dst, &db, &didx));
-  if (db != 1 || didx != sidx)
+  if (db != 1 || didx != f.idx)
     return err(HX_ERR_INVALID, "hx_poly_extract: dst must have batch 1 and the prime set of src");
-  if (b < 0 || b >= sb)
-    return err(HX_ERR_INVALID, "hx_poly_extract: batch element %d of %d", b, sb);
-  if (sidx.empty())
+  if (b < 0 || b >= f.batch)
+    return err(HX_ERR_INVALID, "hx_poly_extract: batch element %d of %d", b, f.batch);
+  if (f.idx.empty())
     return HX_OK;
   uint64_t* d = nullptr;
   RC(hxi::poly_rows_write(dst, &d));
   const uint64_t* sp = hxi::poly_rows_read(src);
-  const size_t rowb = (size_t)v.phim * 8;
-  CK(hipMemcpy2DAsync(d, rowb, sp + (size_t)b * v.phim, rowb * sb, rowb, sidx.size(), hipMemcpyDeviceToDevice,
-                      v.stream));
+  const size_t rowb = (size_t)f.N * 8;
+  CK(hipMemcpy2DAsync(d, rowb, sp + (size_t)b * f.N, rowb * f.batch, rowb, f.idx.size(), hipMemcpyDeviceToDevice,
+                      f.v.stream));
   return HX_OK;
 }

@@ -186,6 +186,14 @@ def test_mask_blend_refusals_touch_nothing(hx):
     refused(INV, "neither 1 nor 3", c0, None, t0, None, hx.DoubleCRT(c, [0, 1, 2], 2))
     # a mask missing a prime
     refused(PS, "no row for prime 1", c0, None, t0, None, hx.DoubleCRT(c, [0, 2], 1))
+    # more rows than one launch descriptor holds
+    from helib_amd import hostnt
+    big, gen = hx.Context(85), hostnt.PrimeGen(50, 85)
+    for _ in range(161):
+        big.add_prime(gen.next())
+    wide = [hx.DoubleCRT(big, range(161), 1) for _ in range(3)]
+    refused(hx.HX_ERR_UNSUPPORTED, "too many rows", wide[0], None, wide[1], None, wide[2])
+    assert not any(w.download().any() for w in wide)
     # an odd number of coefficients: phi(m) is odd for m = 2 only (phi = 1); polys without rows reach the check
     tiny = hx.Context(2)
     assert tiny.phim == 1

@@ -372,6 +372,19 @@ def test_scaled_sub_refusals_touch_nothing(hx):
     big = np.array([1, qs[1], 3], dtype=np.uint64)
     assert call(c0, None, t0, None, u=big) == INV and b"not reduced" in L.hx_last_error()
     assert call(c0, None, t0, None, v=big) == INV
+    # more rows than one launch descriptor holds
+    many, gen = hx.Context(85), hostnt.PrimeGen(50, 85)
+    for _ in range(161):
+        many.add_prime(gen.next())
+    wide = [hx.DoubleCRT(many, range(161), 1) for _ in range(2)]
+    zeros = np.zeros(161, dtype=np.uint64)
+    assert call(wide[0], None, wide[1], None, u=zeros, v=zeros) == hx.HX_ERR_UNSUPPORTED and b"too many rows" in L.hx_last_error()
+    # an odd number of coefficients: phi(m) is odd for m = 2 only (phi = 1); polys without rows reach the check
+    tiny = hx.Context(2)
+    assert tiny.phim == 1
+    ta, tb = (hx.DoubleCRT(tiny, [], 1, zero=False) for _ in range(2))
+    assert call(ta, None, tb, None) == hx.HX_ERR_UNSUPPORTED
+    assert b"hx_scaled_sub needs an even number of coefficients" in L.hx_last_error()
     with pytest.raises(hx.InvalidArgument, match="one u and one v per prime row"):
         hx.scaledSub(c0, None, t0, None, [1, 2], [1, 2, 3])
     for x, w in zip((c0, c1, t0, t1), keep):

@@ -97,8 +97,45 @@ def test_error_returns(hx):
     c, primes = _ctx(hx, m, 3)
     a, b, k = (_rand(hx, c, [0, 1], 3, s) for s in (1, 2, 3))
     out = hx.DoubleCRT(c, [0, 1], 3)
+    out1 = hx.DoubleCRT(c, [0, 1], 3)
+    polys = (a, b, k, out, out1)
+    keep = [x.download() for x in polys]
     with pytest.raises(hx.InvalidArgument):
         hx.mulAddMany(out, None, [], [], None)
+    with pytest.raises(hx.InvalidArgument, match="the same poly"):
+        hx.mulAddMany(out, out, [k], [a], [b])
+    with pytest.raises(hx.InvalidArgument, match=r"also an input \(term 1\)"):
+        hx.mulAddMany(out, None, [k, out], [a, b], None)                     # an output that is also a constant
+    with pytest.raises(hx.InvalidArgument, match=r"also an input \(term 0\)"):
+        hx.mulAddMany(out, out1, [k], [a], [out1])
+    with pytest.raises(hx.InvalidArgument, match=r"in1\[1\] differs from the output"):
+        hx.mulAddMany(out, out1, [k, k], [a, a], [b, _rand(hx, c, [0, 1], 2, 7)])
+    with pytest.raises(hx.InvalidArgument, match="out0 and out1 differ"):
+        hx.mulAddMany(out, hx.DoubleCRT(c, [0, 2], 3), [k], [a], [b])
+    c2, _ = _ctx(hx, m, 3)
+    foreign = _rand(hx, c2, [0, 1], 3, 8)
+    with pytest.raises(hx.InvalidArgument, match=r"incompatible objects \(term 1\)"):
+        hx.mulAddMany(out, None, [k, k], [a, foreign], None)
+    with pytest.raises(hx.InvalidArgument, match=r"incompatible objects \(term 0\)"):
+        hx.mulAddMany(out, None, [_rand(hx, c2, [0, 1], 1, 9)], [a], None)
+    with pytest.raises(hx.InvalidArgument, match="incompatible objects"):
+        hx.mulAddMany(out, foreign, [k], [a], [b])
+    # more rows than one launch descriptor holds (refused before the terms' shapes are looked at)
+    from helib_amd import hostnt
+    big, gen = hx.Context(85), hostnt.PrimeGen(50, 85)
+    for _ in range(161):
+        big.add_prime(gen.next())
+    wide, thin = hx.DoubleCRT(big, range(161), 1), hx.DoubleCRT(big, [5], 1)
+    with pytest.raises(hx.HxError, match="too many rows") as e:
+        hx.mulAddMany(wide, None, [thin], [thin], None)
+    assert e.value.code == hx.HX_ERR_UNSUPPORTED
+    # an odd number of coefficients: phi(m) is odd for m = 2 only (phi = 1); polys without rows reach the check
+    tiny = hx.Context(2)
+    assert tiny.phim == 1
+    ta, tb, tk = (hx.DoubleCRT(tiny, [], 1, zero=False) for _ in range(3))
+    with pytest.raises(hx.HxError, match="hx_mul_add_many needs an even number of coefficients") as e:
+        hx.mulAddMany(ta, None, [tk], [tb], None)
+    assert e.value.code == hx.HX_ERR_UNSUPPORTED
     with pytest.raises(hx.InvalidArgument, match="no row for prime"):
         hx.mulAddMany(out, None, [_rand(hx, c, [0], 1, 4)], [a], None)
     with pytest.raises(hx.InvalidArgument, match="batch"):
@@ -119,6 +156,15 @@ def test_error_returns(hx):
         hx._chk(hx.lib().hx_poly_extract(narrow.h, a.h, 0))
     with pytest.raises(hx.InvalidArgument, match="batch 1"):
         hx._chk(hx.lib().hx_poly_extract(out.h, a.h, 0))
+    with pytest.raises(hx.InvalidArgument, match="null argument"):
+        hx._chk(hx.lib().hx_poly_extract(one.h, None, 0))
+    with pytest.raises(hx.InvalidArgument, match="null argument"):
+        hx._chk(hx.lib().hx_poly_extract(None, a.h, 0))
+    with pytest.raises(hx.InvalidArgument, match="null argument"):
+        hx._chk(hx.lib().hx_poly_extract(one.h, one.h, 0))                   # dst is src
+    with pytest.raises(hx.InvalidArgument, match="incompatible objects"):
+        hx._chk(hx.lib().hx_poly_extract(one.h, foreign.h, 0))
+    assert not one.download().any() and not narrow.download().any()
     rows = a.download()
     for b, d in enumerate(hx.splitBatch(a)):
         assert np.array_equal(d.download()[:, 0], rows[:, b])
@@ -126,12 +172,14 @@ def test_error_returns(hx):
     try:
         with pytest.raises(hx.HxError) as e:
             hx.mulAddMany(out, None, [k], [a], None)
-        assert e.value.code == hx.HX_ERR_UNSUPPORTED
+        assert e.value.code == hx.HX_ERR_UNSUPPORTED and "hx_mul_add_many uploads a pointer table" in str(e.value)
     finally:
         try:
             c.graphEnd().destroy()
         except hx.HxError:
             pass               # (nothing was recorded)
+    for x, w in zip(polys, keep):
+        assert np.array_equal(x.download(), w)
 
 
 def _chain(hx, m, bits, fam, seed=5, extra=()):

@@ -233,6 +233,16 @@ def test_refusals_touch_nothing(hx):
     assert call(Ws=[W, _matrix(hx, g, rng, allp, 1)[0]]) == INV and b"as many columns" in L.hx_last_error()
     assert call(Ws=[W, _matrix(hx, g, rng, [0, 1, 2], ndig)[0]]) == PS and b"prime 3" in L.hx_last_error()
     assert call(ks=[2] * 86, Ws=[W] * 86) == UNS and b"256" in L.hx_last_error()
+    empty = [hx.DoubleCRT(g, [], B, zero=False) for _ in range(2)]
+    assert call(c0=empty[0], c1=empty[1]) == INV and b"c0 has no rows" in L.hx_last_error()
+    # 160 rows and a special prime: one row more than a launch descriptor holds
+    big = _ring(hx, m, 161, bits=50)
+    wide = [hx.DoubleCRT(big, range(160), B) for _ in range(2)]
+    bo = [hx.DoubleCRT(big, [0], B) for _ in range(3)]
+    bW = _matrix(hx, big, rng, [0], 1)[0]
+    assert call(dg=bo[0], c0=wide[0], c1=wide[1], ks=[2], Ws=[bW], sp=[160], out0=bo[1], out1=bo[2]) == UNS
+    assert b"too many rows" in L.hx_last_error()
+    assert all(x.getIndexSet() == [0] and not x.download().any() for x in bo)
     g.graphBegin()                                                      # a call during a graph capture
     try:
         assert call() == UNS and b"cannot be captured" in L.hx_last_error()

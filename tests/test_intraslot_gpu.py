@@ -112,7 +112,7 @@ def test_error_returns_leave_the_outputs_untouched(hx, rings):
     ins = [_rand(hx, c, [0, 1], 3, 10 + t) for t in range(d)]
     ks = [_rand(hx, c, [0, 1], 1, 20 + t) for t in range(d)]
     outs = [_rand(hx, c, [0, 1], 3, 30 + t) for t in range(d)]
-    before = [o.download() for o in outs]
+    before = [o.download() for o in outs + ins + ks]
     with pytest.raises(hx.InvalidArgument, match="also an input"):
         hx.mulAddCirculant([outs[0], ins[1], outs[2]], None, ks, ins, None)
     with pytest.raises(hx.InvalidArgument, match="also an input"):
@@ -136,17 +136,55 @@ def test_error_returns_leave_the_outputs_untouched(hx, rings):
     assert L.hx_mul_add_circulant(arr, None, 1, arr, arr, None, 65) == hx.HX_ERR_UNSUPPORTED and b"64" in L.hx_last_error()
     assert L.hx_mul_add_circulant(arr, None, 4, arr, arr, None, 3) == hx.HX_ERR_INVALID
     assert L.hx_mul_add_circulant(None, None, 1, arr, arr, None, 1) == hx.HX_ERR_INVALID
+
+    def raw(out0, out1, consts, in0, in1, nout=None):
+        def pa(ps):
+            return (C.c_void_p * len(ps))(*[p.h if p is not None else None for p in ps]) if ps is not None else None
+        return L.hx_mul_add_circulant(pa(out0), pa(out1), len(out0) if nout is None else nout, pa(consts), pa(in0), pa(in1),
+                                      len(consts))
+    INV, UNS = hx.HX_ERR_INVALID, hx.HX_ERR_UNSUPPORTED
+    assert raw(outs, None, ks, ins, ins) == INV and b"go together" in L.hx_last_error()
+    assert raw(outs[:2], outs[2:], ks, ins, None, nout=1) == INV and b"go together" in L.hx_last_error()
+    assert raw([outs[0], None], None, ks, ins, None) == INV and b"null poly (output 1)" in L.hx_last_error()
+    assert raw(outs, None, ks, [ins[0], None, ins[2]], None) == INV and b"null poly (term 1)" in L.hx_last_error()
+    foreign = _rand(hx, rings[31], [0, 1], 3, 40)
+    assert raw([outs[0], foreign], None, ks, ins, None) == INV and b"incompatible objects" in L.hx_last_error()
+    assert raw(outs, None, ks, [ins[0], foreign, ins[2]], None) == INV and b"incompatible objects" in L.hx_last_error()
+    assert raw(outs, None, [foreign] + ks[1:], ins, None) == INV and b"incompatible objects" in L.hx_last_error()
+    assert raw([outs[0], _rand(hx, c, [0, 1], 2, 41)], None, ks, ins, None) == INV and b"the outputs differ" in L.hx_last_error()
+    assert raw([outs[0], _rand(hx, c, [1, 0], 3, 42)], None, ks, ins, None) == INV and b"the outputs differ" in L.hx_last_error()
+    assert raw(outs[:1], outs[1:2], ks, ins, [ins[0], _rand(hx, c, [0, 2], 3, 43), ins[2]]) == INV
+    assert b"in1[1] differs from the outputs" in L.hx_last_error()
+    # more rows than one launch descriptor holds (refused before the terms' shapes are looked at)
+    big, gen = hx.Context(85), hostnt.PrimeGen(50, 85)
+    for _ in range(161):
+        big.add_prime(gen.next())
+    wide, thin = hx.DoubleCRT(big, range(161), 1), hx.DoubleCRT(big, [5], 1)
+    assert raw([wide], None, [thin], [thin], None) == UNS and b"too many rows" in L.hx_last_error()
+    # an odd number of coefficients: phi(m) is odd for m = 2 only (phi = 1); polys without rows reach the check
+    tiny = hx.Context(2)
+    assert tiny.phim == 1
+    ta, tb, tk = (hx.DoubleCRT(tiny, [], 1, zero=False) for _ in range(3))
+    assert raw([ta], None, [tk], [tb], None) == UNS
+    assert b"hx_mul_add_circulant needs an even number of coefficients" in L.hx_last_error()
+    # batch 8192 in eight blocks of outputs: one more than the grid's third axis holds
+    c31 = rings[31]
+    many = [hx.DoubleCRT(c31, [0], 8192) for _ in range(57)]
+    x, k1 = hx.DoubleCRT(c31, [0], 8192), hx.DoubleCRT(c31, [0], 1)
+    assert raw(many, None, [k1] * 57, [x] * 57, None) == UNS and b"exceeds the grid" in L.hx_last_error()
+    assert not many[0].download().any() and not many[56].download().any()
+    del many, x
     c.graphBegin()
     try:
         with pytest.raises(hx.HxError) as e:
             hx.mulAddCirculant(outs, None, ks, ins, None)
-        assert e.value.code == hx.HX_ERR_UNSUPPORTED
+        assert e.value.code == hx.HX_ERR_UNSUPPORTED and "hx_mul_add_circulant uploads a pointer table" in str(e.value)
     finally:
         try:
             c.graphEnd().destroy()
         except hx.HxError:
             pass               # (nothing was recorded)
-    for o, b in zip(outs, before):
+    for o, b in zip(outs + ins + ks, before):
         assert np.array_equal(o.download(), b)
     hx.mulAddCirculant(outs, None, ks, ins, None)                            # and the call still works
     want = _sequence(hx, ks, ins, d)

@@ -216,13 +216,14 @@ def test_lin_comb_refusals_touch_nothing(hx):
     assert call(o0, o1, [a0, b0], None) == INV and b"go together" in L.hx_last_error()
     assert call(o0, None, [a0, b0], [a1, b1]) == INV and b"go together" in L.hx_last_error()
     assert L.hx_lin_comb(o0.h, None, arr, None, 0, None, None) == INV
-    assert call(o0, o0, [a0, b0], [a1, b1]) == INV
+    assert call(o0, o0, [a0, b0], [a1, b1]) == INV and b"the same poly" in L.hx_last_error()
     assert call(o0, None, [a0, o0], None) == INV and b"also an input" in L.hx_last_error()
     assert call(o0, o1, [a0, b0], [a1, o1]) == INV and call(o0, o1, [a0, b0], [o0, b1]) == INV
     assert call(o0, None, [a0, rnd(other)], None) == INV and b"incompatible objects" in L.hx_last_error()
     assert call(o0, rnd(other), [a0, b0], [a1, b1]) == INV
     assert call(o0, None, [a0, rnd(B=3)], None) == INV and b"batch" in L.hx_last_error()
     assert call(o0, rnd(B=1), [a0, b0], [a1, b1]) == INV and call(o0, rnd(idx=(0, 2, 1)), [a0, b0], [a1, b1]) == INV
+    assert b"out0 and out1 differ" in L.hx_last_error()
     assert call(o0, o1, [a0, b0], [a1, rnd(idx=(0, 2))]) == INV and b"differs from in0" in L.hx_last_error()
     assert call(o0, None, [a0, rnd(idx=(0, 3))], None) == hx.HX_ERR_PRIMESET and b"prime 3" in L.hx_last_error()
     assert call(o0, None, [a0, b0], None, w=[[1, qs[1], 3], [4, 5, 6]]) == INV and b"not reduced" in L.hx_last_error()
@@ -234,6 +235,12 @@ def test_lin_comb_refusals_touch_nothing(hx):
         big.add_prime(gen.next())
     wide, narrow = hx.DoubleCRT(big, range(161), 1), hx.DoubleCRT(big, [5], 1)
     assert _raw_lin_comb(hx, wide, None, [narrow], None, [[0] * 161], None) == UNS and b"too many rows" in L.hx_last_error()
+    # an odd number of coefficients: phi(m) is odd for m = 2 only (phi = 1); polys without rows reach the check
+    tiny = hx.Context(2)
+    assert tiny.phim == 1
+    ta, tb = (hx.DoubleCRT(tiny, [], 1, zero=False) for _ in range(2))
+    assert _raw_lin_comb(hx, ta, None, [tb], None, [[0]], None) == UNS
+    assert b"hx_lin_comb needs an even number of coefficients" in L.hx_last_error()
     # a call during a graph capture
     g.graphBegin()
     try:
