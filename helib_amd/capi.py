@@ -60,7 +60,7 @@ SYMBOLS = [
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
-    "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum",
+    "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum", "hx_mask_fan",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -166,6 +166,7 @@ def lib():
             "hx_poly_extract": [vp, vp, ip],
             "hx_mask_split": [vp, vp, vp, vp, vp],
             "hx_mask_blend": [vp, vp, vp, vp, vp],
+            "hx_mask_fan": [vp, vp, C.c_int, vp, vp, vp],
             "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
             "hx_lin_comb": [vp, vp, vp, vp, ip, vp, vp],
             "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
@@ -1133,6 +1134,22 @@ def maskBlend(c0, c1, t0, t1, mask):
     if (c1 is None) != (t1 is None):
         raise InvalidArgument(HX_ERR_INVALID, "c1 and t1 go together (both None for a one-part ciphertext)")
     _chk(lib().hx_mask_blend(c0.h, c1.h if c1 is not None else None, t0.h, t1.h if t1 is not None else None, mask.h))
+
+
+def maskFan(out0, out1, c0, c1, masks):
+    """out0[k] = c0 * masks[k], out1[k] = c1 * masks[k] for k < len(masks) in one pass (hx_mask_fan): the mask stage of a
+    permutation-network layer, tmp = c; tmp.multByConstant(mask_k) per shift amount (src/PermNetwork.cpp:239-242).
+    out1 / c1 = None for a one-part operand; the outputs are overwritten (lazy copies of c, or likeUninit) and c is left
+    as it is.  In a context created under HX_NO_MASK_FAN=1 the call issues hx_poly_copy and hx_mul per output and part
+    instead; the words are the same."""
+    nout = len(masks)
+    if (out1 is None) != (c1 is None) or len(out0) != nout or (out1 is not None and len(out1) != nout):
+        raise InvalidArgument(HX_ERR_INVALID, "maskFan: out1 and c1 go together, and one output per part for every mask")
+
+    def arr(ps):
+        return (C.c_void_p * max(len(ps), 1))(*[p.h for p in ps])
+    _chk(lib().hx_mask_fan(arr(out0), arr(out1) if out1 is not None else None, nout, c0.h,
+                           c1.h if c1 is not None else None, arr(masks)))
 
 
 def scaledSub(c0, c1, t0, t1, u, v):

@@ -19,6 +19,7 @@ struct CtxView {
   uint32_t phim;
   bool capturing;             // a graph capture is open
   bool no_mask_split;         // the context's HX_NO_MASK_SPLIT (switches.h)
+  bool no_mask_fan;           // the context's HX_NO_MASK_FAN (switches.h)
   void** state;               // the slot unit's per-context state ...
   void (**state_free)(void*); // ... and how the context releases it
   void** linalg;              // the same pair for linalg.hip

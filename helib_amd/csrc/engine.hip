@@ -5378,6 +5378,7 @@ int ctx_enter(hx_ctx* c, CtxView* v)
   v->phim = c->phim;
   v->capturing = c->capturing;
   v->no_mask_split = c->sw.no_mask_split;
+  v->no_mask_fan = c->sw.no_mask_fan;
   v->state = &c->ckks;
   v->state_free = &c->ckks_free;
   v->linalg = &c->linalg;

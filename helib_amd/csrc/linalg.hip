@@ -21,8 +21,10 @@
 // (hx_hoisted_automorph_sum):
 //   out = ctxt + sum_t keySwitch(sigma_k[t](ctxt)),  the digits of the s-part broken once
 // (src/matmul.cpp:2878-2887: acc += *precon.automorph(p^i)), every digit word and key word read once per term and the two
-// outputs written once.  The unit
-// reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
+// outputs written once; and of the mask stage of a permutation-network layer (hx_mask_fan):
+//   out[k] = c * mask[k],  k < K
+// (src/PermNetwork.cpp:239-242: tmp = c; tmp.multByConstant(mask_k) per shift amount), c read once for the K products.
+// The unit reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
 // key-switching matrix's rows, the tables of Z_m^*).
 #include <hip/hip_runtime.h>
 
@@ -361,6 +363,105 @@ mask_blend_kernel(uint64_t* __restrict__ c0, uint64_t* __restrict__ c1, const ui
   }
 }
 
+// out0[k] = c0 * masks[k], out1[k] = c1 * masks[k], k < nout (hx_mask_fan): per output the words hx_poly_copy(out, c) and
+// hx_mul(out, masks[k]) leave -- ew_binary_kernel<EW_MUL>'s mul_mod on canonical residues.  It is the mask stage of one
+// layer of a permutation network (src/PermNetwork.cpp:239-242), K masked copies of one ciphertext.
+//
+// Table (device, uint64 words, read through the constant address space: wave-uniform scalar loads): [0, nout) the bases
+// of out0[k]; [nout, 2 nout) of out1[k]; then per row r and k < nout, at 2 nout + r nout + k, the base of masks[k]'s row
+// on the prime of row r, bit 0 set when that mask has one row per batch element (bases are 16-byte aligned).
+//
+// The thread shape is mask_split_kernel's: one thread owns two adjacent coefficients of one prime row for BP batch
+// elements.  It loads its PARTS * BP vectors of c once (16 bytes each, non-temporal: every word is read once), then walks
+// the nout masks: per step the mask's two words (one load for all BP elements when the mask has batch 1, else BP loads)
+// and PARTS * BP products stream-stored.  The words of mask k + 1 are loaded before the products of mask k.  No LDS:
+// nothing is shared between threads.  Algorithmic bytes per part, in passes over the part: 1 read and K written (and the
+// K masks read once each), against K (2 read + 2 written) (and the masks) of the K copies and K products.
+template <int PARTS, int BP>
+__global__ void __launch_bounds__(256)
+mask_fan_kernel(const uint64_t* __restrict__ c0, const uint64_t* __restrict__ c1, ro_u64 tab, int nout, int batch,
+                uint32_t N, MadRows map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu;
+  const uint32_t k = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  ulonglong2 x0[BP], x1[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    x0[b] = ld_stream2(c0 + row_off + boff[b]);
+    if (PARTS == 2)
+      x1[b] = ld_stream2(c1 + row_off + boff[b]);
+  }
+  ro_u64 mtab = tab + 2 * (size_t)nout + (size_t)row * nout;
+  // step t loads the words of mask t and then forms the products of mask t - 1, whose words the step before loaded: the
+  // loads are in flight during the products
+  uint64_t nx[BP] = {}, ny[BP] = {};
+  for (int t = 0; t <= nout; t++) {
+    uint64_t mx[BP], my[BP];
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      mx[b] = nx[b];
+      my[b] = ny[b];
+    }
+    if (t < nout) {
+      const uint64_t e = mtab[t];
+      const uint64_t* mp = reinterpret_cast<const uint64_t*>(e & ~(uint64_t)1);
+      const bool per_elem = e & 1;
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        if (b == 0 || per_elem) {
+          const ulonglong2 w = *reinterpret_cast<const ulonglong2*>(mp + (per_elem ? boff[b] : 2 * (size_t)i));
+          nx[b] = w.x;
+          ny[b] = w.y;
+        } else {
+          nx[b] = nx[0];
+          ny[b] = ny[0];
+        }
+      }
+    }
+    if (t == 0)
+      continue;
+    uint64_t* o0 = reinterpret_cast<uint64_t*>(tab[t - 1]) + row_off;
+    uint64_t* o1 = PARTS == 2 ? reinterpret_cast<uint64_t*>(tab[nout + t - 1]) + row_off : nullptr;
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      if (b0 + b < batch) {
+        st_stream2(o0 + boff[b], make_ulonglong2(mul_mod(x0[b].x, mx[b], q, mu, k), mul_mod(x0[b].y, my[b], q, mu, k)));
+        if (PARTS == 2)
+          st_stream2(o1 + boff[b], make_ulonglong2(mul_mod(x1[b].x, mx[b], q, mu, k), mul_mod(x1[b].y, my[b], q, mu, k)));
+      }
+    }
+  }
+}
+
+// the most outputs one hx_mask_fan takes (its table holds nout (2 + rows) words)
+constexpr int FAN_MAX_OUT = 256;
+
+// A table written from the kernel's own arguments (Table::commit under a graph capture): TS_WORDS words per launch, by
+// value, so that a replay finds them without reading host memory.  One thread per word.
+constexpr int TS_WORDS = 448;
+struct TableWords {
+  uint64_t w[TS_WORDS];
+};
+static_assert(sizeof(TableWords) + 64 <= 4096, "the words travel as kernel arguments");
+__global__ void __launch_bounds__(256)
+table_store_kernel(uint64_t* __restrict__ dst, TableWords words, int n)
+{
+  for (int t = threadIdx.x; t < n; t += blockDim.x)
+    dst[t] = words.w[t];
+}
+
 // Per-row scalars of one scaled_sub_kernel launch, by value (the kernel-argument segment holds 4 KiB, so a launch takes
 // SS_ROWS rows and the host issues one per SS_ROWS rows of the operand)
 constexpr int SS_ROWS = 48;
@@ -606,6 +707,7 @@ struct LinState {
   size_t d_cap = 0;
   uint32_t* d_perm = nullptr;   // hx_hoisted_automorph_sum's gather tables
   size_t perm_cap = 0;          // (bytes)
+  std::vector<void*> recorded;  // the tables of calls recorded in a graph capture (Table::acquire_recorded)
 };
 void state_free(void* p)
 {
@@ -620,6 +722,8 @@ void state_free(void* p)
   }
   hipFree(s->d_tab);
   hipFree(s->d_perm);
+  for (void* p : s->recorded)
+    hipFree(p);
   delete s;
 }
 
@@ -867,19 +971,43 @@ int grow(hipStream_t st, void** p, size_t* cap, size_t bytes)
 // table (d), both of at least `words`; it waits for the copy that last read the staging buffer.  commit: the copy, the
 // event that marks it done, and the buffer's `pending` flag.  An entry point acquires after its last check and before
 // it takes an output, so that a failure here touches none.
+//
+// Under a graph capture (acquire_recorded, hx_mask_fan's) neither the ring nor the shared device table will do: a replay
+// runs after later calls have rewritten both, and a table grown since has been freed.  The recorded call gets a device
+// table of its own, kept until the context goes, and commit writes it by table_store_kernel launches whose words are
+// kernel arguments, so the recording holds them.  Nothing is waited for; the one allocation is the table.
 struct Table {
   LinState* s = nullptr;
   int slot = 0;
   size_t bytes = 0;
   uint64_t* h = nullptr;
   uint64_t* d = nullptr;
-  int acquire(const Frame& f, size_t words)
+  std::vector<uint64_t> own;   // h of a recorded call
+  bool recorded = false;
+  void state(const Frame& f)
   {
     if (!*f.v.linalg) {
       *f.v.linalg = new LinState();
       *f.v.linalg_free = state_free;
     }
     s = static_cast<LinState*>(*f.v.linalg);
+  }
+  int acquire_recorded(const Frame& f, size_t words)
+  {
+    state(f);
+    recorded = true;
+    bytes = words * 8;
+    void* p = nullptr;
+    CK(hipMalloc(&p, bytes));
+    s->recorded.push_back(p);
+    own.assign(words, 0);
+    h = own.data();
+    d = static_cast<uint64_t*>(p);
+    return HX_OK;
+  }
+  int acquire(const Frame& f, size_t words)
+  {
+    state(f);
     bytes = words * 8;
     slot = s->next;
     s->next = (slot + 1) % RING;
@@ -911,6 +1039,17 @@ struct Table {
   }
   int commit(hipStream_t st)
   {
+    if (recorded) {
+      const size_t words = bytes / 8;
+      for (size_t at = 0; at < words; at += hx::TS_WORDS) {
+        const int n = (int)std::min(words - at, (size_t)hx::TS_WORDS);
+        hx::TableWords tw{};
+        std::copy(h + at, h + at + n, tw.w);
+        HX_LAUNCH(hx::table_store_kernel, dim3(1), dim3(256), 0, st, d + at, tw, n);
+        CK(hipGetLastError());
+      }
+      return HX_OK;
+    }
     CK(hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, st));
     CK(hipEventRecord(s->copied[slot], st));
     s->pending[slot] = true;
@@ -1108,6 +1247,114 @@ extern "C" int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_
     return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
   HX_LAUNCH_PW(mask_split_kernel, parts, f.bp != 1, 1, 4, f.grid(), f.v.stream, k[0], k[1], t[0], t[1], mp, per_elem, f.batch,
                f.N, map, f.primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_mask_fan(hx_poly* const* out0, hx_poly* const* out1, int nout, const hx_poly* c0, const hx_poly* c1,
+                           const hx_poly* const* masks)
+{
+  if (!out0 || !c0 || !masks)
+    return err(HX_ERR_INVALID, "null argument");
+  if ((out1 == nullptr) != (c1 == nullptr))
+    return err(HX_ERR_INVALID, "out1 and c1 go together (both null for a one-part operand)");
+  if (nout < 1)
+    return err(HX_ERR_INVALID, "hx_mask_fan needs at least one output (nout = %d)", nout);
+  if (nout > hx::FAN_MAX_OUT)
+    return err(HX_ERR_UNSUPPORTED, "hx_mask_fan: too many outputs (nout = %d, at most %d)", nout, hx::FAN_MAX_OUT);
+  // every poly, null checks and aliasing first: a refused call touches no output
+  std::vector<const hx_poly*> outs, ins{c0};
+  if (c1)
+    ins.push_back(c1);
+  for (int t = 0; t < nout; t++) {
+    if (!out0[t] || (out1 && !out1[t]) || !masks[t])
+      return err(HX_ERR_INVALID, "null poly (output %d)", t);
+    outs.push_back(out0[t]);
+    if (out1)
+      outs.push_back(out1[t]);
+    ins.push_back(masks[t]);
+  }
+  if (c0 == c1)
+    return err(HX_ERR_INVALID, "c0 and c1 are the same poly");
+  {
+    std::vector<const hx_poly*> so(outs), si(ins);
+    std::sort(so.begin(), so.end());
+    std::sort(si.begin(), si.end());
+    if (std::adjacent_find(so.begin(), so.end()) != so.end())
+      return err(HX_ERR_INVALID, "an output appears twice");
+    for (const hx_poly* o : so)
+      if (std::binary_search(si.begin(), si.end(), o))
+        return err(HX_ERR_INVALID, "an output is also c0, c1 or a mask");
+  }
+  hx_ctx* ctx = hxi::poly_ctx(c0);
+  for (const hx_poly* p : outs)
+    if (hxi::poly_ctx(p) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  for (const hx_poly* p : ins)
+    if (hxi::poly_ctx(p) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  Frame f;
+  RC(f.open(ctx, c0, nullptr));
+  if (c1)
+    RC(same_shape(c1, f, "c0 and c1 differ in batch or prime set"));
+  for (size_t i = 0; i < outs.size(); i++)
+    RC(same_shape(outs[i], f, "output %d differs from c0 in batch or prime set", (int)(i / (out1 ? 2 : 1))));
+  // mrow[r nout + t]: the row of masks[t] on the prime of row r; mper[t]: masks[t] has one row per batch element
+  std::vector<int> mrow((size_t)f.rows * nout), mper(nout);
+  for (int t = 0; t < nout; t++) {
+    hx::RowMap2 map;
+    RC(check_mask(f, masks[t], &mper[t], &map));
+    for (int r = 0; r < f.rows; r++)
+      mrow[(size_t)r * nout + t] = map.brow[r];
+  }
+  RC(f.even("hx_mask_fan"));
+  if (f.rows == 0)
+    return HX_OK;
+  const int parts = c1 ? 2 : 1;
+  if (f.v.no_mask_fan) {   // HX_NO_MASK_FAN: the sequence the kernel replaces
+    for (int t = 0; t < nout; t++) {
+      RC(hx_poly_copy(out0[t], c0));
+      RC(hx_mul(out0[t], masks[t]));
+      if (c1) {
+        RC(hx_poly_copy(out1[t], c1));
+        RC(hx_mul(out1[t], masks[t]));
+      }
+    }
+    return HX_OK;
+  }
+  // table (kernel's layout): the bases of out0, of out1, then the masks' rows
+  Table tab;
+  const size_t words = (size_t)nout * (2 + (size_t)f.rows);
+  RC(f.v.capturing ? tab.acquire_recorded(f, words) : tab.acquire(f, words));
+  // the outputs first: one that still shares c's rows (a lazy hx_poly_copy) lets go of them, and c's rows stay where
+  // they are
+  bool aligned = true;
+  for (int t = 0; t < nout; t++) {
+    uint64_t *o0 = nullptr, *o1 = nullptr;
+    RC(hxi::poly_rows_write(out0[t], &o0));
+    if (out1)
+      RC(hxi::poly_rows_write(out1[t], &o1));
+    tab.h[t] = (uint64_t)(uintptr_t)o0;
+    tab.h[nout + t] = (uint64_t)(uintptr_t)o1;
+    aligned = aligned && aligned16(o0, o1);
+  }
+  const uint64_t* p0 = hxi::poly_rows_read(c0);
+  const uint64_t* p1 = c1 ? hxi::poly_rows_read(c1) : nullptr;
+  aligned = aligned && aligned16(p0, p1);
+  const size_t rw = (size_t)f.batch * f.N;
+  for (int t = 0; t < nout; t++) {
+    const uint64_t* mb = hxi::poly_rows_read(masks[t]);
+    aligned = aligned && aligned16(mb);
+    const size_t mrw = mper[t] ? rw : (size_t)f.N;
+    for (int r = 0; r < f.rows; r++)
+      tab.h[2 * (size_t)nout + (size_t)r * nout + t] =
+          (uint64_t)(uintptr_t)(mb + (size_t)mrow[(size_t)r * nout + t] * mrw) | (uint64_t)mper[t];
+  }
+  if (!aligned)
+    return err(HX_ERR_INVALID, "rows are not 16-byte aligned");
+  RC(tab.commit(f.v.stream));
+  HX_LAUNCH_PW(mask_fan_kernel, parts, f.bp != 1, 1, 4, f.grid(), f.v.stream, p0, p1, hx::as_ro(tab.d), nout, f.batch, f.N,
+               f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
 }

@@ -30,6 +30,8 @@ struct Switches {
   int mfma_min_n = 9;            // HX_MFMA_MIN_N=n      ... from n source primes on (9 .. 16: the fast kernels' plans; 17 .. 40 always)
   bool no_mask_split = false;    // HX_NO_MASK_SPLIT=1   hx_mask_split as hx_poly_copy + hx_mul + hx_sub per part instead of mask_split_kernel
                                  //                      (linalg.hip)
+  bool no_mask_fan = false;      // HX_NO_MASK_FAN=1     hx_mask_fan as hx_poly_copy + hx_mul per output and part instead of mask_fan_kernel
+                                 //                      (linalg.hip)
   int brk_lds_pad_rows = 0;      // HX_BRK_LDS_PAD=n     digit kernel: n more (unused) LDS rows per thread -- lowers its occupancy, an A/B probe
   // fused ciphertext-level paths
   bool no_tensor_multi = false;  // HX_NO_TENSOR_MULTI=1 tensor product + several-primes mod-switch as two steps
@@ -82,6 +84,7 @@ inline Switches read()
   if (const char* e = std::getenv("HX_MFMA_MIN_N"))
     s.mfma_min_n = std::atoi(e);
   s.no_mask_split = on("HX_NO_MASK_SPLIT");
+  s.no_mask_fan = on("HX_NO_MASK_FAN");
   if (const char* e = std::getenv("HX_BRK_LDS_PAD"))
     s.brk_lds_pad_rows = std::atoi(e);
   s.half15 = on("HX_HALF15");

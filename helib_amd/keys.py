@@ -660,6 +660,19 @@ def addAllMatrices(sk, keyID=0):
     sk.setKeySwitchMap()
 
 
+def addMatrices4Network(sk, net, keyID=0):
+    """src/keySwitching.cpp:667-686: a matrix for (g^e)^shamt of every nonzero shift amount of every layer of a
+    permutations.PermNetwork; a negative amount means the inverse power"""
+    z, m = _zmstar(sk), sk.cc.m
+    for i in range(net.depth()):
+        lyr = net.getLayer(i)
+        g2e = pow(z.gens[lyr.getGenIdx()], lyr.getE(), m)
+        for s in lyr.getShifts():
+            if s != 0:
+                sk.GenKeySWmatrix(1, pow(g2e, int(s), m), keyID, keyID)
+    sk.setKeySwitchMap()
+
+
 def addTheseMatrices(sk, automVals, keyID=0):
     for k in sorted(set(automVals)):
         sk.GenKeySWmatrix(1, k, keyID, keyID)

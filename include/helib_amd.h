@@ -205,6 +205,7 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
  *   HX_NO_LAZY_RNS                            no 128-bit lazy sums / single-subtraction Garner steps
  *   HX_NO_FAST_BREAK, HX_NO_FAST_EXTEND, HX_NO_WIDE_EXTEND   generic breakIntoDigits / basis-extension kernels
  *   HX_NO_MASK_SPLIT                          hx_mask_split as hx_poly_copy + hx_mul + hx_sub per part
+ *   HX_NO_MASK_FAN                            hx_mask_fan as hx_poly_copy + hx_mul per output and part
  *   HX_NO_TENSOR_MULTI, HX_NO_MULRELIN_FUSE   tensor product as a pass of its own in front of the several-primes
  *                                            mod-switch / inside hx_mul_relin
  *   HX_NO_KS_LAST_FUSE                        relinearisation: every extension row transformed by the row kernel and the key
@@ -610,6 +611,25 @@ int hx_mask_split(hx_poly* keep0, hx_poly* keep1, hx_poly* take0, hx_poly* take1
  * context's stream and may be recorded in a graph capture.  Per part, in passes over the part, the four calls read 6
  * and write 4 (and read the mask twice); this call reads 2 and writes 1 (and reads the mask once). */
 int hx_mask_blend(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1, const hx_poly* mask);
+/* The mask stage of one layer of a permutation network (src/PermNetwork.cpp:239-242:
+ *   tmp = c;  tmp.multByConstant(mask_k);   for each of the layer's K shift amounts)
+ * on the parts of one ciphertext, in one pass:  out0[k] = c0 * masks[k],  out1[k] = c1 * masks[k]  for k < nout, row by
+ * row modulo each prime, every word canonical in [0, q) and equal to what hx_poly_copy(out, c), hx_mul(out, masks[k])
+ * leave.  out1 and c1 are both null for a one-part operand.  The outputs are written, not read; they have the batch and
+ * the prime set (same order) of c0 / c1, are distinct polys, and none is c0, c1 or a mask.  An output that still shares
+ * c's rows (a lazy hx_poly_copy) lets go of them first; c is left unchanged.  Each mask is in evaluation form, with
+ * batch 1 (broadcast over the batch) or the batch of c, and may live on more primes than c, in any order: its rows are
+ * matched by prime index, a missing prime is HX_ERR_PRIMESET (as hx_mul's).  Null arguments, nout < 1, aliased
+ * outputs, a poly of another context and mismatched shapes are HX_ERR_INVALID; nout > 256 ("too many outputs"), more
+ * rows than a launch addresses and an odd phi(m) are HX_ERR_UNSUPPORTED; a refused call touches no output.
+ * Asynchronous on the context's stream.  The output and mask addresses travel in a table of nout (2 + rows) words: an
+ * eager call uploads it through the staging ring of hx_mul_add_many; a call recorded in a graph capture takes a device
+ * table of its own (kept until the context is destroyed) and writes it from kernel arguments, so it waits for nothing
+ * and a replay reads no host memory.  Per part, in passes over the part, the K copies and K products read 2 K and
+ * write 2 K; this call reads 1 and writes K (the masks are read once either way).  HX_NO_MASK_FAN=1 runs the copy and
+ * the product per output and part instead. */
+int hx_mask_fan(hx_poly* const* out0, hx_poly* const* out1, int nout, const hx_poly* c0, const hx_poly* c1,
+                const hx_poly* const* masks);
 /* The inner step of digit extraction (src/extractDigits.cpp:106-107:
  *   tmp -= digits[j];  tmp.divideByP();)
  * on the parts of one ciphertext, in one pass:  c = c * u[row] - t * v[row],  row by row modulo each prime.  After
