@@ -236,14 +236,9 @@ static hipError_t launch_conv(const ConvRowArgs& A, const ConvRows& R, int nunit
                               const TW* tw_arena, hipStream_t st)
 {
   constexpr size_t lds_bytes = (size_t)Geo<LOGN>::LDS_WORDS * 4;
-  bool attr_set = false;   // (hxp::dyn_lds is idempotent per device)
-  if (!attr_set) {
-    hipError_t e = hxp::dyn_lds((const void*)ntt_conv_kernel<LOGN, SRC, DST>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-    if (e != hipSuccess)
-      return e;
-    attr_set = true;
-  }
+  hipError_t e = hxp::dyn_lds((const void*)ntt_conv_kernel<LOGN, SRC, DST>, (int)lds_bytes);
+  if (e != hipSuccess)
+    return e;
   HX_LAUNCH((ntt_conv_kernel<LOGN, SRC, DST>), dim3((unsigned)nunits * A.batch), dim3(Geo<LOGN>::T), lds_bytes, st, A, R,
             cprimes, tw_arena);
   return hipGetLastError();

@@ -38,8 +38,6 @@ hipError_t launch_ntt_pow2_lazy_in(int logn, const uint64_t* in, uint64_t* out, 
                                    const PrimeDev* primes, const TW* tw_arena, hipStream_t st);
 hipError_t launch_keyswitch_last_pow2(int logn, int nd, const KsLastArgs& A, const RowMap2& map, const KsLastPlan& plan, int device,
                                       const PrimeDev* primes, const TW* tw_arena, hipStream_t st);
-hipError_t launch_ntt_half15_fwd(bool lazy_in, const uint64_t* in, uint64_t* out, const NttRows& rows, int nrows, int batch,
-                                 const PrimeDev* sub_primes, const TW* tw_arena, hipStream_t st);
 hipError_t launch_moddown_pow2(int logn, const PolyBases& data, const PolyBases& out, int drop_row,
                                int drop_prime, const NttRows& keep, int nkeep, int batch,
                                const ModDownPrep& P, const ModDownApply& A, const PrimeDev* primes,
@@ -136,7 +134,6 @@ struct PrimeHost {
   uint64_t last_s = 0, last_n = 0;  // inverse table slots 0 / 31: S0*N^-1 and N^-1
   uint64_t tw_fwd_off = 0, tw_inv_off = 0;  // into hx_ctx::d_tw (TW units)
   bool proth = false;  // row tables in Proth form (8-byte entries w 2^64 mod q): PrimeDev::proth
-  int half_pd = -1;    // N = 2^15: index into hx_ctx::d_cprimes of the forward half-row kernel's entry for g = 0 (g = 1 follows)
 };
 // the second word of a twiddle constant that a row kernel substitutes for a table entry (ModDownPrep::upS / upN):
 // Shoup's quotient, or -- for a prime whose rows run the Proth-form butterflies -- w 2^64 mod q
@@ -196,10 +193,10 @@ struct hx_ctx {
   int primes_cap = 0;
   TW* d_tw = nullptr;  // twiddle arena shared by all primes
   size_t tw_cap = 0, tw_used = 0;
-  uint64_t* scratch[11] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  uint64_t* scratch[10] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
   uint32_t* d_redo = nullptr;   // redo list of the HPS-form RNS kernels: [0] = count, [1..] = coefficient indices
   size_t redo_cap = 0;          // (in 32-bit words)
-  size_t scratch_words[11] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  size_t scratch_words[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
   uint64_t aux_q[3] = {0, 0, 0};  // auxiliary NTT primes of the aux Bluestein path (lazily chosen)
   // general m (Bluestein): conv sizes 2^bk (chirp), 2^n1 / 2^n2 (rem Phi_m), pseudo "primes"
   // (twiddle tables of the conv sizes) and per-prime tables
@@ -260,15 +257,6 @@ struct hx_ctx {
   bool defer_norms = false;
   std::vector<NormPending> norm_pending, norm_free;
   NormPending prep_np{};   // (prep_norm)
-  // The norm kernels run on a stream of their own, next to whatever the context enqueues after them
-  // (they have no consumer on the device: only the host reads the result).  One LDS-bound workgroup per
-  // CU with almost no VALU work co-resides with the HBM-bound tensor / key-switch kernels.  Ordering:
-  // the side stream waits for an event recorded behind the producers of its input; the main stream
-  // waits for the side stream (norm_join) before anything rewrites what an in-flight norm kernel reads:
-  // scratch[0] / [1] (the mod-down's x, S) or d_frac.
-  hipStream_t norm_stream = nullptr;
-  hipEvent_t norm_in_ev = nullptr, norm_out_ev = nullptr;
-  bool norm_reads_xs = false, norm_reads_frac = false;
   hipEvent_t timer[2] = {nullptr, nullptr};  // hx_ctx_timer_begin / _end
   // HIP graphs (hx_ctx_graph_begin / _end): while a capture is open or a captured graph is alive,
   // nothing a graph may point at is handed back -- slabs that were live during a capture are pinned
@@ -387,8 +375,6 @@ static void retire_or_free(hx_ctx* c, void* p, bool device_wide_sync = false)
 {
   if (!p)
     return;
-  if (c->norm_stream)
-    hipStreamSynchronize(c->norm_stream);  // (the buffer may be one the norm kernels use)
   if (c->capturing || c->graphs_alive > 0) {
     c->graph_retired.push_back(p);
     return;
@@ -415,20 +401,8 @@ static void pool_free(hx_ctx* c, void* p, size_t bytes)
   }
 }
 
-// the main stream waits for the norm kernels still reading the (x, S) scratch slots / d_frac
-static int norm_join(hx_ctx* c, bool xs, bool frac)
-{
-  if ((xs && c->norm_reads_xs) || (frac && c->norm_reads_frac)) {
-    HIPCHK(hipStreamWaitEvent(c->stream, c->norm_out_ev, 0));
-    c->norm_reads_xs = c->norm_reads_frac = false;   // (one event: everything on the side stream so far)
-  }
-  return HX_OK;
-}
-
 static int ensure_scratch(hx_ctx* c, int slot, size_t words)
 {
-  if (slot <= 1)  // about to be rewritten by the caller
-    CHK(norm_join(c, true, false));
   if (c->scratch_words[slot] >= words)
     return HX_OK;
   if (c->scratch[slot]) {
@@ -610,15 +584,10 @@ static void ctx_free(hx_ctx* c)
     hipFree(kv.second->blob_mfma);
     delete kv.second;
   }
-  for (int i = 0; i < 11; i++)
+  for (int i = 0; i < 10; i++)
     if (c->scratch[i])
       hipFree(c->scratch[i]);
   c->arena.destroy();
-  if (c->norm_stream) {
-    hipStreamDestroy(c->norm_stream);
-    hipEventDestroy(c->norm_in_ev);
-    hipEventDestroy(c->norm_out_ev);
-  }
   if (c->own_stream)
     hipStreamDestroy(c->own_stream);
   for (void* q : c->graph_retired)
@@ -694,8 +663,6 @@ extern "C" int hx_ctx_set_stream(hx_ctx* c, void* s)
     // pooled slabs are recycled in stream order: drain the old stream before switching
     hipSetDevice(c->device);
     hipStreamSynchronize(c->stream);
-    if (c->norm_stream)
-      hipStreamSynchronize(c->norm_stream);
   }
   c->stream = (hipStream_t)s;
   return HX_OK;
@@ -707,8 +674,6 @@ extern "C" int hx_ctx_sync(hx_ctx* c)
   CTX_ENTER(c);
   NO_CAPTURE(c, "hx_ctx_sync");
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (c->norm_stream)
-    HIPCHK(hipStreamSynchronize(c->norm_stream));
   return HX_OK;
 }
 extern "C" int hx_ctx_reserve(hx_ctx* c, uint64_t bytes)
@@ -1653,24 +1618,7 @@ extern "C" int hx_ctx_add_prime(hx_ctx* c, uint64_t q, uint64_t root, int* idx_o
     switch (c->logn) {
       case 13: CHK(upload_tw<13>(c, ph)); break;
       case 14: CHK(upload_tw<14>(c, ph)); break;
-      case 15:
-        CHK(upload_tw<15>(c, ph));
-        if (c->sw.half15) {
-          // the forward transform as two 2^14-point workgroups per row (ntt_kernels.hip ntt_row_half15_kernel): the
-          // sub-transforms' tables (what a split power-of-two ring builds with OUT = 1) and the first stage's twiddle
-          int i0 = -1, i1 = -1;
-          CHK(conv_tables_sub<14>(c, q, root, 1, 0, &i0));
-          CHK(conv_tables_sub<14>(c, q, root, 1, 1, &i1));
-          if (i1 != i0 + 1)
-            return fail(HX_ERR_DEVICE, "internal: half-row table entries are not adjacent");
-          const uint64_t t1 = hxh::powmod(root, (uint64_t)1 << 14, q);   // psi_rev[1] = psi^(N/2)
-          const uint64_t h3[3] = {t1, hxh::shoup(t1, q), hx::tw_mont_form(t1, q)};
-          for (int g = 0; g < 2; g++)
-            HIPCHK(hipMemcpy(reinterpret_cast<char*>(c->d_cprimes + i0 + g) + offsetof(PrimeDev, half_t1), h3, sizeof h3,
-                             hipMemcpyHostToDevice));
-          ph.half_pd = i0;
-        }
-        break;
+      case 15: CHK(upload_tw<15>(c, ph)); break;
       default:
         if (c->logn >= 1 && c->logn <= 12)
           CHK(upload_tw_small(c, ph));
@@ -2008,11 +1956,6 @@ static int ntt_launch(hx_ctx* c, int logn, const PrimeDev* table, const uint64_t
     return HX_OK;
   if (logn < 1 || logn > 15)
     return fail(HX_ERR_UNSUPPORTED, "negacyclic NTT kernels support sizes 2..32768");
-  // N = 2^15 forward, out of place, on the context's own primes: two 2^14-point workgroups per row
-  bool half15 = logn == 15 && !inverse && table == c->d_primes && in != out && c->sw.half15;
-  for (size_t i = 0; i < rows.size() && half15; i++)
-    half15 = rows[i].second >= 0 && rows[i].second < (int)c->primes.size() && c->primes[(size_t)rows[i].second].half_pd >= 0 &&
-             c->primes[(size_t)rows[i].second].half_pd < 0xffff;
   for (size_t first = 0; first < rows.size(); first += MAX_ROWS) {
     int n = (int)std::min<size_t>(MAX_ROWS, rows.size() - first);
     NttRows d;
@@ -2020,13 +1963,7 @@ static int ntt_launch(hx_ctx* c, int logn, const PrimeDev* table, const uint64_t
       if (rows[first + i].first > 0xffff || rows[first + i].second > 0xffff)
         return fail(HX_ERR_UNSUPPORTED, "row index too large for one launch descriptor");
       d.row[i] = (uint16_t)rows[first + i].first;
-      d.prime[i] = half15 ? (uint16_t)c->primes[(size_t)rows[first + i].second].half_pd : (uint16_t)rows[first + i].second;
-    }
-    if (half15) {
-      hipError_t e = hx::launch_ntt_half15_fwd(lazy_in, in, out, d, n, batch, c->d_cprimes, c->d_tw, c->stream);
-      if (e != hipSuccess)
-        return fail(HX_ERR_DEVICE, "NTT launch failed: %s", hipGetErrorString(e));
-      continue;
+      d.prime[i] = (uint16_t)rows[first + i].second;
     }
     hipError_t e = (lazy_in && !inverse && logn >= 13 && logn <= 15)
                        ? hx::launch_ntt_pow2_lazy_in(logn, in, out, d, n, batch, table, c->d_tw, c->stream)
@@ -2569,10 +2506,10 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
   size_t o_ginvm = take((size_t)n * n);   // Garner constants times 2^64 (Proth-form sources, ExtPlanDev::ginv_m)
   // rns_extend_wide_kernel (17..40 source primes): per-target record of 8 + n words, padded so that the last
   // record's group-of-four multiplier reads stay inside the blob
-  const bool wide_cand = n > 16 && n <= 40 && !c->sw.no_wide_extend;
+  const bool wide_cand = n > 16 && n <= 40;
   // 9 .. 16 sources (the dropped primes of a CKKS level-2 mod-switch): the fast kernels' plans, whose HPS-form launches
   // go to the matrix-core kernel too -- it reads the wide record's header for its rarer constants
-  const bool mfma_small = n >= c->sw.mfma_min_n && n <= 16 && n >= 4 && !c->sw.no_mfma_ext && !c->sw.no_hps;
+  const bool mfma_small = n >= c->sw.mfma_min_n && n <= 16 && n >= 4 && !c->sw.no_mfma_ext;
   const bool wide_rec = wide_cand || mfma_small;
   const size_t wide_stride = (size_t)hx::wide_stride(n);
   size_t o_wide = wide_rec ? take((size_t)nt * wide_stride) : 0;
@@ -2617,9 +2554,9 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
     uint64_t q = tq(t);
     // lazy 128-bit accumulation is exact when sum_k a_k*W_k < (sum_k q_k)*q_t <= 8*q_t^2
     // (red128_wide's domain; q_t <= 60 bits)
-    tlazy[t] = (hxh::bitlen(q) <= 60 && sum_src <= (hxh::u128)8 * q && !c->sw.no_lazy_rns) ? 1u : 0u;
+    tlazy[t] = (hxh::bitlen(q) <= 60 && sum_src <= (hxh::u128)8 * q) ? 1u : 0u;
     // seven terms + the carried remainder: r + 7 max_src q < 8 q^2 needs max_src <= q
-    tchunk[t] = (hxh::bitlen(q) <= 60 && max_src <= q && !c->sw.no_lazy_rns) ? 1u : 0u;
+    tchunk[t] = (hxh::bitlen(q) <= 60 && max_src <= q) ? 1u : 0u;
     h[o_tq + t] = q;
     h[o_tmu64 + t] = (uint64_t)((((hxh::u128)1) << 64) / q);
     int kb = hxh::bitlen(q);
@@ -2704,8 +2641,7 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
   }
   // HPS front end: y_k = a_k (P/p_k)^-1 mod p_k, multipliers (P/p_k) mod t (scaled plans: / P, i.e.
   // p_k^-1 mod t), the same header; "lazy" needs room for up to n + 1 extra multiples of t in the sum
-  bool hps_ok = n >= 2 && (n <= 16 || wide_cand) && (ptxt <= 1 || ptxt < ((uint64_t)1 << (wide_cand ? 56 : 58))) &&
-                (!c->sw.no_hps || wide_cand);
+  bool hps_ok = n >= 2 && (n <= 16 || wide_cand) && (ptxt <= 1 || ptxt < ((uint64_t)1 << (wide_cand ? 56 : 58)));
   if (hps_ok) {
     auto prod_except = [&](int k, uint64_t m) {   // (P / p_k) mod m
       uint64_t r = 1 % m;
@@ -2757,7 +2693,7 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
         rec2[j] = rec[j];   // (a Proth-form target: rec[2] is -P 2^64 already)
       rec2[8 + 2 * n] = rec[8 + 2 * n];
       rec2[8 + 2 * n + 1] = rec[8 + 2 * n + 1];
-      const uint32_t lazy2 = (hxh::bitlen(q) <= 60 && sum_src + 32 <= (hxh::u128)8 * q && !c->sw.no_lazy_rns) ? 1u : 0u;
+      const uint32_t lazy2 = (hxh::bitlen(q) <= 60 && sum_src + 32 <= (hxh::u128)8 * q) ? 1u : 0u;
       rec2[4] = (uint64_t)tk[t] | ((uint64_t)lazy2 << 8) | ((uint64_t)tchunk[t] << 9) | (rec[4] & ((uint64_t)1 << 10));
       const uint64_t pinv_t = h[o_upd + 2 * (size_t)t];   // P^-1 mod t
       for (int k = 0; k < n; k++) {
@@ -2803,15 +2739,15 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
   pl->dev.Wp = hx::as_ro(reinterpret_cast<const TW*>(d + o_Wp));
   pl->dev.tgt_lazy = hx::as_ro(reinterpret_cast<const uint32_t*>(d + o_tlazy));
   // a_l < q_l <= max < 2*min <= 2*p_k, or the sources ascend (a_l < p_l <= p_k for l < k)
-  pl->dev.garner_cs = ((max_src / 2 < min_src || std::is_sorted(p.begin(), p.end())) && !c->sw.no_lazy_rns) ? 1u : 0u;
+  pl->dev.garner_cs = (max_src / 2 < min_src || std::is_sorted(p.begin(), p.end())) ? 1u : 0u;
   pl->dev.src_rq = hx::as_ro(reinterpret_cast<const double*>(d + o_srcrq));
   pl->dev.tgt_mu63 = hx::as_ro(d + o_tmu63);
   {
-    bool ok = pl->dev.garner_cs && n <= 8 && (min_src >> 32) != 0 && !c->sw.no_fast_break;
+    bool ok = pl->dev.garner_cs && n <= 8 && (min_src >> 32) != 0;
     for (int t = 0; t < nt && ok; t++)
       ok = (tq(t) >> 32) != 0 && hxh::bitlen(tq(t)) <= 60;
     pl->dev.fast_ok = ok ? 1u : 0u;
-    bool ok16 = pl->dev.garner_cs && n <= 16 && (min_src >> 32) != 0 && !c->sw.no_fast_extend;
+    bool ok16 = pl->dev.garner_cs && n <= 16 && (min_src >> 32) != 0;
     for (int t = 0; t < nt && ok16; t++)
       ok16 = (tq(t) >> 32) != 0 && hxh::bitlen(tq(t)) <= 60;
     pl->dev.fast16_ok = ok16 ? 1u : 0u;
@@ -2946,7 +2882,7 @@ static int launch_extend(hx_ctx* c, const ExtPlan* pl, const ExtArgs& args_in, s
         for (const void* f : {(const void*)hx::rns_extend_wide_kernel<20>, (const void*)hx::rns_extend_wide_kernel<24>,
                               (const void*)hx::rns_extend_wide_kernel<28>, (const void*)hx::rns_extend_wide_kernel<32>,
                               (const void*)hx::rns_extend_wide_kernel<36>, (const void*)hx::rns_extend_wide_kernel<40>})
-          HIPCHK(hxp::dyn_lds(f, 160 * 1024));
+          HIPCHK(hxp::dyn_lds(f, 160 * 1024, c->device));
         wide_attr.insert(c->device);
       }
     }
@@ -3020,14 +2956,12 @@ static int frac_begin(hx_ctx* c, size_t doubles)
                 "device embedding norms need m a power of two or m <= 131072 (otherwise the host keeps "
                 "the reference's noiseBoundForUniform bound)");
   if (c->frac_cap < doubles) {
-    CHK(norm_join(c, false, true));
     retire_or_free(c, c->d_frac);
     c->d_frac = nullptr;
     c->frac_cap = 0;
     HIPCHK(hipMalloc((void**)&c->d_frac, doubles * sizeof(double)));
     c->frac_cap = doubles;
   }
-  CHK(norm_join(c, false, true));  // d_frac is about to be rewritten
   c->frac_pos = 0;
   c->want_frac = true;
   c->xs_rows = 0;
@@ -3100,12 +3034,8 @@ static int bnorm_setup(hx_ctx* c)
   HIPCHK(hipMemcpy(c->d_bn_v, v.data(), sizeof(double) * 2 * m, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(c->d_bn_w, w.data(), sizeof(double) * P, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d_cv, cv.data(), sizeof(double) * 2 * P, hipMemcpyHostToDevice));
-  bool attr = false;   // (hxp::dyn_lds is idempotent per device)
-  if (!attr) {
-    HIPCHK(hxp::dyn_lds((const void*)hx::bnorm_fwd_kernel, 16 << hx::NORM_MAX_LOGH));
-    HIPCHK(hxp::dyn_lds((const void*)hx::bnorm_inv_kernel, 16 << hx::NORM_MAX_LOGH));
-    attr = true;
-  }
+  HIPCHK(hxp::dyn_lds((const void*)hx::bnorm_fwd_kernel, 16 << hx::NORM_MAX_LOGH, c->device));
+  HIPCHK(hxp::dyn_lds((const void*)hx::bnorm_inv_kernel, 16 << hx::NORM_MAX_LOGH, c->device));
   const int logp = bk, logh = std::min(logp, hx::NORM_MAX_LOGH);
   const unsigned H = 1u << logh, S = (unsigned)(P >> logh);
   const unsigned threads = std::min<unsigned>(hx::NORM_THREADS, std::max<unsigned>(64u, H / 4));
@@ -3119,7 +3049,7 @@ static int bnorm_setup(hx_ctx* c)
 }
 
 // squared norms of `rows` polynomials into c->d_norm2 (general m)
-static int embed_norms_general(hx_ctx* c, const double* d_f, int rows, hipStream_t ns)
+static int embed_norms_general(hx_ctx* c, const double* d_f, int rows)
 {
   CHK(bnorm_setup(c));
   const int logp = bn_logp(c), logh = std::min(logp, hx::NORM_MAX_LOGH);
@@ -3136,15 +3066,15 @@ static int embed_norms_general(hx_ctx* c, const double* d_f, int rows, hipStream
   const size_t lds = std::max<size_t>(16 * (size_t)H, 256);
   for (size_t r0 = 0; r0 < (size_t)rows; r0 += c->bn_rows_cap) {
     const unsigned nr = (unsigned)std::min<size_t>(c->bn_rows_cap, (size_t)rows - r0);
-    HX_LAUNCH(hx::bnorm_fwd_kernel, dim3(nr * S), dim3(threads), lds, ns,
+    HX_LAUNCH(hx::bnorm_fwd_kernel, dim3(nr * S), dim3(threads), lds, c->stream,
                        d_f + r0 * c->phim, (const double2*)c->d_bn_v, (const double2*)nullptr, c->d_bn_w,
                        (const double2*)c->d_bn_chat, c->d_bn_Z, logp, logh, c->phim, 0);
     HIPCHK(hipGetLastError());
-    HX_LAUNCH(hx::bnorm_inv_kernel, dim3(nr * S), dim3(threads), lds, ns, c->d_bn_Z, c->d_bn_w,
+    HX_LAUNCH(hx::bnorm_inv_kernel, dim3(nr * S), dim3(threads), lds, c->stream, c->d_bn_Z, c->d_bn_w,
                        logp, logh);
     HIPCHK(hipGetLastError());
     const unsigned gx = std::min<unsigned>(64u, (c->phim + 255u) / 256u);
-    HX_LAUNCH(hx::bnorm_max_kernel, dim3(gx, nr), dim3(256), 0, ns, (const double2*)c->d_bn_Z,
+    HX_LAUNCH(hx::bnorm_max_kernel, dim3(gx, nr), dim3(256), 0, c->stream, (const double2*)c->d_bn_Z,
                        c->d_bn_w, c->d_zms, c->phim, logp, logh, c->d_norm2 + r0);
     HIPCHK(hipGetLastError());
   }
@@ -3207,6 +3137,60 @@ static int norm_slot_take(hx_ctx* c, int rows, hx_ctx::NormPending* out)
   return HX_OK;
 }
 
+// The one decision of embed_norms: which kernel serves this ring.  The destination follows from it: the radix-16
+// kernels (one workgroup per polynomial and a plain store of its maximum) write the pinned, device-visible read-back
+// slot themselves; the others reduce into d_norm2 by atomicMax, which takes a zero-fill in front of them and a copy
+// kernel behind them (two ~4 us launches with their gaps per norm call, three calls per multiply).  All of it runs on
+// the context's one stream: a stream of their own gained these kernels nothing (profiles/r03_norm_kernels_ab.txt).
+enum class NormKernel {
+  General,   // m not a power of two: the complex-double Bluestein chain (embed_norms_general)
+  Plain,     // N < 4: embed_norm_kernel, the complex N-point form (the real-input forms below need N >= 4)
+  Quarter,   // 4 <= N <= 2^13: embed_norm_quarter_kernel, one N/2-point transform in one workgroup's LDS
+  R16,       // N = 2^14: embed_norm_r16_kernel, register-tiled (norm_r16.h); HX_NO_PREP_FUSE: its paired form
+  R16x2,     // N = 2^15: embed_norm_r16x2_kernel, both 2^13-point sub-transforms in one 1024-thread workgroup
+  Split      // N >= 2^16: embed_norm_quarter_split_kernel, sub-transforms of 2^13 points parked in d_norm_park
+};
+static NormKernel norm_kernel_of(const hx_ctx* c)
+{
+  static_assert(hx::NORM_MAX_LOGH == 13 && hx::R16_LOGN == 14, "the ring sizes below are these two constants");
+  if (!c->pow2)
+    return NormKernel::General;
+  if (c->logn < 2)
+    return NormKernel::Plain;
+  if (c->logn <= 13)
+    return NormKernel::Quarter;
+  return c->logn == 14 ? NormKernel::R16 : c->logn == 15 ? NormKernel::R16x2 : NormKernel::Split;
+}
+
+// The two kernels that read either source -- the mod-down's (x, S) in place or doubles: one workgroup per polynomial
+template <class SRC>
+static int norm_launch_rows(hx_ctx* c, NormKernel k, const SRC& src, int rows, unsigned long long* pinned)
+{
+  const dim3 grid((unsigned)rows);
+  if (k == NormKernel::R16) {
+    constexpr size_t lds = (size_t)hx::R16_LDS_DOUBLES * sizeof(double);   // one array: two workgroups per CU
+    if (c->sw.no_prep_fuse) {   // the paired kernel (A/B) instead of the direct form (no pairing pass)
+      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_paired_kernel<SRC>, (int)lds, c->device));
+      HX_LAUNCH((hx::embed_norm_r16_paired_kernel<SRC>), grid, dim3(hx::R16_THREADS), lds, c->stream, src, c->d_wtab, pinned, true);
+    } else {
+      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<SRC>, (int)lds, c->device));
+      HX_LAUNCH((hx::embed_norm_r16_kernel<SRC>), grid, dim3(hx::R16_THREADS), lds, c->stream, src, c->d_wtab, pinned, true);
+    }
+    return HX_OK;
+  }
+  const unsigned M = c->phim >> 1;
+  const unsigned threads = std::min<unsigned>(hx::NORM_THREADS, std::max<unsigned>(64u, M / 4));
+  const size_t lds = std::max<size_t>(16 * (size_t)M, 256);
+  if (c->logn == 13 && threads == (unsigned)hx::NORM_THREADS) {   // the instantiation with constant loop bounds
+    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_kernel<SRC, 13>, 16 << hx::NORM_MAX_LOGH, c->device));
+    HX_LAUNCH((hx::embed_norm_quarter_kernel<SRC, 13>), grid, dim3(threads), lds, c->stream, src, c->d_wtab, c->logn, c->d_norm2);
+  } else {
+    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_kernel<SRC, 0>, 16 << hx::NORM_MAX_LOGH, c->device));
+    HX_LAUNCH((hx::embed_norm_quarter_kernel<SRC, 0>), grid, dim3(threads), lds, c->stream, src, c->d_wtab, c->logn, c->d_norm2);
+  }
+  return HX_OK;
+}
+
 static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
 {
   const uint32_t N = c->phim;
@@ -3219,26 +3203,13 @@ static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
     HIPCHK(hipMalloc((void**)&c->d_norm2, sizeof(unsigned long long) * (size_t)rows));
     c->norm_cap = (size_t)rows;
   }
-  // which source the kernel will read: the mod-down's (x, S) in place, or doubles at d_f (then a pending
-  // (x, S) block is written out as doubles first -- on the main stream, before the hand-over below)
-  const bool quarter_form = c->pow2 && logn >= 2 && logn - 1 <= hx::NORM_MAX_LOGH;
-  const bool use_xs = quarter_form && c->xs_rows == rows && d_f == c->d_frac;
+  const NormKernel k = norm_kernel_of(c);
+  const bool direct = k == NormKernel::R16 || k == NormKernel::R16x2;
+  // which source the kernel will read: the mod-down's (x, S) in place (norm_launch_rows), or doubles at d_f (then a
+  // pending (x, S) block is written out as doubles first)
+  const bool use_xs = (k == NormKernel::Quarter || k == NormKernel::R16) && c->xs_rows == rows && d_f == c->d_frac;
   if (!use_xs)
     CHK(flush_xs(c));
-  hipStream_t ns = c->stream;
-  // (measured, profiles/r03_norm_side_stream_ab.txt: no gain -- the one-workgroup-per-CU norm kernel does not get
-  // onto the CUs next to a kernel that fills them -- so the side stream is opt-in: HX_NORM_ASYNC=1)
-  const bool side_stream = c->sw.norm_async;
-  if (side_stream && !c->capturing) {
-    if (!c->norm_stream) {
-      HIPCHK(hipStreamCreateWithFlags(&c->norm_stream, hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->norm_in_ev, hipEventDisableTiming));
-      HIPCHK(hipEventCreateWithFlags(&c->norm_out_ev, hipEventDisableTiming));
-    }
-    HIPCHK(hipEventRecord(c->norm_in_ev, c->stream));             // behind the producers of the input
-    HIPCHK(hipStreamWaitEvent(c->norm_stream, c->norm_in_ev, 0));
-    ns = c->norm_stream;
-  }
   // read-back through a pinned slot and an event; the slot of an (x, S) block whose prep kernels carried the norm
   // is already taken and written (scale_down_impl), and no kernel is launched for it below
   hx_ctx::NormPending np{};
@@ -3260,151 +3231,60 @@ static int embed_norms(hx_ctx* c, const double* d_f, int rows, double* out_host)
         c->norm_free.push_back(*np);
     }
   } slot_guard{c, &np};
-  // One workgroup per polynomial and a plain store of its maximum (the radix-16 kernels): the kernel writes the pinned,
-  // device-visible slot itself -- no zero-fill of d_norm2 in front of it (an atomicMax target) and no copy kernel behind
-  // it, two ~4 us launches with their gaps per norm call, three calls per multiply.
-  const bool by_copy = c->sw.norm_memcpy;
-  const bool r16_path = c->pow2 && !c->sw.norm_old && logn == 14;
-  const bool x2_path = c->pow2 && logn == 15 && !c->sw.norm_old && !c->sw.norm_plain;
-  const bool direct = !by_copy && (r16_path || x2_path);
-  unsigned long long* const out2 = direct ? np.pinned : c->d_norm2;
   if (!direct)
-    HIPCHK(hipMemsetAsync(c->d_norm2, 0, sizeof(unsigned long long) * (size_t)rows, ns));
-  if (!c->pow2) {
-    CHK(flush_xs(c));
-    CHK(embed_norms_general(c, d_f, rows, ns));
-  } else {   // (hxp::dyn_lds is idempotent per device)
-    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_kernel, 16 << hx::NORM_MAX_LOGH));
-#define HX_NORM_ATTR(...)                                                                               \
-  HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_kernel<__VA_ARGS__>,                   \
-                             hipFuncAttributeMaxDynamicSharedMemorySize, 16 << hx::NORM_MAX_LOGH))
-    HX_NORM_ATTR(hx::NormSrcF64, 0);
-    HX_NORM_ATTR(hx::NormSrcF64, 13);
-    HX_NORM_ATTR(hx::NormSrcF64, 14);
-    HX_NORM_ATTR(hx::NormSrcXS, 0);
-    HX_NORM_ATTR(hx::NormSrcXS, 13);
-    HX_NORM_ATTR(hx::NormSrcXS, 14);
-#undef HX_NORM_ATTR
-    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_split_kernel, 16 << hx::NORM_MAX_LOGH));
-  }
-  if (!c->pow2) {
-    // (done above)
-  } else if (from_prep) {
-    c->xs_rows = 0;   // (the maxima are in the slot, stored by the prep workgroups)
-  } else if (logn >= 2 && logn - 1 <= hx::NORM_MAX_LOGH) {
-    // real-input form: one N/2-point transform per polynomial, one workgroup each
-    const unsigned M = N >> 1;
-    const unsigned threads = std::min<unsigned>(hx::NORM_THREADS, std::max<unsigned>(64u, M / 4));
-    const size_t lds = std::max<size_t>(16 * (size_t)M, 256);
-    // (N = 2^13 / 2^14 with the full thread count: the instantiations with constant loop bounds)
-    const bool full = threads == (unsigned)hx::NORM_THREADS;
-#define HX_NORM_LAUNCH(SRCT, srcv)                                                                              \
-  do {                                                                                                          \
-    if (full && logn == 14)                                                                                     \
-      HX_LAUNCH((hx::embed_norm_quarter_kernel<SRCT, 14>), dim3((unsigned)rows), dim3(threads), lds,   \
-                         ns, srcv, c->d_wtab, logn, c->d_norm2);                                         \
-    else if (full && logn == 13)                                                                                \
-      HX_LAUNCH((hx::embed_norm_quarter_kernel<SRCT, 13>), dim3((unsigned)rows), dim3(threads), lds,   \
-                         ns, srcv, c->d_wtab, logn, c->d_norm2);                                         \
-    else                                                                                                        \
-      HX_LAUNCH((hx::embed_norm_quarter_kernel<SRCT, 0>), dim3((unsigned)rows), dim3(threads), lds,    \
-                         ns, srcv, c->d_wtab, logn, c->d_norm2);                                         \
-  } while (0)
-    // N = 2^14: the register-tiled kernel (norm_r16.h); HX_NORM_OLD keeps the LDS-pass kernel (A/B)
-    const bool r16 = !c->sw.norm_old;
-    constexpr size_t r16_lds = (size_t)hx::R16_LDS_DOUBLES * sizeof(double);   // one array: two workgroups per CU
-    // the direct form (no pairing pass); HX_NO_PREP_FUSE keeps the paired kernel (A/B)
-    const bool paired = c->sw.no_prep_fuse;
-    if (r16 && logn == 14) {   // (hxp::dyn_lds is idempotent per device)
-      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<hx::NormSrcXS>, (int)r16_lds));
-      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_kernel<hx::NormSrcF64>, (int)r16_lds));
-      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_paired_kernel<hx::NormSrcXS>, (int)r16_lds));
-      HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16_paired_kernel<hx::NormSrcF64>, (int)r16_lds));
-    }
-#define HX_R16_LAUNCH(SRCT, srcv)                                                                                       \
-  do {                                                                                                                  \
-    if (paired)                                                                                                         \
-      HX_LAUNCH((hx::embed_norm_r16_paired_kernel<SRCT>), dim3((unsigned)rows), dim3(hx::R16_THREADS), r16_lds, ns, srcv, \
-                c->d_wtab, out2, direct);                                                                               \
-    else                                                                                                                \
-      HX_LAUNCH((hx::embed_norm_r16_kernel<SRCT>), dim3((unsigned)rows), dim3(hx::R16_THREADS), r16_lds, ns, srcv,      \
-                c->d_wtab, out2, direct);                                                                               \
-  } while (0)
-    if (c->xs_rows == rows && d_f == c->d_frac) {
-      hx::NormSrcXS src{c->scratch[0], reinterpret_cast<const int64_t*>(c->scratch[1]), c->xs_inv_qd};
-      if (r16 && logn == 14)
-        HX_R16_LAUNCH(hx::NormSrcXS, src);
-      else
-        HX_NORM_LAUNCH(hx::NormSrcXS, src);
-    } else {
-      CHK(flush_xs(c));
-      hx::NormSrcF64 src{d_f};
-      if (r16 && logn == 14)
-        HX_R16_LAUNCH(hx::NormSrcF64, src);
-      else
-        HX_NORM_LAUNCH(hx::NormSrcF64, src);
-    }
-#undef HX_R16_LAUNCH
-#undef HX_NORM_LAUNCH
-    c->xs_rows = 0;
-  } else if (logn - 1 > hx::NORM_MAX_LOGH && !c->sw.norm_plain) {
-    // real-input form beyond one workgroup's LDS: S = N/2/8192 sub-transforms, one workgroup per pair
-    CHK(flush_xs(c));
+    HIPCHK(hipMemsetAsync(c->d_norm2, 0, sizeof(unsigned long long) * (size_t)rows, c->stream));
+  if (from_prep) {
+    // (the maxima are in the slot, stored by the prep workgroups)
+  } else if (use_xs) {
+    CHK(norm_launch_rows(c, k, hx::NormSrcXS{c->scratch[0], reinterpret_cast<const int64_t*>(c->scratch[1]), c->xs_inv_qd}, rows,
+                         np.pinned));
+  } else if (k == NormKernel::Quarter || k == NormKernel::R16) {
+    CHK(norm_launch_rows(c, k, hx::NormSrcF64{d_f}, rows, np.pinned));
+  } else if (k == NormKernel::General) {
+    CHK(embed_norms_general(c, d_f, rows));
+  } else if (k == NormKernel::R16x2) {
+    constexpr size_t lds = 2 * (size_t)hx::R16_LDS_DOUBLES * sizeof(double);
+    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16x2_kernel, (int)lds, c->device));
+    HX_LAUNCH(hx::embed_norm_r16x2_kernel, dim3((unsigned)rows), dim3(2 * hx::R16_THREADS), lds, c->stream, d_f, c->d_wtab,
+              np.pinned, true);
+  } else if (k == NormKernel::Split) {
+    // S = N/2/8192 sub-transforms, one workgroup per pair
     const int logh = hx::NORM_MAX_LOGH;
     const unsigned H = 1u << logh, S = (N >> 1) >> logh;
     const size_t park_words = (size_t)rows * (S / 2) * H;   // complex doubles
-    const bool x2 = logn == 15 && !c->sw.norm_old;
-    if (!x2 && c->norm_park_cap < park_words) {
+    if (c->norm_park_cap < park_words) {
       retire_or_free(c, c->d_norm_park);
       c->d_norm_park = nullptr;
       c->norm_park_cap = 0;
       HIPCHK(hipMalloc((void**)&c->d_norm_park, park_words * sizeof(double2)));
       c->norm_park_cap = park_words;
     }
-    if (x2) {
-      // both sub-transforms at once in one 1024-thread workgroup (norm_r16.h: r16x2), nothing parked
-      constexpr size_t x2_lds = 2 * (size_t)hx::R16_LDS_DOUBLES * sizeof(double);
-      bool attrx2 = false;   // (hxp::dyn_lds is idempotent per device)
-      if (!attrx2) {
-        HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_r16x2_kernel, (int)x2_lds));
-        attrx2 = true;
-      }
-      HX_LAUNCH(hx::embed_norm_r16x2_kernel, dim3((unsigned)rows), dim3(2 * hx::R16_THREADS), x2_lds, ns, d_f, c->d_wtab,
-                out2, direct);
-    } else
-    HX_LAUNCH(hx::embed_norm_quarter_split_kernel, dim3((unsigned)rows * (S / 2)), dim3(hx::NORM_THREADS),
-                       16 * (size_t)H, ns, d_f, c->d_wtab, logn, logh, c->d_norm_park, c->d_norm2);
-  } else {
-    CHK(flush_xs(c));
+    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_quarter_split_kernel, 16 << hx::NORM_MAX_LOGH, c->device));
+    HX_LAUNCH(hx::embed_norm_quarter_split_kernel, dim3((unsigned)rows * (S / 2)), dim3(hx::NORM_THREADS), 16 * (size_t)H,
+              c->stream, d_f, c->d_wtab, logn, logh, c->d_norm_park, c->d_norm2);
+  } else {   // NormKernel::Plain: N < 4 (m = 4 in the tests)
     const int logh = std::min(logn, hx::NORM_MAX_LOGH);
     const unsigned H = 1u << logh, S = N >> logh;
     const unsigned threads = std::min<unsigned>(hx::NORM_THREADS, std::max<unsigned>(64u, H / 4));
     const size_t lds = std::max<size_t>(16 * (size_t)H, 256);
-    HX_LAUNCH(hx::embed_norm_kernel, dim3((unsigned)rows * S), dim3(threads), lds, ns, d_f,
-                       c->d_wtab, logn, logh, c->d_norm2);
+    HIPCHK(hxp::dyn_lds((const void*)hx::embed_norm_kernel, 16 << hx::NORM_MAX_LOGH, c->device));
+    HX_LAUNCH(hx::embed_norm_kernel, dim3((unsigned)rows * S), dim3(threads), lds, c->stream, d_f, c->d_wtab, logn, logh,
+              c->d_norm2);
   }
   HIPCHK(hipGetLastError());
+  c->xs_rows = 0;
   np.rows = rows;
   np.out = out_host;
-  // the few words go to the pinned slot by a kernel writing host memory (hipHostMalloc memory is device-visible),
-  // not by a device-to-host copy command: HX_NORM_MEMCPY=1 restores the copy (A/B)
-  if (direct) {
-    // (written by the norm kernel itself)
-  } else if (by_copy) {
-    HIPCHK(hipMemcpyAsync(np.pinned, c->d_norm2, sizeof(unsigned long long) * (size_t)rows,
-                          hipMemcpyDeviceToHost, ns));
-  } else {
-    HX_LAUNCH(hx::copy_words_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, ns,
+  // d_norm2's few words go to the pinned slot by a kernel writing host memory (hipHostMalloc memory is device-visible),
+  // not by a device-to-host copy command
+  if (!direct) {
+    HX_LAUNCH(hx::copy_words_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream,
               reinterpret_cast<uint64_t*>(np.pinned), reinterpret_cast<const uint64_t*>(c->d_norm2), (size_t)rows);
     HIPCHK(hipGetLastError());
   }
-  HIPCHK(hipEventRecord(np.ev, ns));
+  HIPCHK(hipEventRecord(np.ev, c->stream));
   c->norm_pending.push_back(np);
   slot_guard.armed = false;
-  if (ns != c->stream) {
-    HIPCHK(hipEventRecord(c->norm_out_ev, ns));
-    (use_xs ? c->norm_reads_xs : c->norm_reads_frac) = true;
-  }
   if (c->defer_norms)
     return HX_OK;
   return hx_norms_flush(c);
@@ -3650,7 +3530,7 @@ static int scale_down_multi_fused(hx_poly** ps, int np, const std::vector<int>& 
   for (int i = 0; i < np; i++)
     if (!ps[i]->owns)
       return HX_ERR_UNSUPPORTED;  // caller-owned storage wants its result in place
-  if (tsrc && (np != 3 || c->sw.no_tensor_multi))
+  if (tsrc && np != 3)
     return HX_ERR_UNSUPPORTED;
   const size_t rw = a->row_words();
   const int batch = a->batch;
@@ -4016,8 +3896,7 @@ static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* 
     const size_t nfrac = rw * (size_t)pb.n;
     const bool xs_in_place = c->want_frac && c->xs_rows == 0 && c->frac_pos == 0 && nfrac <= c->frac_cap && !c->want_fdelta;
     // (ptxt < 2^32: the norm-carrying kernels keep no scalar registers for the wide correction's constants)
-    const bool norm_in_prep = P.fuse && xs_in_place && c->logn == 14 && !c->sw.norm_old && !c->sw.norm_memcpy &&
-                              !c->sw.norm_async && !c->capturing && (ptxt >> 32) == 0;
+    const bool norm_in_prep = P.fuse && xs_in_place && c->logn == 14 && !c->capturing && (ptxt >> 32) == 0;
     if (norm_in_prep) {
       prep_norm_drop(c);   // (a slot an earlier call took and then failed before it had an (x, S) block to go with it)
       CHK(norm_wtab(c));
@@ -4524,13 +4403,12 @@ static int break_digits_fused(hx_ctx* c, const uint64_t* coef, const std::vector
   if (fast) {
     const int lds_rows = std::max(1, L - hx::break_fast_n0(A));
     // (the column caps the resident waves at 160 KiB / (rows x 8 B x 64 lanes) per CU: 16 rows at the CKKS chain = five
-    // waves per SIMD where the registers allow seven -- worth 24 % by the HX_BRK_LDS_PAD probe; the two ways tried to
+    // waves per SIMD where the registers allow seven -- worth 24 % by a probe that padded the column; the two ways tried to
     // move the column out of the LDS did not pay: profiles/r06_ab_digit_kernel_occupancy.json)
     for (const void* f : {(const void*)hx::break_digits_fast_kernel<true, false>, (const void*)hx::break_digits_fast_kernel<false, false>,
                           (const void*)hx::break_digits_fast_kernel<true, true>, (const void*)hx::break_digits_fast_kernel<false, true>})
-      HIPCHK(hxp::dyn_lds(f, 64 * hx::BRK_THREADS * 8));
-    // (HX_BRK_LDS_PAD: unused rows on top, to measure what the kernel's occupancy is worth -- profiles/r06_ab_digit_kernel_occupancy)
-    const size_t lds_fast = (size_t)(lds_rows + std::max(0, std::min(40, c->sw.brk_lds_pad_rows))) * hx::BRK_THREADS * 8;
+      HIPCHK(hxp::dyn_lds(f, 64 * hx::BRK_THREADS * 8, c->device));
+    const size_t lds_fast = (size_t)lds_rows * hx::BRK_THREADS * 8;
     bool hps = rw < ((size_t)1 << 32);
     for (int d = 0; d < ndig; d++)
       hps = hps && A.plan[d].hps_ok && (int)A.plan[d].n >= c->sw.brk_hps_min_n;
@@ -4551,18 +4429,10 @@ static int break_digits_fused(hx_ctx* c, const uint64_t* coef, const std::vector
     }
 #undef HX_BRK_LAUNCH
   } else if (nmax <= 8) {
-    bool attr8 = false;   // (hxp::dyn_lds is idempotent per device)
-    if (!attr8) {
-      HIPCHK(hxp::dyn_lds((const void*)hx::break_digits_kernel<8>, 64 * hx::BRK_THREADS * 8));
-      attr8 = true;
-    }
+    HIPCHK(hxp::dyn_lds((const void*)hx::break_digits_kernel<8>, 64 * hx::BRK_THREADS * 8, c->device));
     HX_LAUNCH((hx::break_digits_kernel<8>), grid, block, lds, c->stream, A, rw);
   } else {
-    bool attr16 = false;   // (hxp::dyn_lds is idempotent per device)
-    if (!attr16) {
-      HIPCHK(hxp::dyn_lds((const void*)hx::break_digits_kernel<16>, 64 * hx::BRK_THREADS * 8));
-      attr16 = true;
-    }
+    HIPCHK(hxp::dyn_lds((const void*)hx::break_digits_kernel<16>, 64 * hx::BRK_THREADS * 8, c->device));
     HX_LAUNCH((hx::break_digits_kernel<16>), grid, block, lds, c->stream, A, rw);
   }
   HIPCHK(hipGetLastError());
@@ -5068,12 +4938,6 @@ static int relin_core(hx_ctx* c, const uint64_t* t2e, const std::vector<int>& ow
       for (int r = 0; r < nall; r++)
         if (owner[r] != d && fd[r] != d)
           rows.emplace_back(d * nall + r, all[r]);
-    // N = 2^15: out of place, so that the two-workgroups-per-row forward kernel applies (ntt_launch); the key switch
-    // reads the extension rows only, all of which are written there
-    if (c->pow2 && c->logn == 15 && c->sw.half15) {
-      CHK(ensure_scratch(c, 10, (size_t)ndig * nall * rw));
-      digits_eval = c->scratch[10];
-    }
     CHK(ntt_list(c, c->scratch[1], digits_eval, rows, batch, false, /*lazy_in=*/true));
   }
   std::vector<std::vector<int>> dprimes(ndig);

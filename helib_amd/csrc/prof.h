@@ -76,8 +76,6 @@ inline hipError_t dyn_lds(const void* kern, int bytes, int device = -1)
   }
   return e;
 }
-// (the signature of hipFuncSetAttribute, for the call sites that were written against it)
-inline hipError_t dyn_lds(const void* kern, hipFuncAttribute, int bytes) { return dyn_lds(kern, bytes); }
 
 struct Rec {
   int name, device;

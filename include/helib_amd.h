@@ -200,14 +200,13 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
  * None is needed in production: each selects the older or the generic form of a path, for tests that must reach it
  * and for same-box A/B measurements; results are bit-identical either way.  The library snapshots them when a
  * context is created (hx_ctx_create; helib_amd/csrc/switches.h is the one place that reads the environment).
- *   HX_NO_HPS, HX_HPS_EPS=x, HX_HPS_MIN_N=n   exact-RNS kernels: Garner instead of the HPS front end; the trust
- *                                            margin of an HPS quotient (default 2^-30); HPS from n sources on (9)
- *   HX_NO_LAZY_RNS                            no 128-bit lazy sums / single-subtraction Garner steps
- *   HX_NO_FAST_BREAK, HX_NO_FAST_EXTEND, HX_NO_WIDE_EXTEND   generic breakIntoDigits / basis-extension kernels
+ *   HX_HPS_EPS=x, HX_HPS_MIN_N=n              exact-RNS kernels: the trust margin of an HPS quotient (default 2^-30); the
+ *                                            HPS front end instead of Garner from n sources on (9; the digit kernel: 5)
+ *   HX_NO_MFMA_EXT, HX_MFMA_MIN_N=n           basis extension: VALU limb products instead of the matrix-core kernel; the
+ *                                            matrix-core kernel from n sources on (9)
  *   HX_NO_MASK_SPLIT                          hx_mask_split as hx_poly_copy + hx_mul + hx_sub per part
  *   HX_NO_MASK_FAN                            hx_mask_fan as hx_poly_copy + hx_mul per output and part
- *   HX_NO_TENSOR_MULTI, HX_NO_MULRELIN_FUSE   tensor product as a pass of its own in front of the several-primes
- *                                            mod-switch / inside hx_mul_relin
+ *   HX_NO_MULRELIN_FUSE                       tensor product as a pass of its own inside hx_mul_relin
  *   HX_NO_KS_LAST_FUSE                        relinearisation: every extension row transformed by the row kernel and the key
  *                                            switch as a launch of its own, instead of each output row's last digit transform
  *                                            fused into the key switch
@@ -222,11 +221,9 @@ int hx_break_into_digits(const hx_poly* a, const int* dig_idx, const int* dig_of
  *   HX_BLUE_OLD                               general m: the chain of passes instead of one convolution kernel
  *   HX_NO_PFA                                 m = 21845: Bluestein instead of the Good-Thomas x Rader kernels
  *   HX_PFA_NO_REM                             ... their inverse without the fused rem Phi_m (two convolution launches instead)
- *   HX_NORM_ASYNC, HX_NORM_OLD, HX_NORM_PLAIN, HX_NORM_MEMCPY
- *                                            variants of the canonical-embedding norm kernels and their read-back
  *   HX_WAIT_POLL_US=n                         how long a norm read-back is polled for before the thread sleeps (2000)
  *   HX_ARENA_TRACE                            one line on stderr per hipMalloc of the slab arena
- * (include/helib_amd_ctxt.hpp, the C++ host: HX_NO_LAZY_TENSOR -- multiplyBy forms the tensor product eagerly.) */
+ * (The C++ host, include/helib_amd_ctxt.hpp, reads none of its own.) */
 
 /* ---------------- ciphertext-level fused loops ---------------- */
 /* KeySwitch matrix W (include/helib/keySwitching.h:86-101) with the a-column

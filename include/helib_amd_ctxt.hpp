@@ -1498,8 +1498,7 @@ private:
       IndexSet idx = c0.getIndexSet();
       DoubleCRT::Uninitialized u;
       DoubleCRT t0(*dev, idx, c0.batch(), u), t1(*dev, idx, c0.batch(), u), t2(*dev, idx, c0.batch(), u);
-      static const bool lazy_off = std::getenv("HX_NO_LAZY_TENSOR") != nullptr;   // (A/B switch)
-      if (lazy && !lazy_off)   // copies of the operand parts are copy-on-write handles: nothing moves
+      if (lazy)   // copies of the operand parts are copy-on-write handles: nothing moves
         pendingTensor = std::make_shared<PendingTensor>(PendingTensor{c0, c1, d0, d1});
       else
         helib_amd::tensorProduct(c0, c1, d0, d1, t0, t1, t2);

@@ -1080,17 +1080,31 @@ def test_cpp_facade_matches_oracle(hx, tmp_path):
 NORM_RTOL = 1e-9   # double-precision FFT vs the oracle's long-double evaluation
 
 
+# the norm kernel that serves each power-of-two ring (engine.hip norm_kernel_of: the ring alone decides), from doubles
+NORM_KERNEL_OF_M = {4: "embed_norm_kernel",                                   # N < 4
+                    16: "embed_norm_quarter_kernel<NormSrcF64, 0>",           # 4 <= N <= 2^13 ...
+                    1024: "embed_norm_quarter_kernel<NormSrcF64, 0>",
+                    16384: "embed_norm_quarter_kernel<NormSrcF64, 13>",       # ... N = 2^13: constant loop bounds
+                    32768: "embed_norm_r16_kernel<NormSrcF64>",               # N = 2^14
+                    65536: "embed_norm_r16x2_kernel",                         # N = 2^15
+                    131072: "embed_norm_quarter_split_kernel"}                # N >= 2^16
+
+
 @pytest.mark.parametrize("m", [4, 16, 1024, 16384, 32768, 65536, 131072])
 def test_embedding_norm_device_matches_oracle(hx, m):
     """embeddingLargestCoeff (src/norms.cpp:480-493) on the device: N <= 8192 in one workgroup,
-    larger N split by DIF levels over 2..8 workgroups per polynomial."""
+    larger N split by DIF levels over 2..8 workgroups per polynomial -- and each ring served by its own kernel,
+    checked by name."""
     g = hx.Context(m)
     N = g.phim
     rng = np.random.default_rng(m)
     f = np.stack([rng.normal(size=N), rng.integers(-32768, 32769, size=N).astype(float),
                   np.ones(N), np.eye(1, N, N - 1)[0], np.zeros(N),
                   np.cos(2 * np.pi * 5 * np.arange(N) / m)])
+    hx.profileBegin()
     got = hx.embeddingLargestCoeff(g, f)
+    ran = {k["kernel"].replace("hx::", "") for k in hx.profileEnd()["kernels"]}
+    assert {n for n in ran if "norm" in n} == {NORM_KERNEL_OF_M[m]}, ran
     for r in range(f.shape[0]):
         want = O.embedding_largest_coeff(m, f[r])
         assert got[r] == pytest.approx(want, rel=NORM_RTOL, abs=1e-300), (m, r)
@@ -1647,19 +1661,6 @@ def test_ckks_encrypt_multiply_decrypt_gpu_vs_oracle(hx, m, precision, bits, c, 
         w = np.convolve(ab, ab)
         want = w[:n] - np.append(w[n:], 0.0)
         assert np.max(np.abs(got - want)) < 2.0 ** (-precision + 6) / n
-
-
-def test_half_row_forward_transform_at_2p15_probe(hx, monkeypatch):
-    """HX_HALF15=1: the forward transform of the digit rows of hx_mul_relin at N = 2^15 as two 2^14-point workgroups per
-    row (ntt_kernels.hip ntt_row_half15_kernel: first Cooley-Tukey stage in the load, the sub-transform's tables,
-    interleaved outputs; Cmodulus::FFT, src/CModulus.cpp:389-426) -- measured slower than the one-workgroup kernel and off
-    by default (profiles/r06_ab_half_row_forward_2p15.json); the probe must stay bit-exact: the reference's own CKKS
-    parameters through it, and the kernel that ran checked by name."""
-    monkeypatch.setenv("HX_HALF15", "1")
-    hx.profileBegin()
-    test_ckks_m65536_chain_batched_bit_exact(hx, monkeypatch, 1, 440, (8, 3, 3))
-    names = " ".join(k["kernel"] for k in hx.profileEnd()["kernels"])
-    assert "ntt_row_half15_kernel<8>" in names, names
 
 
 @pytest.mark.parametrize("precision,bits,shape", [(20, 1400, (24, 8, 3)), (1, 1400, (24, 8, 3)), (1, 440, (8, 3, 3))])

@@ -355,6 +355,30 @@ def test_product_does_not_import_oracle():
                                      "cpu_baseline_all_cores"), node.name
 
 
+def test_every_environment_switch_is_set_by_a_test_or_a_tool():
+    """A switch selects a second path through the engine; one that no test, tool or bench.py sets is a path nothing
+    runs.  Every HX_* name the library hands to getenv (helib_amd/csrc/switches.h: directly or through its on()
+    helper, so every "HX_..." literal of a file that calls getenv counts) must be named under tests/, tools/ or in
+    bench.py -- except the diagnostic and the wait policy, which select no compute path."""
+    exempt = {"HX_ARENA_TRACE", "HX_WAIT_POLL_US"}
+    read = set()
+    for sub in (os.path.join("helib_amd", "csrc"), "include"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, sub)):
+            for f in files:
+                txt = open(os.path.join(dirpath, f), errors="ignore").read()
+                if "getenv" in txt:
+                    read |= set(re.findall(r'"(HX_[A-Z0-9_]+)"', txt))
+    assert exempt <= read and len(read) > len(exempt), sorted(read)
+    users = open(os.path.join(ROOT, "bench.py")).read()
+    for sub in ("tests", "tools"):
+        for dirpath, _, files in os.walk(os.path.join(ROOT, sub)):
+            for f in files:
+                if f.endswith((".py", ".sh", ".cpp", ".h", ".hpp", ".hip")):
+                    users += open(os.path.join(dirpath, f), errors="ignore").read()
+    unused = sorted(n for n in read - exempt if not re.search(r"\b%s\b" % n, users))
+    assert not unused, f"environment switches that no test, tool or bench.py sets: {unused}"
+
+
 def test_hostnt_matches_oracle():
     from helib_amd import hostnt
     for length, m in [(60, 32768), (56, 32768), (49, 16384), (60, 21845), (59, 65536)]:
