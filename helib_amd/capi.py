@@ -60,7 +60,7 @@ SYMBOLS = [
     "hx_tensor_bring_to_set", "hx_tensor_bring_to_set_norms", "hx_mul_relin_norms",
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
-    "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum", "hx_mask_fan",
+    "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum", "hx_mask_fan", "hx_tensor_sum",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -169,6 +169,7 @@ def lib():
             "hx_mask_fan": [vp, vp, C.c_int, vp, vp, vp],
             "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
             "hx_lin_comb": [vp, vp, vp, vp, ip, vp, vp],
+            "hx_tensor_sum": [vp, vp, vp, vp, vp, vp, vp, ip],
             "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
             "hx_hoisted_automorph_sum": [vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
@@ -1195,6 +1196,27 @@ def linComb(in0, in1, idx, w, addend=None):
     _chk(lib().hx_lin_comb(out0.h, out1.h if out1 is not None else None, arr(in0), arr(in1) if in1 is not None else None,
                            n, _p(wa), _p(aa) if aa is not None else None))
     return out0, out1
+
+
+def tensorSum(a0, a1, b0, b1):
+    """o0 = sum_t a0[t] b0[t], o1 = sum_t (a0[t] b1[t] + a1[t] b0[t]), o2 = sum_t a1[t] b1[t] in one pass
+    (hx_tensor_sum): the tensor products of n pairs of canonical ciphertexts and their part-wise sums, the loop of
+    innerProduct before its relinearisation (src/Ctxt.cpp:2885-2891).  a0 / a1 and b0 / b1: the parts pointing at 1 and
+    at s of the two operands of every pair, all on one prime set and batch; operands may repeat.
+    -> (o0, o1, o2), new DoubleCRTs on that prime set."""
+    if a0 is None or a1 is None or b0 is None or b1 is None:
+        raise InvalidArgument(HX_ERR_INVALID, "tensorSum: a0, a1, b0 and b1 are required")
+    n = len(a0)
+    if n < 1:
+        raise InvalidArgument(HX_ERR_INVALID, "tensorSum needs at least one term")
+    if len(a1) != n or len(b0) != n or len(b1) != n:
+        raise InvalidArgument(HX_ERR_INVALID, "tensorSum: a0, a1, b0 and b1 go together, term by term")
+    outs = [likeUninit(a0[0]) for _ in range(3)]
+
+    def arr(ps):
+        return (C.c_void_p * n)(*[p.h for p in ps])
+    _chk(lib().hx_tensor_sum(outs[0].h, outs[1].h, outs[2].h, arr(a0), arr(a1), arr(b0), arr(b1), n))
+    return tuple(outs)
 
 
 def hoistedAutomorphSum(digits, c0, c1, ks, Ws, special):

@@ -23,7 +23,11 @@
 // (src/matmul.cpp:2878-2887: acc += *precon.automorph(p^i)), every digit word and key word read once per term and the two
 // outputs written once; and of the mask stage of a permutation-network layer (hx_mask_fan):
 //   out[k] = c * mask[k],  k < K
-// (src/PermNetwork.cpp:239-242: tmp = c; tmp.multByConstant(mask_k) per shift amount), c read once for the K products.
+// (src/PermNetwork.cpp:239-242: tmp = c; tmp.multByConstant(mask_k) per shift amount), c read once for the K products;
+// and of the loop of innerProduct before its relinearisation (hx_tensor_sum):
+//   (o0, o1, o2) = sum_t tensor((a0[t], a1[t]), (b0[t], b1[t]))
+// (src/Ctxt.cpp:2885-2891: tmp = *v1[i]; tmp.multLowLvl(*v2[i]); result += tmp), the 4 n operand rows read once and the
+// three parts of the sum written once.
 // The unit reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
 // key-switching matrix's rows, the tables of Z_m^*).
 #include <hip/hip_runtime.h>
@@ -149,6 +153,87 @@ mul_add_many_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, ro
     st_stream2(out0 + row_off + boff[b], make_ulonglong2((uint64_t)a0[b][0], (uint64_t)a0[b][1]));
     if (PARTS == 2)
       st_stream2(out1 + row_off + boff[b], make_ulonglong2((uint64_t)a1[b][0], (uint64_t)a1[b][1]));
+  }
+}
+
+// o0 = sum_t a0[t] b0[t], o1 = sum_t (a0[t] b1[t] + a1[t] b0[t]), o2 = sum_t a1[t] b1[t], t < n (hx_tensor_sum): the
+// words that n x hx_tensor and the part-wise hx_add of the products leave, since the canonical residue of an exact sum
+// of products does not depend on the order of its terms.  The accumulators start from zero; o1 takes two products per
+// term, so a reduction every TSUM_CHUNK = MAD_CHUNK / 2 terms keeps it within mul_add_many_kernel's bound.
+constexpr int TSUM_CHUNK = 128;
+static_assert(2 * TSUM_CHUNK <= MAD_CHUNK &&
+                  (~(u128)0 - (MAD_QMAX - 1)) / ((MAD_QMAX - 1) * (MAD_QMAX - 1)) >= (u128)(2 * TSUM_CHUNK),
+              "2 TSUM_CHUNK products of residues and one residue must fit 128 bits");
+
+// Table (device, uint64 words, read through the constant address space: wave-uniform scalar loads): [0, n) the bases
+// of a0[t]; [n, 2n) of a1[t]; [2n, 3n) of b0[t]; [3n, 4n) of b1[t].  All of them and the three outputs share one prime
+// set and batch, so one row offset serves every operand.  The thread shape is mul_add_many_kernel's: two adjacent
+// coefficients of one prime row for BP batch elements; per term 4 BP operand vectors loaded (16 bytes each,
+// non-temporal), 8 BP products into 6 BP 128-bit accumulators; 3 BP vectors stored at the end.  No LDS.  Operands may
+// repeat (a square, one poly in several terms): they are only read.
+template <int BP>
+__global__ void __launch_bounds__(256)
+tensor_sum_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, uint64_t* __restrict__ out2, ro_u64 tab, int n,
+                  int batch, uint32_t N, MadRows map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t k = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = row_off + (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i;
+  u128 s0[BP][2], s1[BP][2], s2[BP][2];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    s0[b][0] = s0[b][1] = s1[b][0] = s1[b][1] = s2[b][0] = s2[b][1] = 0;
+  for (int t0 = 0; t0 < n; t0 += TSUM_CHUNK) {
+    const int t1 = t0 + TSUM_CHUNK < n ? t0 + TSUM_CHUNK : n;
+    for (int t = t0; t < t1; t++) {
+      const uint64_t* pa0 = reinterpret_cast<const uint64_t*>(tab[t]);
+      const uint64_t* pa1 = reinterpret_cast<const uint64_t*>(tab[(size_t)n + t]);
+      const uint64_t* pb0 = reinterpret_cast<const uint64_t*>(tab[2 * (size_t)n + t]);
+      const uint64_t* pb1 = reinterpret_cast<const uint64_t*>(tab[3 * (size_t)n + t]);
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        const ulonglong2 x0 = ld_stream2(pa0 + boff[b]);
+        const ulonglong2 x1 = ld_stream2(pa1 + boff[b]);
+        const ulonglong2 y0 = ld_stream2(pb0 + boff[b]);
+        const ulonglong2 y1 = ld_stream2(pb1 + boff[b]);
+        s0[b][0] += (u128)x0.x * y0.x;
+        s0[b][1] += (u128)x0.y * y0.y;
+        s1[b][0] += (u128)x0.x * y1.x;
+        s1[b][1] += (u128)x0.y * y1.y;
+        s1[b][0] += (u128)x1.x * y0.x;
+        s1[b][1] += (u128)x1.y * y0.y;
+        s2[b][0] += (u128)x1.x * y1.x;
+        s2[b][1] += (u128)x1.y * y1.y;
+      }
+    }
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+#pragma unroll
+      for (int j = 0; j < 2; j++) {
+        s0[b][j] = mad_reduce(s0[b][j], q, mu, mu64, k);
+        s1[b][j] = mad_reduce(s1[b][j], q, mu, mu64, k);
+        s2[b][j] = mad_reduce(s2[b][j], q, mu, mu64, k);
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    st_stream2(out0 + boff[b], make_ulonglong2((uint64_t)s0[b][0], (uint64_t)s0[b][1]));
+    st_stream2(out1 + boff[b], make_ulonglong2((uint64_t)s1[b][0], (uint64_t)s1[b][1]));
+    st_stream2(out2 + boff[b], make_ulonglong2((uint64_t)s2[b][0], (uint64_t)s2[b][1]));
   }
 }
 
@@ -1523,6 +1608,65 @@ extern "C" int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* i
   RC(tab.commit(f.v.stream));
   HX_LAUNCH_PW(lin_comb_kernel, out1 ? 2 : 1, f.bp != 1, 1, 4, f.grid(), f.v.stream, o0, o1, hx::as_ro(tab.d), n, rows, f.batch,
                f.N, f.map, f.primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_poly* const* a0, const hx_poly* const* a1,
+                             const hx_poly* const* b0, const hx_poly* const* b1, int n)
+{
+  if (!o0 || !o1 || !o2 || !a0 || !a1 || !b0 || !b1)
+    return err(HX_ERR_INVALID, "null argument");
+  if (n < 1)
+    return err(HX_ERR_INVALID, "hx_tensor_sum needs at least one term (n = %d)", n);
+  if (o0 == o1 || o0 == o2 || o1 == o2)
+    return err(HX_ERR_INVALID, "two outputs are the same poly");
+  const hx_poly* const* in[4] = {a0, a1, b0, b1};
+  static const char* const name[4] = {"a0", "a1", "b0", "b1"};
+  hx_ctx* ctx = hxi::poly_ctx(o0);
+  if (hxi::poly_ctx(o1) != ctx || hxi::poly_ctx(o2) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  for (int t = 0; t < n; t++)
+    for (int j = 0; j < 4; j++) {
+      const hx_poly* p = in[j][t];
+      if (!p)
+        return err(HX_ERR_INVALID, "null poly (%s[%d])", name[j], t);
+      if (hxi::poly_ctx(p) != ctx)
+        return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects (%s[%d])", name[j], t);
+      if (p == o0 || p == o1 || p == o2)
+        return err(HX_ERR_INVALID, "an output is also an input (%s[%d])", name[j], t);
+    }
+  Frame f;
+  RC(f.open(ctx, o0, "hx_tensor_sum uploads a pointer table and cannot be captured in a graph"));
+  RC(same_shape(o1, f, "o1 differs from o0 in batch or prime set"));
+  RC(same_shape(o2, f, "o2 differs from o0 in batch or prime set"));
+  RC(f.even("hx_tensor_sum"));
+  for (int t = 0; t < n; t++)
+    for (int j = 0; j < 4; j++) {
+      RC(same_shape(in[j][t], f, "%s[%d] differs from o0 in batch or prime set", name[j], t));
+      if (!aligned16(hxi::poly_rows_read(in[j][t])))
+        return err(HX_ERR_INVALID, "%s[%d]: rows are not 16-byte aligned", name[j], t);
+    }
+  if (f.rows == 0)
+    return HX_OK;
+  // table (kernel's layout): the bases of a0, a1, b0, b1
+  Table tab;
+  RC(tab.acquire(f, 4 * (size_t)n));
+  // the outputs first: one that still shares a poly's rows (a lazy hx_poly_copy) lets go of them before the inputs'
+  // addresses are read into the table
+  uint64_t* o[3] = {nullptr, nullptr, nullptr};
+  RC(hxi::poly_rows_write(o0, &o[0]));
+  RC(hxi::poly_rows_write(o1, &o[1]));
+  RC(hxi::poly_rows_write(o2, &o[2]));
+  if (!aligned16(o[0], o[1], o[2]))
+    return err(HX_ERR_INVALID, "output rows are not 16-byte aligned");
+  for (int j = 0; j < 4; j++)
+    for (int t = 0; t < n; t++)
+      tab.h[(size_t)j * n + t] = (uint64_t)(uintptr_t)hxi::poly_rows_read(in[j][t]);
+  RC(tab.commit(f.v.stream));
+  // (BP = 4 holds 24 128-bit accumulators and 16 operand vectors without scratch: DESIGN.md 3.9r)
+  HX_LAUNCH_W(f.bp != 1, (hx::tensor_sum_kernel<1>), (hx::tensor_sum_kernel<4>), f.grid(), f.v.stream, o[0], o[1], o[2],
+              hx::as_ro(tab.d), n, f.batch, f.N, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
 }

@@ -1623,6 +1623,59 @@ class Ctxt:
     # fused form won every alternated pair against the loop (tools/bench_thin_recrypt.py, profiles/thin_recrypt.json,
     # DESIGN 3.9p); set it to False to get the loop back
     fuseHoistedSum = True
+    # fused=None in Ctxt.innerProduct: the loop until hx_tensor_sum has been measured as the faster form in every pair
+    # of tools/bench_binary_arith.py
+    fuseTensorSum = False
+
+    @staticmethod
+    def innerProduct(v1, v2, fused=None):
+        """sum_i v1[i] * v2[i] with the low-level product and ONE relinearisation at the end (innerProduct,
+        src/Ctxt.cpp:2878-2893), as a new ciphertext.  fused=False is the reference's loop.  Fused: every pair's
+        multLowLvl runs as in the loop -- the prime-set decision, the mod-switch of the operands, the bookkeeping, the
+        measured norms -- but leaves its tensor product pending; when every pair is two canonical two-part ciphertexts
+        and the n products ended on one prime set (rows in one order) with one ptxtSpace and one intFactor, which is
+        when addCtxt would add the parts as they are, one ops.tensorSum (hx_tensor_sum) forms the three parts of the
+        sum, and lnNoise and ptxtMag are combined in the loop's order by addCtxt's formulas.  In every other case (CKKS
+        among them: addCtxt equalises rational factors) the products are formed and added as the loop adds them.  Then
+        reLinearize() as it is.  fused=True insists on a backend with tensorSum; fused=None follows
+        Ctxt.fuseTensorSum.  Words, lnNoise, primeSet, ptxtSpace, intFactor and ptxtMag are the same either way."""
+        n = min(len(v1), len(v2))
+        if n <= 0:
+            raise ValueError("innerProduct of empty vectors")
+        has = hasattr(v1[0].ops, "tensorSum")
+        if fused and not has:
+            raise RuntimeError("Ctxt::innerProduct: fused=True, but this backend has no tensorSum")
+        if not ((Ctxt.fuseTensorSum if fused is None else fused) and has) or n == 1:
+            return innerProduct(v1, v2)
+        prods = []
+        for i in range(n):
+            tmp = v1[i].clone()
+            tmp.multLowLvl(v2[i], lazyTensor=True)
+            prods.append(tmp)
+        result = prods[0]
+        pend = [c._pendT for c in prods]
+        one = (not result.context.ckks and all(t is not None for t in pend)
+               and all(c.primeSet == result.primeSet and c.ptxtSpace == result.ptxtSpace
+                       and c.intFactor == result.intFactor for c in prods[1:]))
+        if one:
+            rows = pend[0][0].getIndexSet()
+            one = all(t[0].getIndexSet() == rows for t in pend[1:])
+        if not one:
+            for c in prods:
+                c._materializeTensor()
+            for c in prods[1:]:
+                result.addCtxt(c)
+        else:
+            # the launch first: reading lnNoise waits for the mod-switches' norms, and the device works meanwhile
+            t0, t1, t2 = result.ops.tensorSum(*[[t[j] for t in pend] for j in range(4)])
+            for c in prods[1:]:    # addCtxt's bookkeeping (src/Ctxt.cpp:1554-1555), while the operands still say where
+                result.ptxtMag += c.ptxtMag                       # the deferred norms live
+                result.lnNoise = logaddexp(result.lnNoise, c.lnNoise)
+            for c in prods:
+                c._pendT = None
+            result.parts = {"1": t0, "s": t1, "s2": t2}
+        result.reLinearize()
+        return result
 
     @staticmethod
     def linearCombination(terms, free=0, fused=None):

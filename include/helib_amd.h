@@ -663,6 +663,27 @@ int hx_scaled_sub(hx_poly* c0, hx_poly* c1, const hx_poly* t0, const hx_poly* t1
  * HX_ERR_UNSUPPORTED before touching the device.  Asynchronous on the context's stream. */
 int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* in0, const hx_poly* const* in1, int n,
                 const uint64_t* w, const uint64_t* addend);
+/* The loop of innerProduct before its one relinearisation (src/Ctxt.cpp:2885-2891:
+ *   result = *v1[0];  result.multLowLvl(*v2[0]);
+ *   for i = 1 .. n-1:  tmp = *v1[i];  tmp.multLowLvl(*v2[i]);  result += tmp;)
+ * once the operands of every pair sit on one prime set: n x Ctxt::tensorProduct of two canonical ciphertexts
+ * (src/Ctxt.cpp:1576-1597) and the part-wise sums of Ctxt::addCtxt (src/Ctxt.cpp:1538-1553), in one pass:
+ *   o0 = sum_t a0[t] b0[t],   o1 = sum_t (a0[t] b1[t] + a1[t] b0[t]),   o2 = sum_t a1[t] b1[t],   t < n,
+ * row by row modulo each prime.  (a0[t], a1[t]) and (b0[t], b1[t]) are the parts pointing at 1 and at s of the two
+ * operands of pair t; o0, o1, o2 receive the parts pointing at 1, s and s^2.  All 4 n operands and the three outputs
+ * share one batch and one prime set (same order), in evaluation form, words canonical in [0, q); every word written is
+ * canonical and equal to what n x hx_tensor followed by hx_add of the products part by part leave (an exact sum of
+ * products modulo q does not depend on the order of its terms).  Operands may repeat: a[t] and b[t] may be one poly (a
+ * square) and a poly may appear in several terms.  The outputs are overwritten, not read; one that still shares its
+ * rows with a lazy hx_poly_copy lets go of them first.  Null arguments, n < 1, two outputs that are one poly, an
+ * output that is also an input, a poly of another context, a batch or prime set that differs from o0's and rows that
+ * are not 16-byte aligned are HX_ERR_INVALID; an odd phi(m) is HX_ERR_UNSUPPORTED; a refused call touches no output.
+ * Any n: the 128-bit accumulators are reduced every 128 terms (256 products in o1).  The call uploads a table of
+ * operand pointers through the staging ring of hx_mul_add_many, so it cannot be recorded: under an open graph capture
+ * it returns HX_ERR_UNSUPPORTED before touching the device.  Asynchronous on the context's stream.  In passes over a
+ * row, the n tensors and 3 (n - 1) additions read and write 7 n + 9 (n - 1); this call reads 4 n and writes 3. */
+int hx_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_poly* const* a0, const hx_poly* const* a1,
+                  const hx_poly* const* b0, const hx_poly* const* b1, int n);
 /* The hoisted sum of traceMap (src/matmul.cpp:2878-2887 over BasicAutomorphPrecon, :48-184:
  *   BasicAutomorphPrecon precon(ctxt);  acc = ctxt;  for each t  acc += *precon.automorph(k[t]);)
  * in one pass: the ciphertext plus its images under the n automorphisms k[t], each key-switched by its own matrix W[t]
