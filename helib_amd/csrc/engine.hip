@@ -3355,16 +3355,25 @@ extern "C" int hx_embedding_norm(hx_ctx* c, const double* f_host, int rows, doub
 // ------------------------------------------------------------------
 // addPrimesAndScale / addPrimes / scaleDownToSet
 // ------------------------------------------------------------------
+// prod(the n listed primes) mod q: the mod-up factor F of addPrimesAndScale, the P of a mod-down
+static uint64_t prod_mod(const hx_ctx* c, const int* primes, int n, uint64_t q)
+{
+  uint64_t v = 1;
+  for (int i = 0; i < n; i++)
+    v = hxh::mulmod(v, c->primes[primes[i]].q % q, q);
+  return v;
+}
+static uint64_t prod_mod(const hx_ctx* c, const std::vector<int>& primes, uint64_t q)
+{
+  return prod_mod(c, primes.data(), (int)primes.size(), q);
+}
+
 static int scale_rows_by_primes(hx_poly* a, const int* add_idx, int nadd)
 {
   hx_ctx* c = a->ctx;
   std::vector<uint64_t> f(a->nrows());
-  for (int r = 0; r < a->nrows(); r++) {
-    uint64_t q = c->primes[a->prime_idx[r]].q, v = 1;
-    for (int i = 0; i < nadd; i++)
-      v = hxh::mulmod(v, c->primes[add_idx[i]].q % q, q);
-    f[r] = v;
-  }
+  for (int r = 0; r < a->nrows(); r++)
+    f[r] = prod_mod(c, add_idx, nadd, c->primes[a->prime_idx[r]].q);
   return ew_scalar_rows<hx::EWS_MUL>(a, f.data());
 }
 
@@ -3495,16 +3504,310 @@ extern "C" int hx_poly_rem(const hx_poly* a, uint64_t t, uint64_t* out_host)
   return HX_OK;
 }
 
-// others[0..nother): further polys with exactly a's prime rows and batch, mod-switched by the
-// same launches when the fused single-prime path applies (returns HX_ERR_UNSUPPORTED otherwise
-// when nother > 0, so that the caller can fall back to one call per poly).
-// scaleDownToSet / bringToSet dropping SEVERAL primes, for all listed polys (one prime set, one
-// batch) in one set of launches -- what every multiply after the first goes through (the special
-// primes of the previous key switch, the small primes on the way out of a product).  Round 1 did this
-// per polynomial and unfused (inverse transforms, basis extension writing delta, forward transforms,
-// then a separate (c - delta)/P pass; the mod-up as a scaling pass of its own before).  Now:
-//   1. per dropped prime, ONE launch of the mod-down prep kernel over all polys: inverse transform
-//      of that row into the x block, the mod-up factor F = prod(added primes) riding on the last
+// ------------------------------------------------------------------
+// The mod-switch host path (scaleDownToSet, bringToSet, tensorProduct + bringToSet): one resolved request
+// (ModSwitch), three paths (modswitch_fused1, modswitch_fusedN, modswitch_generic), one dispatcher (scale_down_impl)
+// ------------------------------------------------------------------
+// A per-row table of device constants cached in c->plans under `key`: found there, or built on the host by
+// fill(host) (`bytes` zeroed bytes; an error it returns is passed on and nothing is cached), uploaded and inserted.
+// *out: the device table, which lives as long as the context.
+template <class Fill>
+static int plan_table(hx_ctx* c, const std::vector<uint64_t>& key, size_t bytes, Fill fill, const void** out)
+{
+  auto it = c->plans.find(key);
+  if (it == c->plans.end()) {
+    std::vector<uint64_t> host((bytes + 7) / 8, 0);
+    CHK(fill((void*)host.data()));
+    struct Blob {  // an error return below gives the device table back
+      void* p = nullptr;
+      ~Blob()
+      {
+        if (p)
+          hipFree(p);
+      }
+    } blob;
+    HIPCHK(hipMalloc(&blob.p, bytes));
+    HIPCHK(hipMemcpy(blob.p, host.data(), bytes, hipMemcpyHostToDevice));
+    ExtPlan* pl = new ExtPlan();
+    memset(&pl->dev, 0, sizeof pl->dev);
+    std::swap(pl->blob, blob.p);
+    it = c->plans.emplace(key, pl).first;
+  }
+  *out = it->second->blob;
+  return HX_OK;
+}
+
+// One mod-switch request, resolved once from the raw arguments (modswitch_resolve); the paths read it and nothing else.
+struct ModSwitch {
+  hx_ctx* c = nullptr;
+  hx_poly* ps[hx::MD_MAXPOLY];  // the polys (a and others flattened): one context, one batch, one list of prime rows
+  int np = 0;
+  int batch = 0;
+  size_t rw = 0;  // words of one row
+  // drop: the listed primes that are rows of the polys (diff = getIndexSet() / s: only primes actually present are
+  // dropped); keep: their other rows; both in row order.  add: the primes of a mod-up folded in (fused bringToSet: the
+  // polys are first mod-switched UP by these primes, addPrimesAndScale) -- disjoint from the rows and from the drop
+  // list, and the tail of keep.  No poly's prime_idx changes before a path has succeeded.
+  std::vector<int> drop, keep, add;
+  uint64_t ptxt = 1;
+  // tensorProduct folded in: the polys are the three product parts, storage reserved, prime list = the operands',
+  // contents not yet computed -- their rows are formed from the operands' rows inside the transforms and the results
+  // go into the parts' own slabs
+  const hx::TensorSrc* tsrc = nullptr;
+  bool small_S = false;  // |S| <= ptxtSpace/2 + 1 is a reduced residue of every kept prime (the fused kernels take it so)
+  bool ring = false;     // a ring the fused kernels are built for
+  int nd() const { return (int)drop.size(); }
+  int nk() const { return (int)keep.size(); }
+  int nadd() const { return (int)add.size(); }
+};
+
+// All validation and the drop / keep partition, once.  HX_ERR_UNSUPPORTED: a mod-up that cannot be folded in (the
+// caller does addPrimesAndScale and the mod-down as two steps).
+static int modswitch_resolve(ModSwitch& m, hx_poly* a, hx_poly** others, int nother, const int* drop_idx, int ndrop,
+                             uint64_t ptxt, const int* add_idx, int nadd, const hx::TensorSrc* tsrc)
+{
+  hx_ctx* c = a->ctx;
+  if (ptxt < 1)
+    return fail(HX_ERR_INVALID, "ptxtSpace must be at least 1");
+  if (1 + nother > hx::MD_MAXPOLY)
+    return HX_ERR_UNSUPPORTED;
+  m.c = c;
+  m.ps[0] = a;
+  for (int i = 0; i < nother; i++)
+    m.ps[1 + i] = others[i];
+  m.np = 1 + nother;
+  m.batch = a->batch;
+  m.rw = a->row_words();
+  m.ptxt = ptxt;
+  m.tsrc = tsrc;
+  auto listed = [&](int pr) { return std::find(drop_idx, drop_idx + ndrop, pr) != drop_idx + ndrop; };
+  for (int pr : a->prime_idx)
+    (listed(pr) ? m.drop : m.keep).push_back(pr);
+  for (int i = 0; i < nadd; i++) {
+    if (find_row(a->prime_idx, add_idx[i]) >= 0 || listed(add_idx[i]))
+      return HX_ERR_UNSUPPORTED;
+    m.keep.push_back(add_idx[i]);
+    m.add.push_back(add_idx[i]);
+  }
+  m.small_S = true;
+  for (int pr : m.keep)
+    m.small_S = m.small_S && ptxt / 2 + 2 < c->primes[pr].q;
+  m.ring = c->pow2 && c->logn >= 13 && c->logn <= 15;
+  return HX_OK;
+}
+
+// The output slabs of one mod-switch, slot i for poly i of the request: taken from the pool, all given back by the
+// destructor unless committed.  The ordering rule of every path: ALL output slabs are taken BEFORE any shared input
+// slab is released (commit) -- two listed polys may share one slab, and a slab returned to the pool could come
+// straight back as somebody's output.
+struct FreshSlabs {
+  const ModSwitch& m;
+  const int ncap;  // rows every slab holds
+  const size_t bytes;
+  uint64_t* d[hx::MD_MAXPOLY] = {nullptr};
+  FreshSlabs(const ModSwitch& m_, int ncap_) : m(m_), ncap(ncap_), bytes((size_t)ncap_ * m_.rw * 8) {}
+  FreshSlabs(const FreshSlabs&) = delete;
+  ~FreshSlabs()
+  {
+    for (int i = 0; i < m.np; i++)
+      if (d[i])
+        pool_free(m.c, d[i], bytes);
+  }
+  int take(int i)
+  {
+    hipError_t pe = pool_alloc(m.c, bytes, (void**)&d[i]);
+    if (pe != hipSuccess)
+      return fail(HX_ERR_NOMEM, "hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(pe));
+    return HX_OK;
+  }
+  // slab i (if taken) becomes poly i's storage; the slab the poly held stays with its other holders (lazy copies) or
+  // goes back to the pool, whose reuse is ordered behind the kernels already enqueued
+  void commit(int i)
+  {
+    if (!d[i])
+      return;
+    storage_release(m.ps[i]);
+    m.ps[i]->d = d[i];
+    m.ps[i]->cap_rows = ncap;
+    d[i] = nullptr;
+  }
+};
+
+// ---- the fused single-prime path: [inverse NTT of the dropped row + delta preparation] then [forward NTT of delta on
+// every kept row, with  c <- (c - delta) / qd  in its store], for all listed polys in one pair of launches.  The last
+// row takes the dropped row's slot, so no compaction copy is needed.
+// Storage: in place, except for polys that share their slab with a copy (hx_poly_copy is lazy) -- those read the
+// shared slab and write a fresh one, which is what makes `Ctxt tmp = other; tmp.bringToSet(s)` cost no copy at all.
+// A folded mod-up grows the unshared polys for the added rows first (harmless if the path then fails).
+static bool modswitch_fused1_applies(const ModSwitch& m)
+{
+  return m.nd() == 1 && m.ring && m.nk() <= MAX_ROWS && m.ptxt < ((uint64_t)1 << 62) && m.small_S;
+}
+
+// rows: the polys' prime rows followed by the added ones, drow: the dropped row.  kr and *table (cached per (dropped
+// prime, added primes, kept rows and their output slots)): the per-row constants of the apply launch.
+static int modswitch_fused1_rows(const ModSwitch& m, const std::vector<int>& rows, int drow, NttRows& kr,
+                                 const hx::ModDownRow** table)
+{
+  hx_ctx* c = m.c;
+  const int last = (int)rows.size() - 1;
+  const uint64_t qd = c->primes[rows[drow]].q;
+  std::vector<uint64_t> key;
+  key.push_back(0xD0D0D0D0ull);
+  key.push_back((uint64_t)rows[drow]);
+  for (int pr : m.add)
+    key.push_back(0xA000000ull | (uint64_t)pr);
+  std::vector<hx::ModDownRow> hr(m.nk());
+  int i = 0;
+  for (int r = 0; r <= last; r++) {
+    if (r == drow)
+      continue;
+    const int pr = rows[r];
+    const uint64_t q = c->primes[pr].q;
+    kr.row[i] = (uint16_t)r;
+    kr.prime[i] = (uint16_t)pr;
+    uint64_t qdm = qd % q, inv = hxh::invmod(qdm, q);
+    hr[i].qdm.w = qdm;
+    hr[i].qdm.wp = hxh::shoup(qdm, q);
+    hr[i].inv.w = inv;
+    hr[i].inv.wp = tw_companion(c->primes[pr], inv);
+    hr[i].out_row = (uint32_t)((r == last && drow != last) ? drow : r);
+    hr[i].mode = 0;
+    hr[i].cf = hr[i].inv;
+    hr[i].cf_r2 = tw_r2(c->primes[pr], inv);
+    if (find_row(m.add, pr) >= 0) {
+      hr[i].mode = 2;  // a row the mod-up adds: c_r = 0, i.e. cf = 0 (its slot is never initialised)
+      hr[i].cf.w = hr[i].cf.wp = 0;
+      hr[i].cf_r2 = 0;
+    } else if (m.nadd() > 0) {
+      uint64_t cf = hxh::mulmod(prod_mod(c, m.add, q), inv, q);
+      hr[i].mode = 1;
+      hr[i].cf.w = cf;
+      hr[i].cf.wp = tw_companion(c->primes[pr], cf);
+      hr[i].cf_r2 = tw_r2(c->primes[pr], cf);
+    }
+    key.push_back(((uint64_t)pr << 28) | ((uint64_t)hr[i].out_row << 12) | hr[i].mode);
+    i++;
+  }
+  const size_t bytes = sizeof(hx::ModDownRow) * hr.size();
+  return plan_table(c, key, bytes, [&](void* host) { return memcpy(host, hr.data(), bytes), HX_OK; },
+                    reinterpret_cast<const void**>(table));
+}
+
+static int modswitch_fused1(const ModSwitch& m)
+{
+  hx_ctx* c = m.c;
+  const size_t rw = m.rw;
+  const int np = m.np, nk = m.nk();
+  std::vector<int> rows = m.ps[0]->prime_idx;
+  rows.insert(rows.end(), m.add.begin(), m.add.end());
+  const int dprime = m.drop[0], drow = find_row(rows, dprime), last = (int)rows.size() - 1;
+  const uint64_t qd = c->primes[dprime].q;
+  for (int i = 0; i < np && m.nadd() > 0; i++)
+    if (!m.ps[i]->shared())
+      CHK(poly_reserve(m.ps[i], (int)rows.size()));
+  for (int i = 0; i < np; i++)
+    if (m.ps[i]->share && !m.ps[i]->shared())
+      CHK(poly_own(m.ps[i]));  // last holder of its slab: plain in-place
+  PolyBases pb, pbo;
+  memset(&pb, 0, sizeof pb);
+  memset(&pbo, 0, sizeof pbo);
+  pb.n = pbo.n = np;
+  FreshSlabs fresh(m, (int)rows.size() + 2);
+  for (int i = 0; i < np; i++) {
+    pb.d[i] = pbo.d[i] = m.ps[i]->d;
+    if (m.ps[i]->shared()) {
+      CHK(fresh.take(i));
+      pbo.d[i] = fresh.d[i];
+    }
+  }
+  CHK(ensure_scratch(c, 0, rw * np));
+  CHK(ensure_scratch(c, 1, rw * np));
+  hx::ModDownPrep P;
+  memset(&P, 0, sizeof P);
+  P.xs = c->scratch[0];
+  P.S = reinterpret_cast<int64_t*>(c->scratch[1]);
+  P.half = (qd - 1) / 2;
+  if (m.ptxt > 1) {
+    const uint64_t ptxt = m.ptxt;
+    P.ptxt = ptxt;
+    P.ptxt_mu64 = (uint64_t)((((hxh::u128)1) << 64) / ptxt);
+    int kb = hxh::bitlen(ptxt);
+    P.ptxt_k = (uint32_t)kb;
+    P.ptxt_mu = (uint64_t)((((hxh::u128)1) << (2 * kb)) / ptxt);
+    P.qd_mod_p = qd % ptxt;
+    P.qdinv_mod_p = hxh::invmod(qd % ptxt, ptxt);
+    if (P.qdinv_mod_p == 0)
+      return fail(HX_ERR_INVALID, "dropped primes are not invertible modulo ptxtSpace");
+  }
+  P.qd = qd;
+  // Who forms S, and the norm (dev_common.h: ModDownPrep::fuse).  whole_batch: the whole norm batch comes from this
+  // call -- then the norm kernel reads (x, S) in place instead of an fdelta written out, or, when also the ring is the
+  // radix-16 one and the read-back is a plain store into the pinned slot on this stream, the norm rides in the prep
+  // workgroups.  (Taken before the launch; frac_take below moves frac_pos and nothing else in between.)
+  P.fuse = c->sw.no_prep_fuse ? 0u : 1u;
+  const size_t nfrac = rw * (size_t)np;
+  const bool whole_batch = c->want_frac && c->xs_rows == 0 && c->frac_pos == 0 && nfrac <= c->frac_cap && !c->want_fdelta;
+  // (ptxt < 2^32: the norm-carrying kernels keep no scalar registers for the wide correction's constants)
+  const bool norm_in_prep = P.fuse && whole_batch && c->logn == 14 && !c->capturing && (m.ptxt >> 32) == 0;
+  if (norm_in_prep) {
+    prep_norm_drop(c);   // (a slot an earlier call took and then failed before it had an (x, S) block to go with it)
+    CHK(norm_wtab(c));
+    CHK(norm_slot_take(c, np * m.batch, &c->prep_np));
+    c->prep_norm = true;   // (given back by flush_xs / frac_begin unless embed_norms() queues it)
+    P.fuse = 2;
+    P.inv_qd = 1.0 / (double)qd;
+    P.wtab = reinterpret_cast<const double*>(c->d_wtab);
+    P.norm_out = c->prep_np.pinned;
+  }
+  if (m.nadd() > 0) {
+    const uint64_t F = prod_mod(c, m.add, qd);
+    P.has_up = 1;
+    P.upS.w = hxh::mulmod(F, c->primes[dprime].last_s, qd);
+    P.upS.wp = tw_companion(c->primes[dprime], P.upS.w);
+    P.upN.w = hxh::mulmod(F, c->primes[dprime].last_n, qd);
+    P.upN.wp = tw_companion(c->primes[dprime], P.upN.w);
+  }
+  NttRows kr;
+  hx::ModDownApply A;
+  A.xs = c->scratch[0];
+  A.S = reinterpret_cast<const int64_t*>(c->scratch[1]);
+  CHK(modswitch_fused1_rows(m, rows, drow, kr, &A.rows));
+  hipError_t e = m.tsrc ? hx::launch_moddown_tensor_pow2(c->logn, *m.tsrc, pbo, drow, dprime, kr, nk, m.batch, P, A,
+                                                         c->d_primes, c->d_tw, c->stream)
+                        : hx::launch_moddown_pow2(c->logn, pb, pbo, drow, dprime, kr, nk, m.batch, P, A, c->d_primes,
+                                                  c->d_tw, c->stream);
+  if (e != hipSuccess) {
+    prep_norm_drop(c);
+    return fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
+  }
+  for (int i = 0; i < np; i++)
+    fresh.commit(i);
+  if (c->want_frac) {
+    double* fr = frac_take(c, nfrac);
+    if (!fr)
+      return fail(HX_ERR_INVALID, "internal: fraction buffer too small");
+    if (whole_batch) {  // the norm kernel reads (x, S) itself -- or the prep kernels have already formed the norms
+      c->xs_first = 0;
+      c->xs_rows = np * m.batch;
+      c->xs_inv_qd = 1.0 / (double)qd;
+    } else {
+      HX_LAUNCH(hx::frac_from_xs_kernel, dim3((unsigned)std::min<size_t>((nfrac + 255) / 256, 4096)), dim3(256), 0,
+                c->stream, c->scratch[0], reinterpret_cast<const int64_t*>(c->scratch[1]), 1.0 / (double)qd, fr, nfrac);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  rows[drow] = rows[last];
+  rows.pop_back();
+  for (int i = 0; i < np; i++)
+    m.ps[i]->prime_idx = rows;
+  return HX_OK;
+}
+
+// ---- the several-primes path, for all listed polys in one set of launches -- what every multiply after the first
+// goes through (the special primes of the previous key switch, the small primes on the way out of a product):
+//   1. per group of MD_MAXDROP dropped primes, ONE launch of the mod-down prep kernel over all polys: inverse
+//      transform of those rows into the x block, the mod-up factor F = prod(added primes) riding on the last
 //      stage's N^-1 twiddles (no scaled copy of the operand is ever made);
 //   2. per poly, the basis-extension kernel on a plan whose tables carry P^-1 (get_plan scaled):
 //      Garner + centring + ptxtSpace correction, out comes delta/P on every kept prime
@@ -3513,112 +3816,89 @@ extern "C" int hx_poly_rem(const hx_poly* a, uint64_t t, uint64_t* out_host)
 //   3. ONE launch of the apply kernel with a plain load over all polys: forward transform of
 //      delta/P with the store  c_r <- c_r*(F/P) - NTT(.)  into a fresh, compact slab per poly --
 //      out of place by construction, so lazily copied operands (hx_poly::Share) are never copied.
-// Returns HX_ERR_UNSUPPORTED (nothing touched) when the shape is not covered; the callers then
-// take the per-polynomial path.
-// tsrc (tensorProduct folded in): the polys are the three product parts with reserved storage and the operands'
-// prime list; their rows are formed from the operands' rows inside the transforms and the results go into the
-// parts' own slabs.
-static int scale_down_multi_fused(hx_poly** ps, int np, const std::vector<int>& drop_in,
-                                  const std::vector<int>& keep, uint64_t ptxt, const int* add_idx, int nadd,
-                                  const hx::TensorSrc* tsrc = nullptr)
+// Storage: a fresh slab per poly (so caller-owned storage, which wants its result in place, is not covered); with the
+// tensor product folded in nothing of a part exists yet and its own slab takes the result.
+static bool modswitch_fusedN_applies(const ModSwitch& m)
 {
-  hx_poly* a = ps[0];
-  hx_ctx* c = a->ctx;
-  const int nd = (int)drop_in.size(), nk = (int)keep.size();
-  if (!c->pow2 || c->logn < 13 || c->logn > 15 || nd < 2 || nd > 64 || nk > MAX_ROWS || np > hx::MD_MAXPOLY)
-    return HX_ERR_UNSUPPORTED;
-  for (int i = 0; i < np; i++)
-    if (!ps[i]->owns)
-      return HX_ERR_UNSUPPORTED;  // caller-owned storage wants its result in place
-  if (tsrc && np != 3)
-    return HX_ERR_UNSUPPORTED;
-  const size_t rw = a->row_words();
-  const int batch = a->batch;
-  std::vector<int> drop = drop_in;
-  std::sort(drop.begin(), drop.end(), [&](int x, int y) { return c->primes[x].q < c->primes[y].q; });
-  // kept row t: prime keep[t]; its c_r lives in row in_row[t] of the input slab (-1: a row the
-  // fused mod-up adds, c_r = 0)
-  std::vector<int> in_row(nk);
-  for (int t = 0; t < nk; t++)
-    in_row[t] = find_row(a->prime_idx, keep[t]);  // (the added primes are not among the poly's rows)
-  ExtPlan* pl;
-  CHK(get_plan(c, drop, keep, ptxt > 1 ? ptxt : 0, &pl, nullptr, /*scaled=*/true));
-  CHK(ensure_scratch(c, 0, (size_t)np * nd * rw));  // x blocks  [poly][dropped prime][batch][N]
-  CHK(ensure_scratch(c, 1, (size_t)np * nk * rw));  // delta / P [poly][kept row][batch][N]
-  // per-row constants of the apply launch, cached per (dropped set, kept rows, added primes)
+  const int nd = m.nd(), nk = m.nk();
+  if (!m.ring || nd < 2 || nd > 64 || nk > MAX_ROWS || nk == m.nadd() || (m.tsrc && m.np != 3))
+    return false;
+  for (int i = 0; i < m.np; i++)
+    if (!m.ps[i]->owns || (m.tsrc && m.ps[i]->cap_rows < nk))
+      return false;
+  return true;
+}
+
+// kept row t is prime keep[t]; its c_r lives in row kr.row[t] of the input slab, or nowhere (a row the mod-up adds:
+// c_r = 0).  kr and *table (cached per (dropped set, added primes, kept rows)): the per-row constants of the apply
+// launch.
+static int modswitch_fusedN_rows(const ModSwitch& m, const std::vector<int>& drop, NttRows& kr,
+                                 const hx::ModDownRow** table)
+{
+  hx_ctx* c = m.c;
   std::vector<uint64_t> key;
   key.push_back(0xD1D1D1D1ull);
   for (int d : drop)
     key.push_back((uint64_t)d);
   key.push_back(0xFFFFull << 32);
-  for (int j = 0; j < nadd; j++)
-    key.push_back(0xA000000ull | (uint64_t)add_idx[j]);
-  NttRows kr;
-  std::vector<hx::ModDownRow> hr(nk);
-  for (int t = 0; t < nk; t++) {
-    const int pr = keep[t];
+  for (int pr : m.add)
+    key.push_back(0xA000000ull | (uint64_t)pr);
+  std::vector<hx::ModDownRow> hr(m.nk());
+  for (int t = 0; t < m.nk(); t++) {
+    const int pr = m.keep[t], in_row = find_row(m.ps[0]->prime_idx, pr);
     const uint64_t q = c->primes[pr].q;
-    kr.row[t] = (uint16_t)(in_row[t] < 0 ? 0 : in_row[t]);
+    kr.row[t] = (uint16_t)(in_row < 0 ? 0 : in_row);
     kr.prime[t] = (uint16_t)pr;
-    uint64_t P = 1;
-    for (int d : drop)
-      P = hxh::mulmod(P, c->primes[d].q % q, q);
-    uint64_t cf = hxh::invmod(P, q);
+    uint64_t cf = hxh::invmod(prod_mod(c, drop, q), q);
     if (cf == 0)
       return fail(HX_ERR_INVALID, "dropped primes are not invertible modulo a kept prime");
-    memset(&hr[t], 0, sizeof hr[t]);
     hr[t].out_row = (uint32_t)t;
-    if (in_row[t] < 0) {
+    if (in_row < 0) {
       hr[t].mode = 2;  // c_r = 0: cf stays 0
     } else {
-      for (int j = 0; j < nadd; j++)
-        cf = hxh::mulmod(cf, c->primes[add_idx[j]].q % q, q);
-      hr[t].mode = nadd > 0 ? 1 : 0;
+      cf = hxh::mulmod(cf, prod_mod(c, m.add, q), q);
+      hr[t].mode = m.nadd() > 0 ? 1 : 0;
       hr[t].cf.w = cf;
       hr[t].cf.wp = tw_companion(c->primes[pr], cf);
       hr[t].cf_r2 = tw_r2(c->primes[pr], cf);
     }
     key.push_back(((uint64_t)pr << 28) | ((uint64_t)kr.row[t] << 12) | hr[t].mode);
   }
-  auto it = c->plans.find(key);
-  if (it == c->plans.end()) {
-    ExtPlan* rp = new ExtPlan();
-    memset(&rp->dev, 0, sizeof rp->dev);
-    HIPCHK(hipMalloc(&rp->blob, sizeof(hx::ModDownRow) * nk));
-    HIPCHK(hipMemcpy(rp->blob, hr.data(), sizeof(hx::ModDownRow) * nk, hipMemcpyHostToDevice));
-    it = c->plans.emplace(key, rp).first;
-  }
-  // output slabs first (see the single-prime path: nothing is released before everything is taken)
-  const int ncap = nk + 2;
-  const size_t nbytes = (size_t)ncap * rw * 8;
-  uint64_t* fresh[hx::MD_MAXPOLY] = {nullptr};
-  auto drop_fresh = [&]() {
-    for (int i = 0; i < np; i++)
-      if (fresh[i])
-        pool_free(c, fresh[i], nbytes);
-  };
+  const size_t bytes = sizeof(hx::ModDownRow) * hr.size();
+  return plan_table(c, key, bytes, [&](void* host) { return memcpy(host, hr.data(), bytes), HX_OK; },
+                    reinterpret_cast<const void**>(table));
+}
+
+static int modswitch_fusedN(const ModSwitch& m)
+{
+  hx_ctx* c = m.c;
+  hx_poly* a = m.ps[0];
+  const int np = m.np, nd = m.nd(), nk = m.nk(), batch = m.batch;
+  const size_t rw = m.rw;
+  std::vector<int> drop = m.drop;
+  std::sort(drop.begin(), drop.end(), [&](int x, int y) { return c->primes[x].q < c->primes[y].q; });
+  ExtPlan* pl;
+  CHK(get_plan(c, drop, m.keep, m.ptxt > 1 ? m.ptxt : 0, &pl, nullptr, /*scaled=*/true));
+  CHK(ensure_scratch(c, 0, (size_t)np * nd * rw));  // x blocks  [poly][dropped prime][batch][N]
+  CHK(ensure_scratch(c, 1, (size_t)np * nk * rw));  // delta / P [poly][kept row][batch][N]
+  NttRows kr;
+  ModDownApply A;
+  memset(&A, 0, sizeof A);
+  CHK(modswitch_fusedN_rows(m, drop, kr, &A.rows));
+  FreshSlabs fresh(m, nk + 2);
   PolyBases pb, pbo;
   memset(&pb, 0, sizeof pb);
   memset(&pbo, 0, sizeof pbo);
   pb.n = pbo.n = np;
   for (int i = 0; i < np; i++) {
-    if (tsrc) {  // nothing of the part exists yet: its own slab takes the result
-      if (ps[i]->cap_rows < nk)
-        return HX_ERR_UNSUPPORTED;
-      pb.d[i] = pbo.d[i] = ps[i]->d;
-      continue;
+    pb.d[i] = pbo.d[i] = m.ps[i]->d;
+    if (!m.tsrc) {
+      CHK(fresh.take(i));
+      pbo.d[i] = fresh.d[i];
     }
-    hipError_t pe = pool_alloc(c, nbytes, (void**)&fresh[i]);
-    if (pe != hipSuccess) {
-      drop_fresh();
-      return fail(HX_ERR_NOMEM, "hipMalloc(%zu) failed: %s", nbytes, hipGetErrorString(pe));
-    }
-    pb.d[i] = ps[i]->d;
-    pbo.d[i] = fresh[i];
   }
-  int rc = HX_OK;
   // 1. inverse transforms of the dropped rows: all polys and up to MD_MAXDROP dropped primes per launch
-  for (int j0 = 0; j0 < nd && rc == HX_OK; j0 += hx::MD_MAXDROP) {
+  for (int j0 = 0; j0 < nd; j0 += hx::MD_MAXDROP) {
     const int nj = std::min(hx::MD_MAXDROP, nd - j0);
     hx::PrepMulti M;
     memset(&M, 0, sizeof M);
@@ -3626,30 +3906,27 @@ static int scale_down_multi_fused(hx_poly** ps, int np, const std::vector<int>& 
     memset(&P, 0, sizeof P);
     P.xs = c->scratch[0] + (size_t)j0 * rw;
     P.poly_stride = (uint64_t)nd * rw;
-    P.has_up = nadd > 0 ? 1 : 0;
+    P.has_up = m.nadd() > 0 ? 1 : 0;
     for (int j = 0; j < nj; j++) {
-      const int dprime = drop[j0 + j];
-      const uint64_t qd = c->primes[dprime].q;
-      M.row[j] = (uint16_t)find_row(a->prime_idx, dprime);
-      M.prime[j] = (uint16_t)dprime;
-      if (nadd > 0) {
-        uint64_t F = 1;
-        for (int i = 0; i < nadd; i++)
-          F = hxh::mulmod(F, c->primes[add_idx[i]].q % qd, qd);
-        M.up[2 * j].w = hxh::mulmod(F, c->primes[dprime].last_s, qd);
-        M.up[2 * j].wp = tw_companion(c->primes[dprime], M.up[2 * j].w);
-        M.up[2 * j + 1].w = hxh::mulmod(F, c->primes[dprime].last_n, qd);
-        M.up[2 * j + 1].wp = tw_companion(c->primes[dprime], M.up[2 * j + 1].w);
+      const PrimeHost& ph = c->primes[drop[j0 + j]];
+      M.row[j] = (uint16_t)find_row(a->prime_idx, drop[j0 + j]);
+      M.prime[j] = (uint16_t)drop[j0 + j];
+      if (m.nadd() > 0) {
+        const uint64_t F = prod_mod(c, m.add, ph.q);
+        M.up[2 * j].w = hxh::mulmod(F, ph.last_s, ph.q);
+        M.up[2 * j].wp = tw_companion(ph, M.up[2 * j].w);
+        M.up[2 * j + 1].w = hxh::mulmod(F, ph.last_n, ph.q);
+        M.up[2 * j + 1].wp = tw_companion(ph, M.up[2 * j + 1].w);
       }
     }
-    hipError_t e = tsrc ? hx::launch_moddown_prep_multi_tensor_pow2(c->logn, *tsrc, M, nj, batch, P, c->d_primes, c->d_tw,
-                                                                    c->stream)
-                        : hx::launch_moddown_prep_multi_pow2(c->logn, pb, M, nj, batch, P, c->d_primes, c->d_tw, c->stream);
+    hipError_t e = m.tsrc ? hx::launch_moddown_prep_multi_tensor_pow2(c->logn, *m.tsrc, M, nj, batch, P, c->d_primes,
+                                                                      c->d_tw, c->stream)
+                          : hx::launch_moddown_prep_multi_pow2(c->logn, pb, M, nj, batch, P, c->d_primes, c->d_tw, c->stream);
     if (e != hipSuccess)
-      rc = fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
+      return fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
   }
   // 2. delta / P on the kept primes, per poly
-  for (int i = 0; i < np && rc == HX_OK; i++) {
+  for (int i = 0; i < np; i++) {
     ExtArgs args;
     clear_args(args);
     args.src = c->scratch[0] + (size_t)i * nd * rw;
@@ -3664,385 +3941,49 @@ static int scale_down_multi_fused(hx_poly** ps, int np, const std::vector<int>& 
     if (c->want_frac) {
       args.frac = frac_take(c, rw);
       if (!args.frac)
-        rc = fail(HX_ERR_INVALID, "internal: fraction buffer too small");
+        return fail(HX_ERR_INVALID, "internal: fraction buffer too small");
     }
-    if (rc == HX_OK)
-      rc = launch_extend(c, pl, args, rw);
+    CHK(launch_extend(c, pl, args, rw));
   }
   // 3. forward transforms with the subtraction and the division in the store
-  if (rc == HX_OK) {
-    ModDownApply A;
-    memset(&A, 0, sizeof A);
-    A.rows = reinterpret_cast<const hx::ModDownRow*>(it->second->blob);
-    A.delta = c->scratch[1];
-    A.delta_poly_stride = (uint64_t)nk * rw;
-    hipError_t e = tsrc ? hx::launch_moddown_apply_plain_tensor_pow2(c->logn, *tsrc, pbo, kr, nk, batch, A, c->d_primes,
+  A.delta = c->scratch[1];
+  A.delta_poly_stride = (uint64_t)nk * rw;
+  hipError_t e = m.tsrc ? hx::launch_moddown_apply_plain_tensor_pow2(c->logn, *m.tsrc, pbo, kr, nk, batch, A, c->d_primes,
                                                                      c->d_tw, c->stream)
                         : hx::launch_moddown_apply_plain_pow2(c->logn, pb, pbo, kr, nk, batch, A, c->d_primes, c->d_tw,
                                                               c->stream);
-    if (e != hipSuccess)
-      rc = fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
-  }
-  if (rc != HX_OK) {
-    drop_fresh();
-    return rc;
-  }
+  if (e != hipSuccess)
+    return fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
   for (int i = 0; i < np; i++) {
-    if (!tsrc) {
-      storage_release(ps[i]);  // (a slab shared with a lazy copy stays with its other holders)
-      ps[i]->d = fresh[i];
-      ps[i]->cap_rows = ncap;
-    }
-    ps[i]->prime_idx = keep;
+    fresh.commit(i);
+    m.ps[i]->prime_idx = m.keep;
   }
   return HX_OK;
 }
 
-static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* drop_idx, int ndrop,
-                           uint64_t ptxt, const int* add_idx = nullptr, int nadd = 0,
-                           const hx::TensorSrc* tsrc = nullptr)
+// ---- the generic path, one poly, any ring, any storage: inverse transforms of the dropped rows, the basis
+// extension writing delta on the kept primes, forward transforms, then (c - delta) / P as a pass of its own.
+// Storage: delta goes into a fresh compact slab that then becomes the polynomial's storage,
+// new[w] = (old[row of keep[w]] - delta[w]) / diffProd, so neither removePrimes' compaction nor a second buffer is
+// needed; caller-owned storage gets the compact result copied back into it.
+static int modswitch_generic(const ModSwitch& m)
 {
-  // tsrc (tensorProduct folded in): a / others are the three product parts, storage reserved, prime list =
-  // the operands', contents not yet computed -- only the fused single-prime path can take them
-  // add_idx (fused bringToSet): the polys are first mod-switched UP by these primes
-  // (addPrimesAndScale); only the fused single-prime path folds that in, otherwise the caller
-  // gets HX_ERR_UNSUPPORTED and does the two steps separately.
-
-  if (!a)
-    return fail(HX_ERR_INVALID, "null poly");
-  hx_ctx* c = a->ctx;
-  CTX_ENTER(c);
-  if (c->want_frac)
-    CHK(flush_xs(c));  // the scratch slots of an earlier fused block are about to be reused
-  if (ptxt < 1)
-    return fail(HX_ERR_INVALID, "ptxtSpace must be at least 1");
-  // the fused bringToSet appends the mod-up's primes to the row list before its fallible steps (slab
-  // and scratch allocation, the invertibility check): an error return takes them off again, so the
-  // poly never advertises rows that were not written
-  struct PrimeRollback {
-    hx_poly* a;
-    int n = 0;
-    ~PrimeRollback()
-    {
-      if (n > 0)
-        a->prime_idx.resize(a->prime_idx.size() - (size_t)n);
-    }
-  } rollback{a};
-  if (nadd > 0 && ndrop != 1) {
-    // several dropped primes behind a mod-up: the batched path or nothing (the caller then does
-    // addPrimesAndScale and the mod-down as two steps)
-    std::vector<int> drop, keep;
-    for (int r = 0; r < a->nrows(); r++) {
-      bool d = false;
-      for (int i = 0; i < ndrop; i++)
-        d = d || drop_idx[i] == a->prime_idx[r];
-      (d ? drop : keep).push_back(a->prime_idx[r]);
-    }
-    for (int i = 0; i < nadd; i++) {
-      if (find_row(a->prime_idx, add_idx[i]) >= 0)
-        return HX_ERR_UNSUPPORTED;
-      for (int j = 0; j < ndrop; j++)
-        if (drop_idx[j] == add_idx[i])
-          return HX_ERR_UNSUPPORTED;
-      keep.push_back(add_idx[i]);
-    }
-    if (drop.size() < 2 || (int)keep.size() == nadd)
-      return HX_ERR_UNSUPPORTED;
-    hx_poly* ps[hx::MD_MAXPOLY];
-    if (1 + nother > hx::MD_MAXPOLY)
-      return HX_ERR_UNSUPPORTED;
-    ps[0] = a;
-    for (int i = 0; i < nother; i++)
-      ps[1 + i] = others[i];
-    return scale_down_multi_fused(ps, 1 + nother, drop, keep, ptxt, add_idx, nadd, tsrc);
-  }
-  if (nadd > 0) {
-    bool ok = ndrop == 1 && c->pow2 && c->logn >= 13 && c->logn <= 15 && find_row(a->prime_idx, drop_idx[0]) >= 0 &&
-              a->nrows() + nadd - 1 <= MAX_ROWS && ptxt < ((uint64_t)1 << 62);
-    for (int i = 0; i < nadd && ok; i++)
-      if (find_row(a->prime_idx, add_idx[i]) >= 0 || add_idx[i] == drop_idx[0])
-        ok = false;
-    // the fused kernels take |S| <= ptxtSpace/2 + 1 as already reduced modulo every kept prime
-    for (int i = 0; i < nadd && ok; i++)
-      ok = ptxt / 2 + 2 < c->primes[add_idx[i]].q;
-    for (int r = 0; r < a->nrows() && ok; r++)
-      ok = a->prime_idx[r] == drop_idx[0] || ptxt / 2 + 2 < c->primes[a->prime_idx[r]].q;
-    if (!ok)
-      return HX_ERR_UNSUPPORTED;
-    // make room and append the new (never read) rows; a shared poly (copy-on-write) gets its output
-    // slab below instead
-    if (!a->shared())
-      CHK(poly_reserve(a, a->nrows() + nadd));
-    for (int i = 0; i < nother; i++)
-      if (!others[i]->shared())
-        CHK(poly_reserve(others[i], a->nrows() + nadd));
-    for (int i = 0; i < nadd; i++)
-      a->prime_idx.push_back(add_idx[i]);
-    rollback.n = nadd;
-  }
-  const int nrows_old = a->nrows() - nadd;
-  // diff = getIndexSet() / s : only primes actually present are dropped
-  std::vector<int> drop, keep;
-  for (int r = 0; r < a->nrows(); r++) {
-    bool d = false;
-    for (int i = 0; i < ndrop; i++)
-      if (drop_idx[i] == a->prime_idx[r])
-        d = true;
-    (d ? drop : keep).push_back(a->prime_idx[r]);
-  }
-  if (drop.empty()) {  // nothing to do; a requested norm is that of delta = 0
-    if (tsrc)
-      return HX_ERR_UNSUPPORTED;   // (none of the listed primes is there: the caller forms the product on its own)
-    if (c->want_frac) {
-      double* fr = frac_take(c, a->row_words() * (size_t)(1 + nother));
-      if (fr)
-        HIPCHK(hipMemsetAsync(fr, 0, a->row_words() * (size_t)(1 + nother) * sizeof(double), c->stream));
-    }
-    return HX_OK;
-  }
-  if (keep.empty())
-    return fail(HX_ERR_PRIMESET, "s and the index set must have some intersection");
-  if ((int)drop.size() > MAX_EXT_SRC)
-    return fail(HX_ERR_UNSUPPORTED, "scaleDownToSet dropping more than %d primes", MAX_EXT_SRC);
-  size_t rw = a->row_words();
-  int nd = (int)drop.size(), nk = (int)keep.size();
-  bool small_S = true;  // |S| <= ptxtSpace/2 + 1 is a reduced residue of every kept prime
-  for (int pr : keep)
-    small_S = small_S && ptxt / 2 + 2 < c->primes[pr].q;
-  if (tsrc && nd >= 2) {   // (nadd == 0 here: the mod-up case went to the batched path above)
-    hx_poly* ps[hx::MD_MAXPOLY];
-    if (1 + nother > hx::MD_MAXPOLY)
-      return HX_ERR_UNSUPPORTED;
-    ps[0] = a;
-    for (int i = 0; i < nother; i++)
-      ps[1 + i] = others[i];
-    return scale_down_multi_fused(ps, 1 + nother, drop, keep, ptxt, nullptr, 0, tsrc);
-  }
-  if (tsrc && !(nd == 1 && nk <= MAX_ROWS && small_S))
-    return HX_ERR_UNSUPPORTED;   // (checked before anything was changed: nadd > 0 passed its own test above)
-  if (nd == 1 && c->pow2 && c->logn >= 13 && c->logn <= 15 && nk <= MAX_ROWS && ptxt < ((uint64_t)1 << 62) && small_S) {
-    // fused path: [inverse NTT of the dropped row + delta preparation] then [forward NTT of
-    // delta on every kept row, with  c <- (c - delta) / qd  in its store].  The last row takes
-    // the dropped row's slot, so no compaction copy is needed.
-    const int dprime = drop[0], drow = find_row(a->prime_idx, dprime), last = a->nrows() - 1;
-    const uint64_t qd = c->primes[dprime].q;
-    // inputs and outputs: in place, except for polys that share their slab with a copy
-    // (hx_poly_copy is lazy) -- those read the shared slab and write a fresh one, which is what
-    // makes `Ctxt tmp = other; tmp.bringToSet(s)` cost no copy at all
-    PolyBases pb, pbo;
-    memset(&pb, 0, sizeof pb);
-    memset(&pbo, 0, sizeof pbo);
-    pb.n = pbo.n = 1 + nother;
-    hx_poly* ps[hx::MD_MAXPOLY];
-    uint64_t* fresh[hx::MD_MAXPOLY] = {nullptr};
-    ps[0] = a;
-    for (int i = 0; i < nother; i++)
-      ps[1 + i] = others[i];
-    const int ncap = a->nrows() + 2;
-    const size_t nbytes = (size_t)ncap * rw * 8;
-    for (int i = 0; i < pb.n; i++)
-      if (ps[i]->share && !ps[i]->shared())
-        CHK(poly_own(ps[i]));  // last holder of its slab: plain in-place
-    // (all output slabs are taken BEFORE any shared slab is released: two listed polys may share
-    // one slab, and a slab returned to the pool could come straight back as somebody's output)
-    auto drop_fresh = [&]() {
-      for (int i = 0; i < pb.n; i++)
-        if (fresh[i])
-          pool_free(c, fresh[i], nbytes);
-    };
-    for (int i = 0; i < pb.n; i++) {
-      pb.d[i] = pbo.d[i] = ps[i]->d;
-      if (ps[i]->shared()) {
-        hipError_t pe = pool_alloc(c, nbytes, (void**)&fresh[i]);
-        if (pe != hipSuccess) {
-          drop_fresh();
-          return fail(HX_ERR_NOMEM, "hipMalloc(%zu) failed: %s", nbytes, hipGetErrorString(pe));
-        }
-        pbo.d[i] = fresh[i];
-      }
-    }
-    struct FreshGuard {  // error paths below give the output slabs back
-      decltype(drop_fresh)& f;
-      bool armed = true;
-      ~FreshGuard()
-      {
-        if (armed)
-          f();
-      }
-    } fresh_guard{drop_fresh};
-    CHK(ensure_scratch(c, 0, rw * pb.n));
-    CHK(ensure_scratch(c, 1, rw * pb.n));
-    hx::ModDownPrep P;
-    memset(&P, 0, sizeof P);
-    P.xs = c->scratch[0];
-    P.S = reinterpret_cast<int64_t*>(c->scratch[1]);
-    P.half = (qd - 1) / 2;
-    if (ptxt > 1) {
-      P.ptxt = ptxt;
-      P.ptxt_mu64 = (uint64_t)((((hxh::u128)1) << 64) / ptxt);
-      int kb = hxh::bitlen(ptxt);
-      P.ptxt_k = (uint32_t)kb;
-      P.ptxt_mu = (uint64_t)((((hxh::u128)1) << (2 * kb)) / ptxt);
-      P.qd_mod_p = qd % ptxt;
-      P.qdinv_mod_p = hxh::invmod(qd % ptxt, ptxt);
-      if (P.qdinv_mod_p == 0)
-        return fail(HX_ERR_INVALID, "dropped primes are not invertible modulo ptxtSpace");
-    }
-    P.qd = qd;
-    // Who forms S, and the norm (dev_common.h: ModDownPrep::fuse).  The norm rides in the prep workgroups when the
-    // whole norm batch comes from this call (the condition under which the norm kernel would read (x, S) in place,
-    // below), the ring is the radix-16 one and the read-back is a plain store into the pinned slot on this stream.
-    P.fuse = c->sw.no_prep_fuse ? 0u : 1u;
-    const size_t nfrac = rw * (size_t)pb.n;
-    const bool xs_in_place = c->want_frac && c->xs_rows == 0 && c->frac_pos == 0 && nfrac <= c->frac_cap && !c->want_fdelta;
-    // (ptxt < 2^32: the norm-carrying kernels keep no scalar registers for the wide correction's constants)
-    const bool norm_in_prep = P.fuse && xs_in_place && c->logn == 14 && !c->capturing && (ptxt >> 32) == 0;
-    if (norm_in_prep) {
-      prep_norm_drop(c);   // (a slot an earlier call took and then failed before it had an (x, S) block to go with it)
-      CHK(norm_wtab(c));
-      CHK(norm_slot_take(c, pb.n * a->batch, &c->prep_np));
-      c->prep_norm = true;   // (given back by flush_xs / frac_begin unless embed_norms() queues it)
-      P.fuse = 2;
-      P.inv_qd = 1.0 / (double)qd;
-      P.wtab = reinterpret_cast<const double*>(c->d_wtab);
-      P.norm_out = c->prep_np.pinned;
-    }
-    if (nadd > 0) {
-      uint64_t F = 1;
-      for (int i = 0; i < nadd; i++)
-        F = hxh::mulmod(F, c->primes[add_idx[i]].q % qd, qd);
-      P.has_up = 1;
-      P.upS.w = hxh::mulmod(F, c->primes[dprime].last_s, qd);
-      P.upS.wp = tw_companion(c->primes[dprime], P.upS.w);
-      P.upN.w = hxh::mulmod(F, c->primes[dprime].last_n, qd);
-      P.upN.wp = tw_companion(c->primes[dprime], P.upN.w);
-    }
-    // per-row constants (cached per (dropped prime, kept rows and their output slots))
-    std::vector<uint64_t> key;
-    key.push_back(0xD0D0D0D0ull);
-    key.push_back((uint64_t)dprime);
-    for (int j = 0; j < nadd; j++)
-      key.push_back(0xA000000ull | (uint64_t)add_idx[j]);
-    NttRows kr;
-    std::vector<hx::ModDownRow> hr(nk);
-    int i = 0;
-    for (int r = 0; r <= last; r++) {
-      if (r == drow)
-        continue;
-      const int pr = a->prime_idx[r];
-      const uint64_t q = c->primes[pr].q;
-      kr.row[i] = (uint16_t)r;
-      kr.prime[i] = (uint16_t)pr;
-      uint64_t qdm = qd % q, inv = hxh::invmod(qdm, q);
-      hr[i].qdm.w = qdm;
-      hr[i].qdm.wp = hxh::shoup(qdm, q);
-      hr[i].inv.w = inv;
-      hr[i].inv.wp = tw_companion(c->primes[pr], inv);
-      hr[i].out_row = (uint32_t)((r == last && drow != last) ? drow : r);
-      hr[i].mode = 0;
-      hr[i].cf = hr[i].inv;
-      hr[i].cf_r2 = tw_r2(c->primes[pr], inv);
-      if (nadd > 0) {
-        if (r >= nrows_old) {
-          hr[i].mode = 2;  // a row the mod-up adds: c_r = 0, i.e. cf = 0 (its slot is never initialised)
-          hr[i].cf.w = hr[i].cf.wp = 0;
-          hr[i].cf_r2 = 0;
-        } else {
-          uint64_t F = 1;
-          for (int j = 0; j < nadd; j++)
-            F = hxh::mulmod(F, c->primes[add_idx[j]].q % q, q);
-          uint64_t cf = hxh::mulmod(F, inv, q);
-          hr[i].mode = 1;
-          hr[i].cf.w = cf;
-          hr[i].cf.wp = tw_companion(c->primes[pr], cf);
-          hr[i].cf_r2 = tw_r2(c->primes[pr], cf);
-        }
-      }
-      key.push_back(((uint64_t)pr << 28) | ((uint64_t)hr[i].out_row << 12) | hr[i].mode);
-      i++;
-    }
-    auto it = c->plans.find(key);
-    if (it == c->plans.end()) {
-      ExtPlan* pl = new ExtPlan();
-      memset(&pl->dev, 0, sizeof pl->dev);
-      HIPCHK(hipMalloc(&pl->blob, sizeof(hx::ModDownRow) * nk));
-      HIPCHK(hipMemcpy(pl->blob, hr.data(), sizeof(hx::ModDownRow) * nk, hipMemcpyHostToDevice));
-      it = c->plans.emplace(key, pl).first;
-    }
-    hx::ModDownApply A;
-    A.xs = c->scratch[0];
-    A.S = reinterpret_cast<const int64_t*>(c->scratch[1]);
-    A.rows = reinterpret_cast<const hx::ModDownRow*>(it->second->blob);
-    hipError_t e = tsrc ? hx::launch_moddown_tensor_pow2(c->logn, *tsrc, pbo, drow, dprime, kr, nk, a->batch, P, A,
-                                                         c->d_primes, c->d_tw, c->stream)
-                        : hx::launch_moddown_pow2(c->logn, pb, pbo, drow, dprime, kr, nk, a->batch, P, A,
-                                                  c->d_primes, c->d_tw, c->stream);
-    if (e != hipSuccess) {
-      prep_norm_drop(c);
-      return fail(HX_ERR_DEVICE, "mod-down launch failed: %s", hipGetErrorString(e));
-    }
-    fresh_guard.armed = false;
-    for (int i = 0; i < pb.n; i++)
-      if (fresh[i]) {  // the shared input slab stays with its other holders (or goes back to the
-        storage_release(ps[i]);  // pool, whose reuse is ordered behind the kernels just enqueued)
-        ps[i]->d = fresh[i];
-        ps[i]->cap_rows = ncap;
-      }
-    if (c->want_frac) {
-      const size_t n = rw * (size_t)pb.n;
-      double* fr = frac_take(c, n);
-      if (!fr)
-        return fail(HX_ERR_INVALID, "internal: fraction buffer too small");
-      if (c->xs_rows == 0 && c->frac_pos == n && !c->want_fdelta) {
-        // the whole norm batch comes from this call: the norm kernel reads (x, S) itself -- or the prep kernels
-        // have already formed the norms (xs_in_place above is this very condition, taken before the launch)
-        c->xs_first = 0;
-        c->xs_rows = pb.n * a->batch;
-        c->xs_inv_qd = 1.0 / (double)qd;
-      } else {
-        HX_LAUNCH(hx::frac_from_xs_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 4096)),
-                           dim3(256), 0, c->stream, c->scratch[0],
-                           reinterpret_cast<const int64_t*>(c->scratch[1]), 1.0 / (double)qd, fr, n);
-        HIPCHK(hipGetLastError());
-      }
-    }
-    rollback.n = 0;
-    if (drow != last)
-      a->prime_idx[drow] = a->prime_idx[last];
-    a->prime_idx.pop_back();
-    for (int i = 0; i < nother; i++)
-      others[i]->prime_idx = a->prime_idx;
-    return HX_OK;
-  }
-  if (nd >= 2 && 1 + nother <= hx::MD_MAXPOLY) {
-    hx_poly* ps[hx::MD_MAXPOLY];
-    ps[0] = a;
-    for (int i = 0; i < nother; i++)
-      ps[1 + i] = others[i];
-    int rc = scale_down_multi_fused(ps, 1 + nother, drop, keep, ptxt, nullptr, 0);
-    if (rc != HX_ERR_UNSUPPORTED)
-      return rc;
-  }
-  if (nother > 0)
-    return HX_ERR_UNSUPPORTED;
+  hx_ctx* c = m.c;
+  hx_poly* a = m.ps[0];
+  const int nd = m.nd(), nk = m.nk();
+  const size_t rw = m.rw;
   // toPoly(delta, diff): inverse transform of the dropped rows, out of place into scratch rows
   // of the same index (no row copies)
   CHK(ensure_scratch(c, 0, (size_t)a->nrows() * rw));
   std::vector<std::pair<int, int>> drows;
   for (int k = 0; k < nd; k++)
-    drows.emplace_back(find_row(a->prime_idx, drop[k]), drop[k]);
-  CHK(ntt_list(c, a->d, c->scratch[0], drows, a->batch, true));
+    drows.emplace_back(find_row(a->prime_idx, m.drop[k]), m.drop[k]);
+  CHK(ntt_list(c, a->d, c->scratch[0], drows, m.batch, true));
   ExtPlan* pl;
-  CHK(get_plan(c, drop, keep, ptxt > 1 ? ptxt : 0, &pl));
-  // delta on the kept primes goes into a fresh slab that then becomes the polynomial's storage:
-  // new[w] = (old[row of keep[w]] - delta[w]) / diffProd, so neither removePrimes' compaction nor
-  // a second buffer is needed
-  uint64_t* nd_buf = nullptr;
-  const int ncap = nk + 2;
-  const size_t nbytes = (size_t)ncap * rw * 8;
-  hipError_t pe = pool_alloc(c, nbytes, (void**)&nd_buf);
-  if (pe != hipSuccess)
-    return fail(HX_ERR_NOMEM, "hipMalloc(%zu) failed: %s", nbytes, hipGetErrorString(pe));
+  CHK(get_plan(c, m.drop, m.keep, m.ptxt > 1 ? m.ptxt : 0, &pl));
+  FreshSlabs fresh(m, nk + 2);
+  CHK(fresh.take(0));
+  uint64_t* nd_buf = fresh.d[0];
   ExtArgs args;
   clear_args(args);
   args.src = c->scratch[0];
@@ -4051,51 +3992,106 @@ static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* 
     args.src_row[k] = (uint16_t)drows[k].first;
   for (int t = 0; t < nk; t++)
     args.dst_row[t] = (uint16_t)t;
-  int rc = HX_OK;
   if (c->want_frac) {
     args.frac = frac_take(c, rw);
     if (!args.frac)
-      rc = fail(HX_ERR_INVALID, "internal: fraction buffer too small");
+      return fail(HX_ERR_INVALID, "internal: fraction buffer too small");
   }
-  if (rc == HX_OK)
-    rc = launch_extend(c, pl, args, rw);
-  if (rc == HX_OK)
-    rc = ntt_rows(c, nd_buf, keep, nk, 0, nk, a->batch, false);
-  if (rc != HX_OK) {
-    pool_free(c, nd_buf, nbytes);
-    return rc;
-  }
+  CHK(launch_extend(c, pl, args, rw));
+  CHK(ntt_rows(c, nd_buf, m.keep, nk, 0, nk, m.batch, false));
   // *this -= delta; *this /= diffProd, reading the kept rows where they are
   RowMap2 map;
   RowScalars sc;
   for (int r = 0; r < nk; r++) {
-    uint64_t q = c->primes[keep[r]].q, v = 1;
-    for (int k = 0; k < nd; k++)
-      v = hxh::mulmod(v, c->primes[drop[k]].q % q, q);
-    uint64_t inv = hxh::invmod(v, q);
-    map.p[r] = (uint16_t)keep[r];
-    map.brow[r] = (uint16_t)find_row(a->prime_idx, keep[r]);
+    const uint64_t q = c->primes[m.keep[r]].q, inv = hxh::invmod(prod_mod(c, m.drop, q), q);
+    map.p[r] = (uint16_t)m.keep[r];
+    map.brow[r] = (uint16_t)find_row(a->prime_idx, m.keep[r]);
     sc.c[r] = inv;
     sc.cp[r] = hxh::shoup(inv, q);
   }
-  HX_LAUNCH(hx::sub_scale_from_kernel, ew_grid(rw, nk), dim3(256), 0, c->stream, nd_buf,
-                     a->d, map, sc, rw, c->d_primes);
+  HX_LAUNCH(hx::sub_scale_from_kernel, ew_grid(rw, nk), dim3(256), 0, c->stream, nd_buf, a->d, map, sc, rw,
+            c->d_primes);
   HIPCHK(hipGetLastError());
-  if (a->owns) {
-    storage_release(a);  // stream-ordered reuse (a shared slab stays with its other holders)
-    a->d = nd_buf;
-    a->cap_rows = ncap;
-  } else {  // caller-owned storage: the compact result goes back into it
-    CHK(dcopy(c, a->d, nd_buf, (size_t)nk * rw));
-    pool_free(c, nd_buf, nbytes);
-  }
-  a->prime_idx = keep;
+  if (a->owns)
+    fresh.commit(0);  // stream-ordered reuse (a shared slab stays with its other holders)
+  else
+    CHK(dcopy(c, a->d, nd_buf, (size_t)nk * rw));  // (the fresh slab goes back to the pool)
+  a->prime_idx = m.keep;
   return HX_OK;
+}
+
+// The dispatcher.  others[0..nother): further polys with exactly a's prime rows and batch, mod-switched by the same
+// launches where a fused path applies.  add_idx: a mod-up folded in (ModSwitch::add), tsrc: the tensor product folded
+// in (ModSwitch::tsrc).  HX_ERR_UNSUPPORTED: nothing was touched, and the caller takes its own way round -- one call
+// per poly, addPrimesAndScale and the mod-down as two steps, the tensor product on its own.
+static int scale_down_impl(hx_poly* a, hx_poly** others, int nother, const int* drop_idx, int ndrop, uint64_t ptxt,
+                           const int* add_idx = nullptr, int nadd = 0, const hx::TensorSrc* tsrc = nullptr)
+{
+  if (!a)
+    return fail(HX_ERR_INVALID, "null poly");
+  hx_ctx* c = a->ctx;
+  CTX_ENTER(c);
+  if (c->want_frac)
+    CHK(flush_xs(c));  // the scratch slots of an earlier fused block are about to be reused
+  ModSwitch m;
+  CHK(modswitch_resolve(m, a, others, nother, drop_idx, ndrop, ptxt, add_idx, nadd, tsrc));
+  if (nadd > 0) {  // only the fused paths fold a mod-up in: one LISTED prime the single-prime path, else the other
+    if (ndrop == 1)
+      return modswitch_fused1_applies(m) ? modswitch_fused1(m) : HX_ERR_UNSUPPORTED;
+    return modswitch_fusedN_applies(m) ? modswitch_fusedN(m) : HX_ERR_UNSUPPORTED;
+  }
+  if (m.drop.empty()) {  // nothing to do; a requested norm is that of delta = 0
+    if (tsrc)
+      return HX_ERR_UNSUPPORTED;   // (none of the listed primes is there: the caller forms the product on its own)
+    if (c->want_frac) {
+      double* fr = frac_take(c, m.rw * (size_t)m.np);
+      if (fr)
+        HIPCHK(hipMemsetAsync(fr, 0, m.rw * (size_t)m.np * sizeof(double), c->stream));
+    }
+    return HX_OK;
+  }
+  if (m.keep.empty())
+    return fail(HX_ERR_PRIMESET, "s and the index set must have some intersection");
+  if (m.nd() > MAX_EXT_SRC)
+    return fail(HX_ERR_UNSUPPORTED, "scaleDownToSet dropping more than %d primes", MAX_EXT_SRC);
+  if (tsrc) {  // only the fused paths form the product parts
+    if (m.nd() == 1)
+      return modswitch_fused1_applies(m) ? modswitch_fused1(m) : HX_ERR_UNSUPPORTED;
+    return modswitch_fusedN_applies(m) ? modswitch_fusedN(m) : HX_ERR_UNSUPPORTED;
+  }
+  if (modswitch_fused1_applies(m))
+    return modswitch_fused1(m);
+  if (modswitch_fusedN_applies(m)) {
+    int rc = modswitch_fusedN(m);
+    if (rc != HX_ERR_UNSUPPORTED)
+      return rc;
+  }
+  if (nother > 0)
+    return HX_ERR_UNSUPPORTED;
+  return modswitch_generic(m);
 }
 
 extern "C" int hx_scale_down(hx_poly* a, const int* drop_idx, int ndrop, uint64_t ptxt)
 {
   return scale_down_impl(a, nullptr, 0, drop_idx, ndrop, ptxt);
+}
+
+// the polys of a multi call: none null, none listed twice (else an error); *same: one context, one batch, one list
+// of prime rows, and few enough for one set of launches
+static int same_shape(hx_poly** polys, int npoly, bool* same)
+{
+  *same = npoly <= hx::MD_MAXPOLY;
+  for (int i = 0; i < npoly; i++) {
+    if (!polys[i])
+      return fail(HX_ERR_INVALID, "null poly");
+    if (polys[i]->ctx != polys[0]->ctx || polys[i]->batch != polys[0]->batch ||
+        polys[i]->prime_idx != polys[0]->prime_idx)
+      *same = false;
+    for (int j = 0; j < i; j++)
+      if (polys[j] == polys[i])
+        return fail(HX_ERR_INVALID, "the same poly listed twice");
+  }
+  return HX_OK;
 }
 
 // The same mod-switch applied to several DoubleCRT objects that share one prime set and batch
@@ -4106,17 +4102,8 @@ extern "C" int hx_scale_down_multi(hx_poly** polys, int npoly, const int* drop_i
 {
   if (!polys || npoly < 1)
     return fail(HX_ERR_INVALID, "bad argument");
-  bool same = npoly <= hx::MD_MAXPOLY;
-  for (int i = 0; i < npoly; i++) {
-    if (!polys[i])
-      return fail(HX_ERR_INVALID, "null poly");
-    if (polys[i]->ctx != polys[0]->ctx || polys[i]->batch != polys[0]->batch ||
-        polys[i]->prime_idx != polys[0]->prime_idx)
-      same = false;
-    for (int j = 0; j < i; j++)
-      if (polys[j] == polys[i])
-        return fail(HX_ERR_INVALID, "the same poly listed twice");
-  }
+  bool same;
+  CHK(same_shape(polys, npoly, &same));
   if (same && npoly > 1) {
     int rc = scale_down_impl(polys[0], polys + 1, npoly - 1, drop_idx, ndrop, ptxt);
     if (rc != HX_ERR_UNSUPPORTED)
@@ -4136,17 +4123,8 @@ extern "C" int hx_bring_to_set_multi(hx_poly** polys, int npoly, const int* add_
 {
   if (!polys || npoly < 1 || (nadd > 0 && !add_idx) || (ndrop > 0 && !drop_idx))
     return fail(HX_ERR_INVALID, "bad argument");
-  bool same = npoly <= hx::MD_MAXPOLY;
-  for (int i = 0; i < npoly; i++) {
-    if (!polys[i])
-      return fail(HX_ERR_INVALID, "null poly");
-    if (polys[i]->ctx != polys[0]->ctx || polys[i]->batch != polys[0]->batch ||
-        polys[i]->prime_idx != polys[0]->prime_idx)
-      same = false;
-    for (int j = 0; j < i; j++)
-      if (polys[j] == polys[i])
-        return fail(HX_ERR_INVALID, "the same poly listed twice");
-  }
+  bool same;
+  CHK(same_shape(polys, npoly, &same));
   CHK(check_rows(polys[0]->ctx, add_idx, nadd));
   if (same && nadd > 0 && ndrop >= 1) {
     int rc = scale_down_impl(polys[0], polys + 1, npoly - 1, drop_idx, ndrop, ptxt, add_idx, nadd);
@@ -4245,8 +4223,6 @@ static int tensor_bring_to_set(const hx_poly* c0, const hx_poly* c1, const hx_po
     int rc = scale_down_impl(o0, os + 1, 2, drop_idx, ndrop, ptxt, add_idx, nadd, &T);
     if (rc != HX_ERR_UNSUPPORTED)
       return rc;
-    for (auto* o : os)
-      o->prime_idx = c0->prime_idx;   // (untouched by an unsupported attempt; restated for clarity)
   }
   CHK(tensor_launch(c0, c1, d0, d1, o0->d, o1->d, o2->d, nullptr));
   return hx_bring_to_set_multi(os, 3, add_idx, nadd, drop_idx, ndrop, ptxt);
@@ -4692,20 +4668,15 @@ static int ks_fix_table(hx_ctx* c, const std::vector<int>& all, const std::vecto
     for (int p : dp)
       key.push_back((uint64_t)p);
   }
-  auto it = c->plans.find(key);
-  if (it == c->plans.end()) {
+  auto fill = [&](void* host) {  // (runs on a miss only)
     if ((int)digit_primes.size() > hx::KS_MAXD)
       return fail(HX_ERR_UNSUPPORTED, "more than %d digits", hx::KS_MAXD);
-    std::vector<hx::KsFix> h(nall);
+    hx::KsFix* h = static_cast<hx::KsFix*>(host);
     for (int r = 0; r < nall; r++) {
-      memset(&h[r], 0, sizeof(hx::KsFix));
       h[r].owner = owner[r];
       uint64_t q = c->primes[all[r]].q;
       for (int e = 0; e < (int)digit_primes.size(); e++) {
-        uint64_t pe = 1;
-        for (int p : digit_primes[e])
-          pe = hxh::mulmod(pe, c->primes[p].q % q, q);
-        uint64_t inv = (h[r].owner >= 0 && e < h[r].owner) ? hxh::invmod(pe, q) : 0;
+        uint64_t inv = (h[r].owner >= 0 && e < h[r].owner) ? hxh::invmod(prod_mod(c, digit_primes[e], q), q) : 0;
         h[r].pinv[e].w = inv;
         h[r].pinv[e].wp = hxh::shoup(inv, q);
       }
@@ -4722,14 +4693,9 @@ static int ks_fix_table(hx_ctx* c, const std::vector<int>& all, const std::vecto
         h[r].one_m = hx::tw_mont_form(1, q);
       }
     }
-    ExtPlan* pl = new ExtPlan();
-    memset(&pl->dev, 0, sizeof pl->dev);
-    HIPCHK(hipMalloc(&pl->blob, sizeof(hx::KsFix) * nall));
-    HIPCHK(hipMemcpy(pl->blob, h.data(), sizeof(hx::KsFix) * nall, hipMemcpyHostToDevice));
-    it = c->plans.emplace(key, pl).first;
-  }
-  *out = reinterpret_cast<const hx::KsFix*>(it->second->blob);
-  return HX_OK;
+    return (int)HX_OK;
+  };
+  return plan_table(c, key, sizeof(hx::KsFix) * nall, fill, reinterpret_cast<const void**>(out));
 }
 
 // own_src/owner: when given, digit `owner[r]` of row r is not read from `dig` but rebuilt in the
