@@ -33,7 +33,7 @@ HEADERS = ["ntt_core.h", "dev_common.h", "rns_kernels.h", "rns_types.h", "hostma
            os.path.join("..", "..", "include", "helib_amd.h")]
 # headers only some units include (a change there does not rebuild the row kernels: minutes)
 UNIT_HEADERS = {"pfa_kernels.hip": ["pfa_core.h", "pfa_dev.h"], "rns_mfma_kernels.hip": ["mfma_ext.h", "rns_mfma_dev.h"],
-                "engine.hip": ["pfa_core.h", "pfa_dev.h", "switches.h", "mfma_ext.h", "rns_mfma_dev.h", "ckks_bridge.h"],
+                "engine.hip": ["pfa_core.h", "pfa_dev.h", "switches.h", "mfma_ext.h", "rns_plan.h", "rns_mfma_dev.h", "ckks_bridge.h"],
                 "ckks_slots.hip": ["ckks_slots.h", "ckks_bridge.h"], "bgv_slots.hip": ["bgv_slots.h", "bgv_encode.h", "ckks_bridge.h"],
                 "bgv_crt.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "ckks_bridge.h"],
                 "bgv_gf.hip": ["bgv_slots.h", "bgv_encode.h", "bgv_crt.h", "bgv_gf.h", "bgv_gf_tail.h", "ckks_bridge.h"],

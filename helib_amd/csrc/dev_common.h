@@ -69,7 +69,7 @@ struct ModDownPrep {
   const double* wtab;    //   the norm kernels' table, W^k = (wtab[2k], wtab[2k+1]) for k < N, W = exp(2 pi i / 2N);
   unsigned long long* norm_out;   //   squared maximum per prep workgroup ([poly][batch]), stored by the workgroup itself
 };
-// several dropped primes in ONE prep launch (scale_down_multi_fused): workgroup block j of
+// several dropped primes in ONE prep launch (engine.hip modswitch_fusedN): workgroup block j of
 // polys.n * batch workgroups inverse-transforms dropped row row[j] (prime prime[j]) of every poly
 // into x block j; up[2j], up[2j+1] = that prime's F*S0*N^-1 and F*N^-1 when the mod-up is folded in
 constexpr int MD_MAXDROP = 16;

@@ -10,6 +10,7 @@
 #include <algorithm>
 #include <chrono>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <string>
 #include <unordered_set>
@@ -26,6 +27,7 @@
 #include "pfa_dev.h"
 #include "rns_kernels.h"
 #include "mfma_ext.h"
+#include "rns_plan.h"
 #include "rns_mfma_dev.h"
 #include "norm_kernels.h"
 #include "prg_kernels.h"
@@ -2448,8 +2450,51 @@ extern "C" int hx_complex_conj(hx_poly* a)
 // ------------------------------------------------------------------
 // exact RNS plans
 // ------------------------------------------------------------------
-// tgt_moduli (optional): explicit target moduli instead of context primes (tgt then only sizes the
-// plan): any t in [2, 2^60) -- a target needs no transform tables (hx_poly_rem).
+// A device table uploaded from the host (get_plan, plan_table): an error return gives it back, take() hands it to
+// its owner (an ExtPlan, freed with its context).
+struct DevBlob {
+  void* p = nullptr;
+  DevBlob() = default;
+  DevBlob(const DevBlob&) = delete;
+  DevBlob& operator=(const DevBlob&) = delete;
+  ~DevBlob() { hipFree(p); }   // (a null pointer is fine)
+  int upload(const void* host, size_t bytes)
+  {
+    HIPCHK(hipMalloc(&p, bytes));
+    HIPCHK(hipMemcpy(p, host, bytes, hipMemcpyHostToDevice));
+    return HX_OK;
+  }
+  void* take() { return std::exchange(p, nullptr); }
+};
+
+static_assert(hx::rnsplan::wide_stride(17) == 8 + 20 && hx::rnsplan::wide_stride(40) == 8 + 40, "rns_types.h: wide_stride");
+
+// ExtPlanDev of a host plan (rns_plan.h) whose blob lies at d and whose matrix-core table, if built, at mfma
+static void bind_plan(const hx::rnsplan::Plan& hp, const uint64_t* d, const void* mfma, ExtPlanDev& v)
+{
+  namespace rp = hx::rnsplan;
+  auto u64 = [&](rp::Section s) { return hx::as_ro(d + hp.off[s]); };
+  auto u32 = [&](rp::Section s) { return hx::as_ro(reinterpret_cast<const uint32_t*>(d + hp.off[s])); };
+  auto tw = [&](rp::Section s) { return hx::as_ro(reinterpret_cast<const TW*>(d + hp.off[s])); };
+  memset(&v, 0, sizeof v);
+  v.n = hp.n, v.nt = hp.nt;
+  v.src_q = u64(rp::SRC_Q), v.src_mu64 = u64(rp::SRC_MU64), v.ginv = tw(rp::GINV), v.half = u64(rp::HALF);
+  v.tgt_q = u64(rp::TGT_Q), v.tgt_mu64 = u64(rp::TGT_MU64), v.tgt_mu = u64(rp::TGT_MU), v.tgt_k = u32(rp::TGT_K);
+  v.pmod = u64(rp::PMOD), v.W = tw(rp::W), v.upd = tw(rp::UPD), v.Wp = tw(rp::WP), v.tgt_lazy = u32(rp::TGT_LAZY);
+  v.src_rq = hx::as_ro(reinterpret_cast<const double*>(d + hp.off[rp::SRC_RQ]));
+  v.tgt_pack = u64(rp::TGT_PACK), v.tgt_pack_hps = u64(rp::TGT_PACK_HPS), v.wide_pack = u64(rp::WIDE_PACK);
+  v.hps_inv = tw(rp::HPS_INV), v.Wp_hps = tw(rp::WP_HPS), v.ginv_m = u64(rp::GINV_M);
+  v.ptxt = hp.ptxt, v.ptxt_mu64 = hp.ptxt_mu64, v.pinv_ptxt = hp.pinv_ptxt, v.pmod_ptxt = hp.pmod_ptxt;
+  v.ptxt_mu = hp.ptxt_mu, v.ptxt_k = hp.ptxt_k, v.hps_eps = hp.hps_eps;
+  v.garner_cs = hp.garner_cs, v.src_mont = hp.src_mont, v.corr_unit = hp.corr_unit;
+  v.fast_ok = hp.fast_ok, v.fast16_ok = hp.fast16_ok, v.hps_ok = hp.hps_ok, v.wide_ok = hp.wide_ok;
+  v.lazy_tight_ok = hp.lazy_tight_ok;
+  v.mfma_a = mfma, v.mfma_steps = hp.mfma_steps;
+}
+
+// The plan of the extension from the context primes src to the context primes tgt: key, lookup, build (rns_plan.h, on
+// the host), upload, bind.  tgt_moduli (optional): explicit target moduli instead of context primes (tgt then only
+// sizes the plan): any t in [2, 2^60) -- a target needs no transform tables (hx_poly_rem).
 // scaled: every target residue comes out multiplied by P^-1 mod q_t (W[t][k] and P mod t are
 // stored times P^-1: the kernels themselves are unchanged) -- the several-primes mod-switch wants
 // delta / P, whose transform it subtracts from c_r / P.
@@ -2457,6 +2502,7 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
                     uint64_t ptxt, ExtPlan** out, const std::vector<uint64_t>* tgt_moduli = nullptr,
                     bool scaled = false)
 {
+  namespace rp = hx::rnsplan;
   int n = (int)src.size(), nt = (int)tgt.size();
   if (n < 1 || n > MAX_EXT_SRC)
     return fail(HX_ERR_UNSUPPORTED, "basis extension supports 1..%d source primes (got %d)", MAX_EXT_SRC, n);
@@ -2476,324 +2522,32 @@ static int get_plan(hx_ctx* c, const std::vector<int>& src, const std::vector<in
     for (uint64_t t : *tgt_moduli)
       key.push_back(t);
   }
-  auto tq = [&](int t) { return tgt_moduli ? (*tgt_moduli)[t] : c->primes[tgt[t]].q; };
   auto it = c->plans.find(key);
   if (it != c->plans.end()) {
     *out = it->second;
     return HX_OK;
   }
-  std::vector<uint64_t> p(n);
+  std::vector<uint64_t> p(n), tq(nt);
   for (int k = 0; k < n; k++)
     p[k] = c->primes[src[k]].q;
-  // blob layout in 64-bit words
-  size_t off = 0;
-  auto take = [&](size_t words) {
-    size_t o = off;
-    off += (words + 1) & ~(size_t)1;  // keep 16-byte alignment
-    return o;
-  };
-  size_t o_srcq = take(n), o_srcmu = take(n), o_ginv = take((size_t)2 * n * n), o_half = take(n);
-  size_t o_tq = take(nt), o_tmu64 = take(nt), o_tmu = take(nt), o_tk = take((nt + 1) / 2);
-  size_t o_pmod = take(nt), o_W = take((size_t)2 * nt * n), o_upd = take((size_t)2 * nt);
-  size_t o_Wp = take((size_t)2 * n);
-  size_t o_tlazy = take((nt + 1) / 2);
-  size_t o_srcrq = take(n), o_tmu63 = take(nt);
-  size_t o_tchunk = take((nt + 1) / 2);
-  const size_t pack_stride = 10 + 2 * (size_t)n;  // per-target record of the fast kernels (TgtRec in rns_kernels.h)
-  size_t o_pack = take((size_t)nt * pack_stride);
-  size_t o_pack2 = take((size_t)nt * pack_stride);   // the same for the HPS front end (rns_kernels.h)
-  size_t o_hinv = take((size_t)2 * n), o_Wp2 = take((size_t)2 * n);
-  size_t o_ginvm = take((size_t)n * n);   // Garner constants times 2^64 (Proth-form sources, ExtPlanDev::ginv_m)
-  // rns_extend_wide_kernel (17..40 source primes): per-target record of 8 + n words, padded so that the last
-  // record's group-of-four multiplier reads stay inside the blob
-  const bool wide_cand = n > 16 && n <= 40;
-  // 9 .. 16 sources (the dropped primes of a CKKS level-2 mod-switch): the fast kernels' plans, whose HPS-form launches
-  // go to the matrix-core kernel too -- it reads the wide record's header for its rarer constants
-  const bool mfma_small = n >= c->sw.mfma_min_n && n <= 16 && n >= 4 && !c->sw.no_mfma_ext;
-  const bool wide_rec = wide_cand || mfma_small;
-  const size_t wide_stride = (size_t)hx::wide_stride(n);
-  size_t o_wide = wide_rec ? take((size_t)nt * wide_stride) : 0;
-  std::vector<uint64_t> h(off, 0);
-  std::vector<uint64_t> mfma_w(wide_rec ? (size_t)nt * n : 0), mfma_negp(wide_rec ? (size_t)nt : 0);   // (mfma_ext.h)
-  hxh::BigU P(1);
-  for (int k = 0; k < n; k++) {
-    h[o_srcq + k] = p[k];
-    h[o_srcmu + k] = (uint64_t)((((hxh::u128)1) << 64) / p[k]);
-    {
-      const double rq = 1.0 / (double)p[k];
-      memcpy(&h[o_srcrq + k], &rq, 8);
-    }
-    for (int l = 0; l < k; l++) {
-      uint64_t inv = hxh::invmod(p[l] % p[k], p[k]);
-      if (inv == 0)
-        return fail(HX_ERR_INVALID, "source primes are not pairwise coprime");
-      h[o_ginv + 2 * ((size_t)k * n + l)] = inv;
-      h[o_ginv + 2 * ((size_t)k * n + l) + 1] = hxh::shoup(inv, p[k]);
-      h[o_ginvm + (size_t)k * n + l] = (uint64_t)(((hxh::u128)inv << 64) % p[k]);
-    }
-    P.mul_word(p[k]);
-  }
-  {
-    hxh::BigU H = P;  // (P-1)/2 ; P is odd
-    H.sub_word(1);
-    H.shr1();
-    for (int k = 0; k < n; k++)
-      h[o_half + k] = H.divmod_word(p[k]);
-  }
-  uint32_t* tk = reinterpret_cast<uint32_t*>(&h[o_tk]);
-  uint32_t* tlazy = reinterpret_cast<uint32_t*>(&h[o_tlazy]);
-  uint32_t* tchunk = reinterpret_cast<uint32_t*>(&h[o_tchunk]);
-  hxh::u128 sum_src = 0;
-  uint64_t max_src = 0, min_src = ~0ull;
-  for (int k = 0; k < n; k++) {
-    sum_src += p[k];
-    max_src = std::max(max_src, p[k]);
-    min_src = std::min(min_src, p[k]);
-  }
-  for (int t = 0; t < nt; t++) {
-    uint64_t q = tq(t);
-    // lazy 128-bit accumulation is exact when sum_k a_k*W_k < (sum_k q_k)*q_t <= 8*q_t^2
-    // (red128_wide's domain; q_t <= 60 bits)
-    tlazy[t] = (hxh::bitlen(q) <= 60 && sum_src <= (hxh::u128)8 * q) ? 1u : 0u;
-    // seven terms + the carried remainder: r + 7 max_src q < 8 q^2 needs max_src <= q
-    tchunk[t] = (hxh::bitlen(q) <= 60 && max_src <= q) ? 1u : 0u;
-    h[o_tq + t] = q;
-    h[o_tmu64 + t] = (uint64_t)((((hxh::u128)1) << 64) / q);
-    int kb = hxh::bitlen(q);
-    tk[t] = (uint32_t)kb;
-    h[o_tmu + t] = (uint64_t)((((hxh::u128)1) << (2 * kb)) / q);
-    h[o_tmu63 + t] = (uint64_t)((((hxh::u128)1) << (63 + kb)) / q);  // < 2^64: q > 2^(kb-1)
-    uint64_t run = 1 % q;
-    for (int k = 0; k < n; k++) {
-      h[o_W + 2 * ((size_t)t * n + k)] = run;
-      h[o_W + 2 * ((size_t)t * n + k) + 1] = hxh::shoup(run, q);
-      run = hxh::mulmod(run, p[k] % q, q);
-    }
-    h[o_pmod + t] = run;  // P mod q
-    uint64_t pinv = hxh::invmod(run, q);
-    h[o_upd + 2 * (size_t)t] = pinv;
-    h[o_upd + 2 * (size_t)t + 1] = hxh::shoup(pinv, q);
-    if (scaled) {
-      if (pinv == 0)
-        return fail(HX_ERR_INVALID, "dropped primes are not invertible modulo a kept prime");
-      for (int k = 0; k < n; k++) {
-        const uint64_t w = hxh::mulmod(h[o_W + 2 * ((size_t)t * n + k)], pinv, q);
-        h[o_W + 2 * ((size_t)t * n + k)] = w;
-        h[o_W + 2 * ((size_t)t * n + k) + 1] = hxh::shoup(w, q);
-      }
-      h[o_pmod + t] = 1 % q;
-    }
-  }
-  ExtPlan* pl = new ExtPlan();
-  memset(&pl->dev, 0, sizeof pl->dev);
-  if (ptxt > 1) {
-    uint64_t run = 1 % ptxt;
-    for (int k = 0; k < n; k++) {
-      h[o_Wp + 2 * (size_t)k] = run;
-      h[o_Wp + 2 * (size_t)k + 1] = hxh::shoup(run, ptxt);
-      run = hxh::mulmod(run, p[k] % ptxt, ptxt);
-    }
-    uint64_t pinv = hxh::invmod(run, ptxt);
-    if (pinv == 0) {
-      delete pl;
-      return fail(HX_ERR_INVALID, "dropped primes are not invertible modulo ptxtSpace");
-    }
-    pl->dev.ptxt = ptxt;
-    pl->dev.ptxt_mu64 = (uint64_t)((((hxh::u128)1) << 64) / ptxt);
-    int kb = hxh::bitlen(ptxt);
-    pl->dev.ptxt_k = (uint32_t)kb;
-    pl->dev.ptxt_mu = (uint64_t)((((hxh::u128)1) << (2 * kb)) / ptxt);
-    pl->dev.pinv_ptxt = pinv;
-    pl->dev.pmod_ptxt = run;
-  }
-  // Proth-form targets (TgtRec::mont, rns_kernels.h): the record's multipliers, -P mod t (in mu63's slot) and P^-1 mod t
-  // (in the slot of 2^64 mod t) times 2^64 -- the fast kernels reduce such a target's limb sum by mont_redc128
-  const bool rns_proth = !c->sw.no_proth && !c->sw.no_proth_rns && n <= 16;
-  auto tgt_mont = [&](int t) { return rns_proth && hx::is_proth32(tq(t)); };
-  auto rec_to_mont = [&](uint64_t* rec) {
-    const uint64_t q = rec[0];
-    auto m64 = [&](uint64_t x) { return (uint64_t)(((hxh::u128)(x % q) << 64) % q); };
-    rec[2] = m64(q - rec[1] % q);
-    rec[4] |= (uint64_t)1 << 10;
-    for (int k = 0; k < n; k++)
-      rec[8 + k] = m64(rec[8 + k]);
-    rec[8 + 2 * n] = m64(rec[5]);
-  };
-  for (int t = 0; t < nt; t++) {
-    uint64_t* rec = &h[o_pack + (size_t)t * pack_stride];
-    rec[0] = h[o_tq + t];
-    rec[1] = h[o_pmod + t];
-    rec[2] = h[o_tmu63 + t];
-    rec[3] = h[o_tmu64 + t];
-    rec[4] = (uint64_t)tk[t] | ((uint64_t)tlazy[t] << 8) | ((uint64_t)tchunk[t] << 9);
-    rec[5] = h[o_upd + 2 * (size_t)t];
-    rec[6] = h[o_upd + 2 * (size_t)t + 1];
-    rec[7] = h[o_tmu + t];
-    for (int k = 0; k < n; k++) {
-      rec[8 + k] = h[o_W + 2 * ((size_t)t * n + k)];
-      rec[8 + n + k] = h[o_W + 2 * ((size_t)t * n + k) + 1];
-    }
-    const uint64_t r64 = (uint64_t)((((hxh::u128)1) << 64) % rec[0]);   // red128_any's constant
-    rec[8 + 2 * n] = r64;
-    rec[8 + 2 * n + 1] = hxh::shoup(r64, rec[0]);
-    if (tgt_mont(t))
-      rec_to_mont(rec);
-  }
-  // HPS front end: y_k = a_k (P/p_k)^-1 mod p_k, multipliers (P/p_k) mod t (scaled plans: / P, i.e.
-  // p_k^-1 mod t), the same header; "lazy" needs room for up to n + 1 extra multiples of t in the sum
-  bool hps_ok = n >= 2 && (n <= 16 || wide_cand) && (ptxt <= 1 || ptxt < ((uint64_t)1 << (wide_cand ? 56 : 58)));
-  if (hps_ok) {
-    auto prod_except = [&](int k, uint64_t m) {   // (P / p_k) mod m
-      uint64_t r = 1 % m;
-      for (int l = 0; l < n; l++)
-        if (l != k)
-          r = hxh::mulmod(r, p[l] % m, m);
-      return r;
-    };
-    for (int k = 0; k < n && hps_ok; k++) {
-      const uint64_t inv = hxh::invmod(prod_except(k, p[k]), p[k]);
-      hps_ok = inv != 0;
-      h[o_hinv + 2 * (size_t)k] = inv;
-      h[o_hinv + 2 * (size_t)k + 1] = hxh::shoup(inv, p[k]);
-      if (ptxt > 1) {
-        const uint64_t w = prod_except(k, ptxt);
-        h[o_Wp2 + 2 * (size_t)k] = w;
-        h[o_Wp2 + 2 * (size_t)k + 1] = hxh::shoup(w, ptxt);
-      }
-    }
-    for (int t = 0; t < nt && hps_ok && wide_rec; t++) {
-      // WideRec: q, P mod t (scaled: 1), 2^64 mod t with its Shoup companion, floor(2^64/t), P^-1 mod t with its
-      // companion, the companion of P mod t; then the multipliers (P/p_k) mod t (scaled: / P) as 30-bit limbs
-      const uint64_t q = tq(t);
-      uint64_t* rec = &h[o_wide + (size_t)t * wide_stride];
-      const uint64_t r64 = (uint64_t)((((hxh::u128)1) << 64) % q);
-      rec[0] = q;
-      rec[1] = h[o_pmod + t];
-      rec[2] = r64;
-      rec[3] = hxh::shoup(r64, q);
-      rec[4] = h[o_tmu64 + t];
-      rec[5] = h[o_upd + 2 * (size_t)t];
-      rec[6] = h[o_upd + 2 * (size_t)t + 1];
-      rec[7] = hxh::shoup(h[o_pmod + t], q);
-      const uint64_t pinv_t = h[o_upd + 2 * (size_t)t];   // P^-1 mod t
-      for (int k = 0; k < n; k++) {
-        uint64_t w = prod_except(k, q);
-        if (scaled)
-          w = hxh::mulmod(w, pinv_t, q);
-        rec[8 + k] = (w & 0x3fffffffull) | ((w >> 30) << 32);
-        mfma_w[(size_t)t * n + k] = w;
-      }
-      mfma_negp[t] = (q - rec[1] % q) % q;
-    }
-    for (int t = 0; t < nt && hps_ok && !wide_cand; t++) {
-      const uint64_t q = tq(t);
-      const uint64_t* rec = &h[o_pack + (size_t)t * pack_stride];
-      uint64_t* rec2 = &h[o_pack2 + (size_t)t * pack_stride];
-      for (int j = 0; j < 8; j++)
-        rec2[j] = rec[j];   // (a Proth-form target: rec[2] is -P 2^64 already)
-      rec2[8 + 2 * n] = rec[8 + 2 * n];
-      rec2[8 + 2 * n + 1] = rec[8 + 2 * n + 1];
-      const uint32_t lazy2 = (hxh::bitlen(q) <= 60 && sum_src + 32 <= (hxh::u128)8 * q) ? 1u : 0u;
-      rec2[4] = (uint64_t)tk[t] | ((uint64_t)lazy2 << 8) | ((uint64_t)tchunk[t] << 9) | (rec[4] & ((uint64_t)1 << 10));
-      const uint64_t pinv_t = h[o_upd + 2 * (size_t)t];   // P^-1 mod t
-      for (int k = 0; k < n; k++) {
-        uint64_t w = prod_except(k, q);
-        if (scaled)
-          w = hxh::mulmod(w, pinv_t, q);
-        rec2[8 + n + k] = hxh::shoup(w, q);
-        if (tgt_mont(t))
-          w = (uint64_t)(((hxh::u128)w << 64) % q);
-        rec2[8 + k] = w;
-      }
-    }
-  }
-  uint64_t* d = nullptr;
-  HIPCHK(hipMalloc((void**)&d, off * 8));
-  HIPCHK(hipMemcpy(d, h.data(), off * 8, hipMemcpyHostToDevice));
-  pl->blob = d;
-  pl->dev.tgt_pack = hx::as_ro(d + o_pack);
-  pl->dev.ginv_m = hx::as_ro(d + o_ginvm);
-  {
-    bool sm = rns_proth;
-    for (int k = 0; k < n && sm; k++)
-      sm = hx::is_proth32(p[k]);
-    pl->dev.src_mont = sm ? 1u : 0u;
-  }
-  pl->dev.tgt_pack_hps = hx::as_ro(d + o_pack2);
-  pl->dev.hps_inv = hx::as_ro(reinterpret_cast<const TW*>(d + o_hinv));
-  pl->dev.Wp_hps = hx::as_ro(reinterpret_cast<const TW*>(d + o_Wp2));
-  pl->dev.hps_eps = c->sw.hps_eps;
-  pl->dev.n = n;
-  pl->dev.nt = nt;
-  pl->dev.src_q = hx::as_ro(d + o_srcq);
-  pl->dev.src_mu64 = hx::as_ro(d + o_srcmu);
-  pl->dev.ginv = hx::as_ro(reinterpret_cast<const TW*>(d + o_ginv));
-  pl->dev.half = hx::as_ro(d + o_half);
-  pl->dev.tgt_q = hx::as_ro(d + o_tq);
-  pl->dev.tgt_mu64 = hx::as_ro(d + o_tmu64);
-  pl->dev.tgt_mu = hx::as_ro(d + o_tmu);
-  pl->dev.tgt_k = hx::as_ro(reinterpret_cast<const uint32_t*>(d + o_tk));
-  pl->dev.pmod = hx::as_ro(d + o_pmod);
-  pl->dev.W = hx::as_ro(reinterpret_cast<const TW*>(d + o_W));
-  pl->dev.upd = hx::as_ro(reinterpret_cast<const TW*>(d + o_upd));
-  pl->dev.Wp = hx::as_ro(reinterpret_cast<const TW*>(d + o_Wp));
-  pl->dev.tgt_lazy = hx::as_ro(reinterpret_cast<const uint32_t*>(d + o_tlazy));
-  // a_l < q_l <= max < 2*min <= 2*p_k, or the sources ascend (a_l < p_l <= p_k for l < k)
-  pl->dev.garner_cs = (max_src / 2 < min_src || std::is_sorted(p.begin(), p.end())) ? 1u : 0u;
-  pl->dev.src_rq = hx::as_ro(reinterpret_cast<const double*>(d + o_srcrq));
-  pl->dev.tgt_mu63 = hx::as_ro(d + o_tmu63);
-  {
-    bool ok = pl->dev.garner_cs && n <= 8 && (min_src >> 32) != 0;
-    for (int t = 0; t < nt && ok; t++)
-      ok = (tq(t) >> 32) != 0 && hxh::bitlen(tq(t)) <= 60;
-    pl->dev.fast_ok = ok ? 1u : 0u;
-    bool ok16 = pl->dev.garner_cs && n <= 16 && (min_src >> 32) != 0;
-    for (int t = 0; t < nt && ok16; t++)
-      ok16 = (tq(t) >> 32) != 0 && hxh::bitlen(tq(t)) <= 60;
-    pl->dev.fast16_ok = ok16 ? 1u : 0u;
-    {
-      // lazy output is read at the Proth rows' tight bounds: legal only when the kernel that wrote a Proth-form
-      // target row took its Montgomery branch (tgt_mont) -- derived here from the plan's own flags, not from the
-      // environment switches the call sites used to consult
-      bool lz = hxh::bitlen(max_src) <= 60;
-      for (int t = 0; t < nt && lz; t++)
-        if (!c->sw.no_proth && hx::is_proth32(tq(t)) && !tgt_mont(t))
-          lz = false;
-      pl->dev.lazy_tight_ok = lz ? 1u : 0u;
-    }
-    pl->dev.hps_ok = (hps_ok && ok16) ? 1u : 0u;   // (the front end lives in the fast kernels only)
-    bool okw = wide_cand && hps_ok && (min_src >> 32) != 0 && hxh::bitlen(max_src) <= 60;
-    for (int t = 0; t < nt && okw; t++)
-      okw = (tq(t) >> 32) != 0 && hxh::bitlen(tq(t)) <= 60;
-    pl->dev.wide_ok = okw ? 1u : 0u;
-    pl->dev.wide_pack = hx::as_ro(d + o_wide);
-    // the same extension on the matrix cores: multipliers as balanced 8-bit limbs in MFMA operand order (mfma_ext.h)
-    pl->dev.mfma_a = nullptr;
-    pl->dev.mfma_steps = 0;
-    const bool oks = mfma_small && pl->dev.hps_ok;   // (hps_ok: the fast kernels' preconditions hold and the HPS tables exist)
-    if ((okw || oks) && !c->sw.no_mfma_ext) {
-      std::vector<uint8_t> tab;
-      std::vector<uint64_t> tqs((size_t)nt);
-      for (int t = 0; t < nt; t++)
-        tqs[(size_t)t] = tq(t);
-      hx::mfx::build_tables(n, nt, tqs.data(), mfma_w.data(), mfma_negp.data(), &h[o_upd], tab);
-      uint8_t* dm = nullptr;
-      HIPCHK(hipMalloc((void**)&dm, tab.size()));
-      HIPCHK(hipMemcpy(dm, tab.data(), tab.size(), hipMemcpyHostToDevice));
-      pl->blob_mfma = dm;
-      pl->dev.mfma_a = dm;
-      pl->dev.mfma_steps = (uint32_t)hx::mfx::steps_for(n);
-    }
-  }
-  pl->dev.tgt_chunk7 = hx::as_ro(reinterpret_cast<const uint32_t*>(d + o_tchunk));
-  {
-    bool unit = scaled && ptxt > 1;   // (P mod t is 1 in a scaled plan)
-    for (int t = 0; t < nt && unit; t++)
-      unit = ptxt <= tq(t);
-    pl->dev.corr_unit = unit ? 1u : 0u;
-  }
-  c->plans[key] = pl;
-  *out = pl;
+  for (int t = 0; t < nt; t++)
+    tq[t] = tgt_moduli ? (*tgt_moduli)[t] : c->primes[tgt[t]].q;
+  rp::Switches sw;
+  sw.no_proth = c->sw.no_proth, sw.no_proth_rns = c->sw.no_proth_rns, sw.no_mfma_ext = c->sw.no_mfma_ext;
+  sw.mfma_min_n = c->sw.mfma_min_n, sw.hps_eps = c->sw.hps_eps;
+  const rp::Plan hp = rp::build(p, tq, ptxt, scaled, sw);
+  if (hp.err)
+    return fail(HX_ERR_INVALID, "%s", rp::message(hp.err));
+  DevBlob blob, mfma;
+  CHK(blob.upload(hp.blob.data(), hp.blob.size() * 8));
+  if (!hp.mfma.empty())
+    CHK(mfma.upload(hp.mfma.data(), hp.mfma.size()));
+  std::unique_ptr<ExtPlan> pl(new ExtPlan());
+  bind_plan(hp, static_cast<const uint64_t*>(blob.p), mfma.p, pl->dev);
+  c->plans.emplace(key, pl.get());   // complete from here on: the context owns the plan and its tables
+  pl->blob = blob.take();
+  pl->blob_mfma = mfma.take();
+  *out = pl.release();
   return HX_OK;
 }
 
@@ -2813,111 +2567,104 @@ static int redo_prepare(hx_ctx* c, size_t row_words, uint32_t** out)
   *out = c->d_redo;
   return HX_OK;
 }
-// The HPS form pays from nine source primes on: measured same-box (gpurun_out r3c29), the digit kernel with 5-8 primes
-// per digit is 3-5 % SLOWER with it (366 vs 350 us at BGV L=16, 828 vs 808 us at CKKS L=24: eight u64 -> double
-// conversions cost what the 10-28 dependent Garner products cost), the basis extension of 11 dropped primes is faster
-// (Garner there is 55 products and spills 62 dwords; CKKS level 2 +3 %).  HX_HPS_MIN_N overrides (tests force 2).
-static int hps_min_n(const hx_ctx* c)
-{
-  return c->sw.hps_min_n;
-}
 static const dim3 REDO_GRID(64);   // the Garner pass over the listed coefficients (grid-stride; the list is almost always empty)
 
-static int launch_extend(hx_ctx* c, const ExtPlan* pl, const ExtArgs& args_in, size_t row_words)
+// rns_extend_fast_kernel<n, HPS> (1 .. 16 sources) over `grid` workgroups
+template <bool HPS>
+static void launch_fast(hx_ctx* c, const ExtPlanDev& P, const ExtArgs& args, size_t row_words, dim3 grid)
 {
-  dim3 grid((unsigned)((row_words + 255) / 256)), block(256);
-  int n = pl->dev.n;
-  ExtArgs args = args_in;
-  args.redo = nullptr;
-  if (pl->dev.fast16_ok) {
-    // HPS form + Garner over its redo list when the plan has the tables and no row is updated in place (an in-place
-    // update cannot be redone); otherwise Garner over everything
-    // (the plan carries the matrix-core tables from mfma_min_n sources on: below hps_min_n too)
-    const bool mfma = pl->dev.hps_ok && pl->dev.mfma_steps != 0 && args.upd == nullptr && row_words < ((size_t)1 << 32);
-    const bool hps = mfma || (pl->dev.hps_ok && n >= hps_min_n(c) && args.upd == nullptr && row_words < ((size_t)1 << 32));
-    if (hps)
-      CHK(redo_prepare(c, row_words, &args.redo));
-    if (mfma)   // the HPS form with its target sums on the matrix cores; the Garner form below over its redo list
-      HIPCHK(hx::launch_rns_extend_mfma(pl->dev, args, row_words, c->stream));
-#define HX_EXT_FAST(NN)                                                                                            \
-  case NN:                                                                                                         \
-    if (hps) {                                                                                                     \
-      if (!mfma)                                                                                                   \
-        HX_LAUNCH((hx::rns_extend_fast_kernel<NN, true>), grid, block, 0, c->stream, pl->dev, args, row_words);    \
-      HX_LAUNCH((hx::rns_extend_fast_kernel<NN, false>), REDO_GRID, block, 0, c->stream, pl->dev, args, row_words); \
-    } else {                                                                                                       \
-      HX_LAUNCH((hx::rns_extend_fast_kernel<NN, false>), grid, block, 0, c->stream, pl->dev, args, row_words);     \
-    }                                                                                                              \
+#define HX_EXT_FAST(NN)                                                                                              \
+  case NN:                                                                                                           \
+    HX_LAUNCH((hx::rns_extend_fast_kernel<NN, HPS>), grid, dim3(256), 0, c->stream, P, args, row_words);             \
     break;
-    switch (n) {
-      HX_EXT_FAST(1) HX_EXT_FAST(2) HX_EXT_FAST(3) HX_EXT_FAST(4) HX_EXT_FAST(5) HX_EXT_FAST(6) HX_EXT_FAST(7) HX_EXT_FAST(8)
-      HX_EXT_FAST(9) HX_EXT_FAST(10) HX_EXT_FAST(11) HX_EXT_FAST(12) HX_EXT_FAST(13) HX_EXT_FAST(14) HX_EXT_FAST(15)
-      HX_EXT_FAST(16)
-    }
+  switch (P.n) {
+    HX_EXT_FAST(1) HX_EXT_FAST(2) HX_EXT_FAST(3) HX_EXT_FAST(4) HX_EXT_FAST(5) HX_EXT_FAST(6) HX_EXT_FAST(7) HX_EXT_FAST(8)
+    HX_EXT_FAST(9) HX_EXT_FAST(10) HX_EXT_FAST(11) HX_EXT_FAST(12) HX_EXT_FAST(13) HX_EXT_FAST(14) HX_EXT_FAST(15)
+    HX_EXT_FAST(16)
+  }
 #undef HX_EXT_FAST
-    HIPCHK(hipGetLastError());
-    return HX_OK;
+}
+
+// rns_extend_wide_kernel<20 .. 40> (17 .. 40 sources): the plan's multipliers once per workgroup, in its LDS
+static int launch_wide(hx_ctx* c, const ExtPlanDev& P, const ExtArgs& args, size_t row_words)
+{
+  const dim3 grid((unsigned)((row_words + hx::WIDE_THREADS - 1) / hx::WIDE_THREADS)), block(hx::WIDE_THREADS);
+  const size_t lds = (size_t)P.nt * (size_t)hx::wide_stride(P.n) * 8;
+#define HX_EXT_WIDE(NN)                                                                                              \
+  {                                                                                                                  \
+    HIPCHK(hxp::dyn_lds((const void*)hx::rns_extend_wide_kernel<NN>, (int)hx::rnsplan::WIDE_LDS_MAX, c->device));    \
+    HX_LAUNCH((hx::rns_extend_wide_kernel<NN>), grid, block, lds, c->stream, P, args, row_words);                    \
+    return HX_OK;                                                                                                    \
   }
-  // (a plan whose multiplier table does not fit the LDS goes to the generic kernel below, which handles any plan)
-  const size_t wide_lds = (size_t)pl->dev.nt * (size_t)hx::wide_stride(n) * 8;   // the plan's multipliers, once per workgroup
-  if (pl->dev.wide_ok && row_words < ((size_t)1 << 32) && wide_lds <= 160 * 1024) {
-    // 17..40 source primes (the reference's own benchmark chain): HPS form, then Garner over the coefficients it
-    // could not vouch for (they were left untouched, so in-place updates are redone correctly too)
-    CHK(redo_prepare(c, row_words, &args.redo));
-    if (pl->dev.mfma_steps) {
-      // the target sums as an int8 matrix product (rns_mfma_kernels.hip), the Garner pass over its redo list behind it
-      HIPCHK(hx::launch_rns_extend_mfma(pl->dev, args, row_words, c->stream));
-      HX_LAUNCH((hx::rns_extend_kernel<40>), REDO_GRID, block, 0, c->stream, pl->dev, args, row_words);
-      HIPCHK(hipGetLastError());
-      return HX_OK;
-    }
-    const dim3 wgrid((unsigned)((row_words + hx::WIDE_THREADS - 1) / hx::WIDE_THREADS)), wblock(hx::WIDE_THREADS);
-    const size_t lds = wide_lds;
-    // (function attributes are per device: one flag per device a context of this process has used)
-    static std::mutex wide_mu;
-    static std::unordered_set<int> wide_attr;
-    {
-      std::lock_guard<std::mutex> lk(wide_mu);
-      if (!wide_attr.count(c->device)) {
-        for (const void* f : {(const void*)hx::rns_extend_wide_kernel<20>, (const void*)hx::rns_extend_wide_kernel<24>,
-                              (const void*)hx::rns_extend_wide_kernel<28>, (const void*)hx::rns_extend_wide_kernel<32>,
-                              (const void*)hx::rns_extend_wide_kernel<36>, (const void*)hx::rns_extend_wide_kernel<40>})
-          HIPCHK(hxp::dyn_lds(f, 160 * 1024, c->device));
-        wide_attr.insert(c->device);
-      }
-    }
-    if (n <= 20)
-      HX_LAUNCH((hx::rns_extend_wide_kernel<20>), wgrid, wblock, lds, c->stream, pl->dev, args, row_words);
-    else if (n <= 24)
-      HX_LAUNCH((hx::rns_extend_wide_kernel<24>), wgrid, wblock, lds, c->stream, pl->dev, args, row_words);
-    else if (n <= 28)
-      HX_LAUNCH((hx::rns_extend_wide_kernel<28>), wgrid, wblock, lds, c->stream, pl->dev, args, row_words);
-    else if (n <= 32)
-      HX_LAUNCH((hx::rns_extend_wide_kernel<32>), wgrid, wblock, lds, c->stream, pl->dev, args, row_words);
-    else if (n <= 36)
-      HX_LAUNCH((hx::rns_extend_wide_kernel<36>), wgrid, wblock, lds, c->stream, pl->dev, args, row_words);
-    else
-      HX_LAUNCH((hx::rns_extend_wide_kernel<40>), wgrid, wblock, lds, c->stream, pl->dev, args, row_words);
-    HX_LAUNCH((hx::rns_extend_kernel<40>), REDO_GRID, block, 0, c->stream, pl->dev, args, row_words);
-    HIPCHK(hipGetLastError());
-    return HX_OK;
-  }
-  if (n <= 8)
-    HX_LAUNCH((hx::rns_extend_kernel<8>), grid, block, 0, c->stream, pl->dev, args,
-                       row_words);
-  else if (n <= 16)
-    HX_LAUNCH((hx::rns_extend_kernel<16>), grid, block, 0, c->stream, pl->dev, args,
-                       row_words);
-  else if (n <= 40)
-    HX_LAUNCH((hx::rns_extend_kernel<40>), grid, block, 0, c->stream, pl->dev, args,
-                       row_words);
-  else if (n <= 64)
-    HX_LAUNCH((hx::rns_extend_kernel<64>), grid, block, 0, c->stream, pl->dev, args,
-                       row_words);
+  if (P.n <= 20)
+    HX_EXT_WIDE(20)
+  if (P.n <= 24)
+    HX_EXT_WIDE(24)
+  if (P.n <= 28)
+    HX_EXT_WIDE(28)
+  if (P.n <= 32)
+    HX_EXT_WIDE(32)
+  if (P.n <= 36)
+    HX_EXT_WIDE(36)
+  HX_EXT_WIDE(40)
+#undef HX_EXT_WIDE
+}
+
+// rns_extend_kernel<.>, which handles any plan
+static void launch_generic(hx_ctx* c, const ExtPlanDev& P, const ExtArgs& args, size_t row_words, dim3 grid)
+{
+  const dim3 block(256);
+  if (P.n <= 8)
+    HX_LAUNCH((hx::rns_extend_kernel<8>), grid, block, 0, c->stream, P, args, row_words);
+  else if (P.n <= 16)
+    HX_LAUNCH((hx::rns_extend_kernel<16>), grid, block, 0, c->stream, P, args, row_words);
+  else if (P.n <= 40)
+    HX_LAUNCH((hx::rns_extend_kernel<40>), grid, block, 0, c->stream, P, args, row_words);
+  else if (P.n <= 64)
+    HX_LAUNCH((hx::rns_extend_kernel<64>), grid, block, 0, c->stream, P, args, row_words);
   else  // whole chains of the reference's own benchmark parameter (bits=6400: 143 primes, e.g. the
         // toPoly of a decryption): the digits live in private memory -- slow, and rare
-    HX_LAUNCH((hx::rns_extend_kernel<MAX_EXT_SRC>), grid, block, 0, c->stream, pl->dev, args,
-                       row_words);
+    HX_LAUNCH((hx::rns_extend_kernel<MAX_EXT_SRC>), grid, block, 0, c->stream, P, args, row_words);
+}
+
+// One extension launch: the route (rns_plan.h extend_route, where the decision and its reasons live), then its kernels.
+// Every route but the Garner and the generic one is an HPS form that lists the coefficients it could not vouch for,
+// with a Garner-form pass over that list behind it.
+static int launch_extend(hx_ctx* c, const ExtPlan* pl, const ExtArgs& args_in, size_t row_words)
+{
+  namespace rp = hx::rnsplan;
+  const ExtPlanDev& P = pl->dev;
+  const dim3 grid((unsigned)((row_words + 255) / 256)), block(256);
+  ExtArgs args = args_in;
+  args.redo = nullptr;
+  const rp::Route route = rp::extend_route({P.fast16_ok, P.hps_ok, P.wide_ok, P.mfma_steps}, P.n, P.nt, args.upd != nullptr,
+                                           row_words, c->sw.hps_min_n);
+  if (route != rp::FAST_GARNER && route != rp::GENERIC)
+    CHK(redo_prepare(c, row_words, &args.redo));
+  switch (route) {
+    case rp::FAST_GARNER:
+      launch_fast<false>(c, P, args, row_words, grid);
+      break;
+    case rp::FAST_HPS:
+      launch_fast<true>(c, P, args, row_words, grid);
+      launch_fast<false>(c, P, args, row_words, REDO_GRID);
+      break;
+    case rp::FAST_MFMA:   // the target sums as an int8 matrix product (rns_mfma_kernels.hip)
+      HIPCHK(hx::launch_rns_extend_mfma(P, args, row_words, c->stream));
+      launch_fast<false>(c, P, args, row_words, REDO_GRID);
+      break;
+    case rp::WIDE_VALU:
+      CHK(launch_wide(c, P, args, row_words));
+      HX_LAUNCH((hx::rns_extend_kernel<40>), REDO_GRID, block, 0, c->stream, P, args, row_words);
+      break;
+    case rp::WIDE_MFMA:
+      HIPCHK(hx::launch_rns_extend_mfma(P, args, row_words, c->stream));
+      HX_LAUNCH((hx::rns_extend_kernel<40>), REDO_GRID, block, 0, c->stream, P, args, row_words);
+      break;
+    case rp::GENERIC:
+      launch_generic(c, P, args, row_words, grid);
+      break;
+  }
   HIPCHK(hipGetLastError());
   return HX_OK;
 }
@@ -3518,19 +3265,11 @@ static int plan_table(hx_ctx* c, const std::vector<uint64_t>& key, size_t bytes,
   if (it == c->plans.end()) {
     std::vector<uint64_t> host((bytes + 7) / 8, 0);
     CHK(fill((void*)host.data()));
-    struct Blob {  // an error return below gives the device table back
-      void* p = nullptr;
-      ~Blob()
-      {
-        if (p)
-          hipFree(p);
-      }
-    } blob;
-    HIPCHK(hipMalloc(&blob.p, bytes));
-    HIPCHK(hipMemcpy(blob.p, host.data(), bytes, hipMemcpyHostToDevice));
+    DevBlob blob;   // (an error return gives the device table back)
+    CHK(blob.upload(host.data(), bytes));
     ExtPlan* pl = new ExtPlan();
     memset(&pl->dev, 0, sizeof pl->dev);
-    std::swap(pl->blob, blob.p);
+    pl->blob = blob.take();
     it = c->plans.emplace(key, pl).first;
   }
   *out = it->second->blob;

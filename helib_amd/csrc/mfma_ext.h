@@ -1,6 +1,6 @@
 // mfma_ext.h -- the exact basis extension from many source primes as an int8 matrix product on the matrix cores
 // (rns_mfma_kernels.hip): limb split, table layout and recombination, as pure functions shared by the kernel, the host
-// table builder (engine.hip ext_plan_get) and the CPU restatement (tests/cpp/mfma_ext_test.cpp).
+// table builder (rns_plan.h build) and the CPU restatement (tests/cpp/mfma_ext_test.cpp).
 //
 // What is computed (src/DoubleCRT.cpp:565-599 addPrimes, :1464-1516 scaleDownToSet, :479-561 breakIntoDigits at the
 // reference's own benchmark chain, benchmarks/bgv_basic.cpp:247): for every target prime t

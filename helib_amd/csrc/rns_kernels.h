@@ -1009,8 +1009,8 @@ __device__ __forceinline__ bool break_digit_pass(const ExtPlanDev& P, uint64_t* 
 // =====================================================================
 // rns_extend_kernel in the fast form (same contract, chosen by the host when the plan has
 // fast16_ok): N compile-time, Garner with shoup4 on lazy values, residues by 30-bit-limb
-// accumulation -- the whole sum at once (tgt_lazy), or seven terms at a time with the previous
-// remainder carried (tgt_chunk7) when sum_k p_k is just above 8 q_t, as when as many same-size
+// accumulation -- the whole sum at once (TgtRec::lazy), or seven terms at a time with the previous
+// remainder carried (TgtRec::chunk7, bit 9 of the record's word 4) when sum_k p_k is just above 8 q_t, as when as many same-size
 // primes are dropped as a 60-bit accumulator scheme was sized for plus one -- otherwise shoup4
 // products normalised once.  The plaintext-space correction, the fraction and the stores are the
 // generic kernel's, so every output word and every fraction is the same.

@@ -5,7 +5,8 @@
 
 namespace hx {
 
-// words of one target's record: 8 header words + the multipliers padded to a multiple of four (host and device agree)
+// words of one target's record: 8 header words + the multipliers padded to a multiple of four (the host builder states
+// the same in rns_plan.h)
 __host__ __device__ inline int wide_stride(int n) { return 8 + ((n + 3) & ~3); }
 
 struct ExtPlanDev {
@@ -32,15 +33,12 @@ struct ExtPlanDev {
   ro_u32 tgt_lazy;  // [nt] 1: sum_k q_k <= 8*q_t, so the target residue can be taken from
                              // the 128-bit sum of the n products with ONE Barrett reduction
   ro_f64 src_rq;      // [n] 1.0 / q_k (host-rounded), for the value/P fraction
-  ro_u64 tgt_mu63;  // [nt] floor(2^(63+k) / q_t), k = bitlen(q_t)  (red128_q8)
   uint32_t fast_ok;          // break_digits_fast_kernel's preconditions hold for this plan:
                              // garner_cs, every prime > 2^32 (32-bit reciprocals), n <= 8
   uint32_t fast16_ok;        // the same with n <= 16: rns_extend_fast_kernel
   uint32_t corr_unit;        // scaled plan (tables carry P^-1, so "P mod t" is 1) and ptxtSpace <= every
                              // target prime: the plaintext-space correction of a target is the balanced
                              // remainder itself -- no reduction, no 128-bit Barrett product per target
-  ro_u32 tgt_chunk7;  // [nt] 1: every source prime <= q_t, so the limb sum may be taken 7
-                               // terms at a time with the previous remainder carried (r + 7 p q < 8 q^2)
   // HPS front end of the fast kernels (hps_ok): instead of Garner's n(n-1)/2 dependent products,
   //   y_k = a_k (P/p_k)^-1 mod p_k,  value = sum_k y_k (P/p_k) - v P,  v = floor(sum_k y_k / p_k),
   // the quotient v taken from a double-precision sum that is trusted only when its fractional part
@@ -71,7 +69,10 @@ struct ExtPlanDev {
   ro_u64 tgt_pack;    // [nt][10 + 2n] everything the fast kernels need of one target in ONE record
                       // (TgtRec): the loop over targets then makes one scalar-memory round trip per
                       // target instead of one per table (q, P mod t, flags, k, mu, W row: six
-                      // dependent s_load / s_waitcnt pairs per iteration before)
+                      // dependent s_load / s_waitcnt pairs per iteration before).  Two of its words exist
+                      // nowhere else: word 2, floor(2^(63+k) / q_t) with k = bitlen(q_t) (red128_q8), and bit 9
+                      // of word 4, "every source prime <= q_t": the limb sum may be taken 7 terms at a time
+                      // with the previous remainder carried (r + 7 p q < 8 q^2).  Layout: rns_plan.h
 };
 
 constexpr int EXT_MAXSRC = 192;  // source primes of one extension (a whole bits=6400 chain: 143)
