@@ -61,6 +61,7 @@ SYMBOLS = [
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
     "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum", "hx_mask_fan", "hx_tensor_sum",
+    "hx_table_tensor_sum",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -170,6 +171,7 @@ def lib():
             "hx_scaled_sub": [vp, vp, vp, vp, vp, vp],
             "hx_lin_comb": [vp, vp, vp, vp, ip, vp, vp],
             "hx_tensor_sum": [vp, vp, vp, vp, vp, vp, vp, ip],
+            "hx_table_tensor_sum": [vp, vp, vp, vp, vp, ip, vp, vp, ip, vp, ip],
             "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
             "hx_hoisted_automorph_sum": [vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
@@ -1216,6 +1218,29 @@ def tensorSum(a0, a1, b0, b1):
     def arr(ps):
         return (C.c_void_p * n)(*[p.h for p in ps])
     _chk(lib().hx_tensor_sum(outs[0].h, outs[1].h, outs[2].h, arr(a0), arr(a1), arr(b0), arr(b1), n))
+    return tuple(outs)
+
+
+def tableTensorSum(a0, a1, b0, b1, table, size=None):
+    """o0 = sum T[j k + i] a0[i] b0[j], o1 = sum T[j k + i] (a0[i] b1[j] + a1[i] b0[j]), o2 = sum T[j k + i] a1[i] b1[j]
+    over i < k = len(a0), j < l = len(b0), j k + i < size, in one pass (hx_table_tensor_sum): the last level of
+    computeAllProducts and the weighted sum of tableLookup before ONE relinearisation (src/tableLookup.cpp:94-103,
+    261-267).  a0 / a1 and b0 / b1: the parts pointing at 1 and at s of products1 and products2, all on one prime set and
+    batch; table: one DoubleCRT whose batch axis is the table index (batch = size, default: the table's batch), with a row
+    for every prime of a0[0].  -> (o0, o1, o2), new DoubleCRTs on the operands' prime set."""
+    if a0 is None or a1 is None or b0 is None or b1 is None or table is None:
+        raise InvalidArgument(HX_ERR_INVALID, "tableTensorSum: a0, a1, b0, b1 and the table are required")
+    k, l = len(a0), len(b0)
+    if k < 1 or l < 1:
+        raise InvalidArgument(HX_ERR_INVALID, "tableTensorSum needs at least one a and one b")
+    if len(a1) != k or len(b1) != l:
+        raise InvalidArgument(HX_ERR_INVALID, "tableTensorSum: a0 and a1, and b0 and b1, go together entry by entry")
+    size = table.batch if size is None else int(size)
+    outs = [likeUninit(a0[0]) for _ in range(3)]
+
+    def arr(ps):
+        return (C.c_void_p * len(ps))(*[p.h for p in ps])
+    _chk(lib().hx_table_tensor_sum(outs[0].h, outs[1].h, outs[2].h, arr(a0), arr(a1), k, arr(b0), arr(b1), l, table.h, size))
     return tuple(outs)
 
 

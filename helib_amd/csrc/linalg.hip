@@ -27,7 +27,12 @@
 // and of the loop of innerProduct before its relinearisation (hx_tensor_sum):
 //   (o0, o1, o2) = sum_t tensor((a0[t], a1[t]), (b0[t], b1[t]))
 // (src/Ctxt.cpp:2885-2891: tmp = *v1[i]; tmp.multLowLvl(*v2[i]); result += tmp), the 4 n operand rows read once and the
-// three parts of the sum written once.
+// three parts of the sum written once; and of the last level of computeAllProducts with the weighted sum of tableLookup
+// in front of ONE relinearisation (hx_table_tensor_sum):
+//   (o0, o1, o2) = sum_(i<k, j<l) T[j k + i] tensor((a0[i], a1[i]), (b0[j], b1[j]))
+// (src/tableLookup.cpp:261-267: *products[ii] = products1[i]; products[ii]->multiplyBy(products2[j]); and :94-103:
+// products[i].multByConstant(table[i]); out += products[i]), every a read once per four values of j and every table word
+// once per two batch elements.
 // The unit reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
 // key-switching matrix's rows, the tables of Z_m^*).
 #include <hip/hip_runtime.h>
@@ -224,6 +229,132 @@ tensor_sum_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, uint
         s0[b][j] = mad_reduce(s0[b][j], q, mu, mu64, k);
         s1[b][j] = mad_reduce(s1[b][j], q, mu, mu64, k);
         s2[b][j] = mad_reduce(s2[b][j], q, mu, mu64, k);
+      }
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    if (b0 + b >= batch)
+      break;
+    st_stream2(out0 + boff[b], make_ulonglong2((uint64_t)s0[b][0], (uint64_t)s0[b][1]));
+    st_stream2(out1 + boff[b], make_ulonglong2((uint64_t)s1[b][0], (uint64_t)s1[b][1]));
+    st_stream2(out2 + boff[b], make_ulonglong2((uint64_t)s2[b][0], (uint64_t)s2[b][1]));
+  }
+}
+
+// o0 = sum T[j k + i] a0[i] b0[j], o1 = sum T[j k + i] (a0[i] b1[j] + a1[i] b0[j]), o2 = sum T[j k + i] a1[i] b1[j] over
+// i < k, j < l, j k + i < size (hx_table_tensor_sum): the words that, per j, one hx_mul_add_many of k terms
+// (W_j = sum_i T[j k + i] a[i]) and then one hx_tensor_sum of the l pairs (W_j, b[j]) leave.  Per j the two inner sums
+// U0_j, U1_j take k <= MAD_CHUNK products from zero and one mad_reduce; the outer sums then take 4 products of residues
+// per j, two of them in o1, which is tensor_sum_kernel's count: a reduction every TSUM_CHUNK values of j.  A thread
+// works on TTS_JB values of j at once, so TSUM_CHUNK is a multiple of it and the reduction falls between two blocks.
+constexpr int TTS_MAX = 256;   // k and l
+constexpr int TTS_JB = 4;
+static_assert(TTS_MAX <= MAD_CHUNK, "an inner sum of k products is reduced once");
+static_assert(TSUM_CHUNK % TTS_JB == 0, "the outer sums are reduced between two blocks of j, every TSUM_CHUNK values of j");
+
+// Table (device, uint64 words, constant address space): [0, k) the bases of a0[i]; [k, 2k) of a1[i]; [2k, 2k + l) of
+// b0[j]; [2k + l, 2k + 2l) of b1[j]; all of them and the outputs share one prime set and batch.  tbl: the table poly's
+// rows, [its rows][size][N]; map.brow[row] is its row on the prime of output row `row`; entry e of that row serves every
+// batch element.  The thread shape is the family's: two adjacent coefficients of one prime row for BP batch elements.
+// Per block of TTS_JB values of j and per i the thread loads 2 BP operand vectors (non-temporal: they come back only
+// l / TTS_JB times, far apart) and TTS_JB table vectors (plain loads: the other batch groups read them too), each
+// table word used for BP elements and each operand word for TTS_JB values of j; 4 TTS_JB BP 128-bit accumulators for the
+// inner sums and 6 BP for the outer ones (DESIGN.md 3.9s has the register counts).  Entries past `size` (a ragged row
+// of the grid, rows without an entry) and values of j past l contribute nothing: neither their table words nor the b
+// of an empty row are loaded.  No LDS.
+template <int BP>
+__global__ void __launch_bounds__(256)
+table_tensor_sum_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, uint64_t* __restrict__ out2, ro_u64 tab,
+                        const uint64_t* __restrict__ tbl, int k, int l, int size, int batch, uint32_t N, RowMap2 map,
+                        const PrimeDev* __restrict__ primes)
+{
+  const uint32_t i2 = blockIdx.x * blockDim.x + threadIdx.x;   // vector index inside one polynomial
+  if (2 * i2 >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t kb = pd.k;
+  const size_t row_off = (size_t)row * batch * N;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = row_off + (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N + 2 * (size_t)i2;
+  const uint64_t* trow = tbl + (size_t)map.brow[row] * (size_t)size * N + 2 * (size_t)i2;
+  ro_u64 ta0 = tab, ta1 = tab + k, tb0 = tab + 2 * (size_t)k, tb1 = tab + 2 * (size_t)k + l;
+  u128 s0[BP][2], s1[BP][2], s2[BP][2];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    s0[b][0] = s0[b][1] = s1[b][0] = s1[b][1] = s2[b][0] = s2[b][1] = 0;
+  for (int j0 = 0; j0 < l; j0 += TTS_JB) {
+    u128 u0[TTS_JB][BP][2], u1[TTS_JB][BP][2];
+    int cnt[TTS_JB];   // the entries of row j0 + jj of the grid that exist: k, fewer in the ragged last row, 0 past l
+#pragma unroll
+    for (int jj = 0; jj < TTS_JB; jj++) {
+      const int left = size - (j0 + jj) * k;
+      cnt[jj] = left < 0 ? 0 : left < k ? left : k;
+#pragma unroll
+      for (int b = 0; b < BP; b++)
+        u0[jj][b][0] = u0[jj][b][1] = u1[jj][b][0] = u1[jj][b][1] = 0;
+    }
+    const uint64_t* tj = trow + (size_t)j0 * k * N;
+    for (int i = 0; i < k; i++) {
+      const uint64_t* pa0 = reinterpret_cast<const uint64_t*>(ta0[i]);
+      const uint64_t* pa1 = reinterpret_cast<const uint64_t*>(ta1[i]);
+      ulonglong2 x0[BP], x1[BP];
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        x0[b] = ld_stream2(pa0 + boff[b]);
+        x1[b] = ld_stream2(pa1 + boff[b]);
+      }
+#pragma unroll
+      for (int jj = 0; jj < TTS_JB; jj++) {
+        if (i < cnt[jj]) {   // (wave-uniform)
+          const ulonglong2 c = *reinterpret_cast<const ulonglong2*>(tj + ((size_t)jj * k + i) * N);
+#pragma unroll
+          for (int b = 0; b < BP; b++) {
+            u0[jj][b][0] += (u128)c.x * x0[b].x;
+            u0[jj][b][1] += (u128)c.y * x0[b].y;
+            u1[jj][b][0] += (u128)c.x * x1[b].x;
+            u1[jj][b][1] += (u128)c.y * x1[b].y;
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int jj = 0; jj < TTS_JB; jj++) {
+      if (cnt[jj] > 0) {
+        const uint64_t* pb0 = reinterpret_cast<const uint64_t*>(tb0[j0 + jj]);
+        const uint64_t* pb1 = reinterpret_cast<const uint64_t*>(tb1[j0 + jj]);
+#pragma unroll
+        for (int b = 0; b < BP; b++) {
+          const ulonglong2 y0 = ld_stream2(pb0 + boff[b]);
+          const ulonglong2 y1 = ld_stream2(pb1 + boff[b]);
+          const uint64_t w0x = mad_reduce(u0[jj][b][0], q, mu, mu64, kb), w0y = mad_reduce(u0[jj][b][1], q, mu, mu64, kb);
+          const uint64_t w1x = mad_reduce(u1[jj][b][0], q, mu, mu64, kb), w1y = mad_reduce(u1[jj][b][1], q, mu, mu64, kb);
+          s0[b][0] += (u128)w0x * y0.x;
+          s0[b][1] += (u128)w0y * y0.y;
+          s1[b][0] += (u128)w0x * y1.x;
+          s1[b][1] += (u128)w0y * y1.y;
+          s1[b][0] += (u128)w1x * y0.x;
+          s1[b][1] += (u128)w1y * y0.y;
+          s2[b][0] += (u128)w1x * y1.x;
+          s2[b][1] += (u128)w1y * y1.y;
+        }
+      }
+    }
+    if ((j0 + TTS_JB) % TSUM_CHUNK == 0 || j0 + TTS_JB >= l) {
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+#pragma unroll
+        for (int c = 0; c < 2; c++) {
+          s0[b][c] = mad_reduce(s0[b][c], q, mu, mu64, kb);
+          s1[b][c] = mad_reduce(s1[b][c], q, mu, mu64, kb);
+          s2[b][c] = mad_reduce(s2[b][c], q, mu, mu64, kb);
+        }
       }
     }
   }
@@ -1667,6 +1798,93 @@ extern "C" int hx_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_pol
   // (BP = 4 holds 24 128-bit accumulators and 16 operand vectors without scratch: DESIGN.md 3.9r)
   HX_LAUNCH_W(f.bp != 1, (hx::tensor_sum_kernel<1>), (hx::tensor_sum_kernel<4>), f.grid(), f.v.stream, o[0], o[1], o[2],
               hx::as_ro(tab.d), n, f.batch, f.N, f.map, f.primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_table_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_poly* const* a0, const hx_poly* const* a1,
+                                   int k, const hx_poly* const* b0, const hx_poly* const* b1, int l, const hx_poly* table,
+                                   int size)
+{
+  if (!o0 || !o1 || !o2 || !a0 || !a1 || !b0 || !b1 || !table)
+    return err(HX_ERR_INVALID, "null argument");
+  if (k < 1 || l < 1)
+    return err(HX_ERR_INVALID, "hx_table_tensor_sum needs at least one a and one b (k = %d, l = %d)", k, l);
+  if (k > hx::TTS_MAX || l > hx::TTS_MAX)
+    return err(HX_ERR_UNSUPPORTED, "hx_table_tensor_sum takes at most %d a and %d b (k = %d, l = %d)", hx::TTS_MAX,
+               hx::TTS_MAX, k, l);
+  if (size < 1 || size > k * l)
+    return err(HX_ERR_INVALID, "hx_table_tensor_sum: size %d is not in [1, k l] = [1, %d]", size, k * l);
+  if (o0 == o1 || o0 == o2 || o1 == o2)
+    return err(HX_ERR_INVALID, "two outputs are the same poly");
+  if (table == o0 || table == o1 || table == o2)
+    return err(HX_ERR_INVALID, "an output is also the table");
+  const hx_poly* const* in[4] = {a0, a1, b0, b1};
+  const int cnt[4] = {k, k, l, l};
+  static const char* const name[4] = {"a0", "a1", "b0", "b1"};
+  hx_ctx* ctx = hxi::poly_ctx(o0);
+  if (hxi::poly_ctx(o1) != ctx || hxi::poly_ctx(o2) != ctx || hxi::poly_ctx(table) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  for (int j = 0; j < 4; j++)
+    for (int t = 0; t < cnt[j]; t++) {
+      const hx_poly* p = in[j][t];
+      if (!p)
+        return err(HX_ERR_INVALID, "null poly (%s[%d])", name[j], t);
+      if (hxi::poly_ctx(p) != ctx)
+        return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects (%s[%d])", name[j], t);
+      if (p == o0 || p == o1 || p == o2)
+        return err(HX_ERR_INVALID, "an output is also an input (%s[%d])", name[j], t);
+    }
+  Frame f;
+  RC(f.open(ctx, o0, "hx_table_tensor_sum uploads a pointer table and cannot be captured in a graph"));
+  RC(same_shape(o1, f, "o1 differs from o0 in batch or prime set"));
+  RC(same_shape(o2, f, "o2 differs from o0 in batch or prime set"));
+  RC(f.even("hx_table_tensor_sum"));
+  for (int j = 0; j < 4; j++)
+    for (int t = 0; t < cnt[j]; t++) {
+      RC(same_shape(in[j][t], f, "%s[%d] differs from o0 in batch or prime set", name[j], t));
+      if (!aligned16(hxi::poly_rows_read(in[j][t])))
+        return err(HX_ERR_INVALID, "%s[%d]: rows are not 16-byte aligned", name[j], t);
+    }
+  // the table: its batch axis is the table index, and it has a row for every prime of o0 (in any order, among others)
+  int tbatch = 0;
+  std::vector<int> tidx;
+  RC(shape_of(table, &tbatch, &tidx));
+  if (tbatch != size)
+    return err(HX_ERR_INVALID, "the table has batch %d, not size = %d", tbatch, size);
+  hx::RowMap2 map;
+  for (int r = 0; r < f.rows; r++) {
+    const int at = row_of(tidx.data(), tidx.size(), f.idx[r]);
+    if (at < 0)
+      return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (the table has no row for prime %d)", f.idx[r]);
+    map.p[r] = (uint16_t)f.idx[r];
+    map.brow[r] = (uint16_t)at;
+  }
+  const uint64_t* tp = hxi::poly_rows_read(table);
+  if (!aligned16(tp))
+    return err(HX_ERR_INVALID, "table: rows are not 16-byte aligned");
+  if (f.rows == 0)
+    return HX_OK;
+  // table (kernel's layout): the bases of a0, a1, b0, b1
+  Table tab;
+  RC(tab.acquire(f, 2 * ((size_t)k + l)));
+  // the outputs first: one that still shares a poly's rows (a lazy hx_poly_copy) lets go of them before the inputs'
+  // addresses are read into the table
+  uint64_t* o[3] = {nullptr, nullptr, nullptr};
+  RC(hxi::poly_rows_write(o0, &o[0]));
+  RC(hxi::poly_rows_write(o1, &o[1]));
+  RC(hxi::poly_rows_write(o2, &o[2]));
+  if (!aligned16(o[0], o[1], o[2]))
+    return err(HX_ERR_INVALID, "output rows are not 16-byte aligned");
+  uint64_t* w = tab.h;
+  for (int j = 0; j < 4; j++)
+    for (int t = 0; t < cnt[j]; t++)
+      *w++ = (uint64_t)(uintptr_t)hxi::poly_rows_read(in[j][t]);
+  RC(tab.commit(f.v.stream));
+  // (a thread takes 2 batch elements and 4 values of j: 44 128-bit accumulators without scratch)
+  f.bp = f.batch == 1 ? 1 : 2;
+  HX_LAUNCH_W(f.bp != 1, (hx::table_tensor_sum_kernel<1>), (hx::table_tensor_sum_kernel<2>), f.grid(), f.v.stream, o[0], o[1],
+              o[2], hx::as_ro(tab.d), hxi::poly_rows_read(table), k, l, size, f.batch, f.N, map, f.primes);
   CK(hipGetLastError());
   return HX_OK;
 }

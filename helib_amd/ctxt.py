@@ -1626,6 +1626,10 @@ class Ctxt:
     # fused=None in Ctxt.innerProduct: the loop until hx_tensor_sum has been measured as the faster form in every pair
     # of tools/bench_binary_arith.py
     fuseTensorSum = False
+    # fused=None in table_lookup.tableLookup's lazy form: one hx_table_tensor_sum.  True because the kernel and the
+    # whole lookup through it won every alternated pair against l x hx_mul_add_many and one hx_tensor_sum
+    # (tools/bench_table_lookup.py, profiles/table_lookup.json); set it to False to get those calls back
+    fuseTableSum = True
 
     @staticmethod
     def innerProduct(v1, v2, fused=None):

@@ -684,6 +684,34 @@ int hx_lin_comb(hx_poly* out0, hx_poly* out1, const hx_poly* const* in0, const h
  * row, the n tensors and 3 (n - 1) additions read and write 7 n + 9 (n - 1); this call reads 4 n and writes 3. */
 int hx_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_poly* const* a0, const hx_poly* const* a1,
                   const hx_poly* const* b0, const hx_poly* const* b1, int n);
+/* The last level of computeAllProducts and the weighted sum of tableLookup under one relinearisation
+ * (src/tableLookup.cpp:261-267:  *products[ii] = products1[i];  products[ii]->multiplyBy(products2[j]);  ii = j k + i,
+ *  and :94-103:  products[i].multByConstant(table[i]);  out += products[i];)
+ * once the k + l operands sit on one prime set: relinearisation is linear, so the size tensor products weighted by the
+ * table entries are summed first, in one pass:
+ *   o0 = sum T[j k + i] a0[i] b0[j],   o1 = sum T[j k + i] (a0[i] b1[j] + a1[i] b0[j]),   o2 = sum T[j k + i] a1[i] b1[j]
+ * over i < k, j < l with j k + i < size, row by row modulo each prime.  (a0[i], a1[i]) and (b0[j], b1[j]) are the parts
+ * pointing at 1 and at s of products1[i] and products2[j]; o0, o1, o2 receive the parts pointing at 1, s and s^2.  The
+ * 2 k + 2 l operands and the three outputs share one batch and one prime set (same order), in evaluation form, words
+ * canonical in [0, q).  table is ONE poly whose batch axis is the table index: its batch equals size, entry e is T[e],
+ * and every entry serves every batch element of the ciphertexts; it needs a row for every prime of o0 and may have
+ * more, in another order.  1 <= k, l <= 256 and 1 <= size <= k l: the row of the grid that holds the last entry may be
+ * ragged, and the rows after it hold nothing (their b[j] are checked like the others, and not read).
+ * Every word written is canonical and equal to what, per j, one hx_mul_add_many of k terms (W_j = sum_i T[j k + i] a[i],
+ * not accumulating) and then one hx_tensor_sum of the pairs (W_j, b[j]) leave: an exact sum of products modulo q does
+ * not depend on the order of its terms.  The inner sums take k <= 256 products in 128 bits and one reduction; the outer
+ * sums are reduced every 128 values of j (256 products in o1).  Operands may repeat (a[i] and b[j] may be one poly).
+ * The outputs are overwritten, not read; one that still shares its rows with a lazy hx_poly_copy lets go of them
+ * first.  Null arguments, k or l below 1, a size outside [1, k l], two outputs that are one poly, an output
+ * that is also an input or the table, a poly of another context, a batch or prime set that differs from o0's, a table
+ * whose batch is not size and rows that are not 16-byte aligned are HX_ERR_INVALID; a prime of o0 that the table lacks
+ * is HX_ERR_PRIMESET; k or l above 256 and an odd phi(m) are HX_ERR_UNSUPPORTED; a refused call touches no operand.
+ * The call uploads a table of operand pointers through the staging ring of hx_mul_add_many, so it cannot be recorded:
+ * under an open graph capture it returns HX_ERR_UNSUPPORTED before touching the device.  Asynchronous on the context's
+ * stream.  In passes over a row of one batch element, the l + 1 calls read (2 + 1/4) k l + 4 l and write 2 l + 3; this
+ * call reads (1/2 + 1/2) k l + 2 l at batch > 1 and writes 3. */
+int hx_table_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_poly* const* a0, const hx_poly* const* a1, int k,
+                        const hx_poly* const* b0, const hx_poly* const* b1, int l, const hx_poly* table, int size);
 /* The hoisted sum of traceMap (src/matmul.cpp:2878-2887 over BasicAutomorphPrecon, :48-184:
  *   BasicAutomorphPrecon precon(ctxt);  acc = ctxt;  for each t  acc += *precon.automorph(k[t]);)
  * in one pass: the ciphertext plus its images under the n automorphisms k[t], each key-switched by its own matrix W[t]
