@@ -61,7 +61,7 @@ SYMBOLS = [
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
     "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum", "hx_mask_fan", "hx_tensor_sum",
-    "hx_table_tensor_sum",
+    "hx_table_tensor_sum", "hx_hoisted_mask_fan",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -174,6 +174,7 @@ def lib():
             "hx_table_tensor_sum": [vp, vp, vp, vp, vp, ip, vp, vp, ip, vp, ip],
             "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
             "hx_hoisted_automorph_sum": [vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
+            "hx_hoisted_mask_fan": [vp, vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -1265,6 +1266,32 @@ def hoistedAutomorphSum(digits, c0, c1, ks, Ws, special):
 
 
 hoistedSum = hoistedAutomorphSum    # the name helib_amd.ctxt looks for on a backend's ops
+
+
+def hoistedMaskFan(digits, c0, c1, ks, Ws, A, B, special):
+    """For every t: A[t] * (c0, c1) + B[t] * (the image of (c0, c1) under the automorphism ks[t], key-switched by Ws[t]
+    from the digit block of c1), in one pass (hx_hoisted_mask_fan): an inner node of replicateAll's recursion
+    (src/replicate.cpp:432-483) over one BasicAutomorphPrecon.  A, B: lists of DoubleCRT masks in evaluation form (batch 1
+    or the operands'), None in a position -- or None for a whole list -- standing for the constant 1.
+    -> (list of out0, list of out1), new DoubleCRTs on the primes of c0 followed by special."""
+    if digits is None or c0 is None or c1 is None or ks is None or Ws is None:
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedMaskFan: digits, c0, c1, ks and Ws are required")
+    n = len(ks)
+    if n < 1 or len(Ws) != n:
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedMaskFan takes at least one automorphism, and one matrix for each")
+    if (A is not None and len(A) != n) or (B is not None and len(B) != n):
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedMaskFan: A and B hold one mask (or None) per automorphism")
+    ka = np.array([int(k) for k in ks], dtype=np.uint64)
+    sp = _i32(list(special))
+    idx = c0.getIndexSet() + [int(i) for i in sp]
+    out0 = [DoubleCRT(c0.context, idx, c0.batch, zero=False) for _ in range(n)]
+    out1 = [DoubleCRT(c0.context, idx, c0.batch, zero=False) for _ in range(n)]
+
+    def arr(ps):
+        return (C.c_void_p * n)(*[p.h if p is not None else None for p in ps]) if ps is not None else None
+    _chk(lib().hx_hoisted_mask_fan(digits.h, c0.h, c1.h, _p(ka), arr(Ws), arr(A), arr(B), n, _p(sp), len(sp), arr(out0),
+                                   arr(out1)))
+    return out0, out1
 
 
 def constantLike(poly, idx, num):

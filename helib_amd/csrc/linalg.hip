@@ -32,7 +32,11 @@
 //   (o0, o1, o2) = sum_(i<k, j<l) T[j k + i] tensor((a0[i], a1[i]), (b0[j], b1[j]))
 // (src/tableLookup.cpp:261-267: *products[ii] = products1[i]; products[ii]->multiplyBy(products2[j]); and :94-103:
 // products[i].multByConstant(table[i]); out += products[i]), every a read once per four values of j and every table word
-// once per two batch elements.
+// once per two batch elements; and of an inner node of replicateAll's recursion over one digit decomposition
+// (hx_hoisted_mask_fan):
+//   out[t] = A[t] * ctxt + B[t] * keySwitch(sigma_k[t](ctxt)),  t < n
+// (src/replicate.cpp:432-483 and :411-415 over BasicAutomorphPrecon, src/matmul.cpp:48-184), every digit word and key
+// word read once per term, the ciphertext once for all terms, each output written once.
 // The unit reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
 // key-switching matrix's rows, the tables of Z_m^*).
 #include <hip/hip_runtime.h>
@@ -901,6 +905,97 @@ hoisted_sum_kernel(uint64_t* __restrict__ out0, uint64_t* __restrict__ out1, con
       break;
     st_stream1(out0 + row_off + boff[b] + j, mad_reduce(a0[b], q, mu, mu64, k));
     st_stream1(out1 + row_off + boff[b] + j, mad_reduce(a1[b], q, mu, mu64, k));
+  }
+}
+
+// The hoisted masked fan-out (hx_hoisted_mask_fan), hoisted_sum_kernel's sibling with one output pair per term: an inner
+// node of recursiveReplicateDim (src/replicate.cpp:432-483) and its leaf (:411-415) over BasicAutomorphPrecon
+// (src/matmul.cpp:48-184).  Per output row r and term t, with sigma_t the gather by k[t] and A_t, B_t the two masks read
+// at the thread's own index,
+//   out0[t] = A_t (Psp c0) + B_t (Psp sigma_t(c0) + sum_d sigma_t(dig_d) b[t][d])
+//   out1[t] = A_t (Psp c1) + B_t (              sum_d sigma_t(dig_d) a[t][d])
+// on the ciphertext's rows (r < L) and B_t times the sum over d alone on the special rows.
+//
+// Table (device, uint64 words): [0, n) the k[t] (hoisted_perm_kernel's); [n, 2n) and [2n, 3n) the bases of out0[t] and
+// out1[t]; then per output row r and term t five words at 3 n + 5 (r n + t): the address of row r's words of digit 0 in
+// b[t] and in a[t], the words between two digits of that matrix, and the address of the row of A_t and of B_t on the prime
+// of r, bit 0 set when the mask has one row per batch element (0: the constant 1); behind them, at 3 n + 5 rows n + r, Psp
+// modulo the prime of row r.  It is read through the constant address space: the entries are wave-uniform, so they are
+// scalar loads and the branches on them are uniform.
+//
+// The thread shape is hoisted_sum_kernel's: one output coefficient j of one prime row for BP batch elements.  Psp c0[j]
+// and Psp c1[j] are formed once (reduced: they are multiplied again) and serve all n terms.  Per term the thread reads its
+// gather index once, per digit the two key words once and BP digit words at the gathered index, into 128-bit accumulators
+// of 1 + ndig <= MAD_CHUNK products, reduced; then out = A (Psp c) + B inner, two products in a second 128-bit sum,
+// reduced once and stored non-temporally.  No LDS: nothing is shared between threads.
+template <int BP>
+__global__ void __launch_bounds__(256)
+hoisted_mask_fan_kernel(const uint64_t* __restrict__ dig, const uint64_t* __restrict__ c0, const uint64_t* __restrict__ c1,
+                        const uint32_t* __restrict__ perm, ro_u64 tab, int n, int ndig, int L, int nall, int batch, uint32_t N,
+                        MadRows map, const PrimeDev* __restrict__ primes)
+{
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= N)
+    return;
+  const int row = blockIdx.y;
+  const int b0 = blockIdx.z * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t k = pd.k;
+  const size_t rw = (size_t)batch * N;
+  const size_t row_off = (size_t)row * rw;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(b0 + b < batch ? b0 + b : batch - 1) * N;
+  const bool own = row < L;
+  const uint64_t psp = tab[3 * (size_t)n + 5 * (size_t)nall * n + row];
+  uint64_t pc0[BP], pc1[BP];   // Psp c0[j], Psp c1[j]
+#pragma unroll
+  for (int b = 0; b < BP; b++) {
+    pc0[b] = own ? mad_reduce((u128)psp * c0[row_off + boff[b] + j], q, mu, mu64, k) : 0;
+    pc1[b] = own ? mad_reduce((u128)psp * c1[row_off + boff[b] + j], q, mu, mu64, k) : 0;
+  }
+  ro_u64 e = tab + 3 * (size_t)n + 5 * (size_t)row * n;
+  const size_t dstride = (size_t)nall * rw;   // words between two digits of the block
+  for (int t = 0; t < n; t++) {
+    const uint32_t s = perm[(size_t)t * N + j];
+    const uint64_t* kb = reinterpret_cast<const uint64_t*>(e[5 * t]);
+    const uint64_t* ka = reinterpret_cast<const uint64_t*>(e[5 * t + 1]);
+    const size_t kstride = e[5 * t + 2];
+    const uint64_t ae = e[5 * t + 3], be = e[5 * t + 4];
+    const uint64_t* ap = reinterpret_cast<const uint64_t*>(ae & ~(uint64_t)1);
+    const uint64_t* bp = reinterpret_cast<const uint64_t*>(be & ~(uint64_t)1);
+    u128 a0[BP], a1[BP];
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      a0[b] = own ? (u128)psp * c0[row_off + boff[b] + s] : (u128)0;
+      a1[b] = 0;
+    }
+    for (int d = 0; d < ndig; d++) {
+      const uint64_t wb = kb[d * kstride + j], wa = ka[d * kstride + j];
+      const uint64_t* dp = dig + d * dstride + row_off + s;
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        const uint64_t x = dp[boff[b]];
+        a0[b] += (u128)x * wb;
+        a1[b] += (u128)x * wa;
+      }
+    }
+    uint64_t* o0 = reinterpret_cast<uint64_t*>(tab[n + t]) + row_off + j;
+    uint64_t* o1 = reinterpret_cast<uint64_t*>(tab[2 * (size_t)n + t]) + row_off + j;
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      if (b0 + b >= batch)
+        break;
+      const uint64_t am = ap ? ap[((ae & 1) ? boff[b] : 0) + j] : 1;
+      const uint64_t bm = bp ? bp[((be & 1) ? boff[b] : 0) + j] : 1;
+      const u128 r0 = (u128)am * pc0[b] + (u128)bm * mad_reduce(a0[b], q, mu, mu64, k);
+      const u128 r1 = (u128)am * pc1[b] + (u128)bm * mad_reduce(a1[b], q, mu, mu64, k);
+      st_stream1(o0 + boff[b], mad_reduce(r0, q, mu, mu64, k));
+      st_stream1(o1 + boff[b], mad_reduce(r1, q, mu, mu64, k));
+    }
   }
 }
 
@@ -2004,6 +2099,179 @@ extern "C" int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0
   grid.x = (N + 255) / 256;   // one coefficient per thread
   const uint64_t *dg = hxi::poly_rows_read(digits), *p0 = hxi::poly_rows_read(c0), *p1 = hxi::poly_rows_read(c1);
   HX_LAUNCH_W(f.bp != 1, (hx::hoisted_sum_kernel<1>), (hx::hoisted_sum_kernel<4>), grid, st, o0, o1, dg, p0, p1, perm,
+              hx::as_ro(tab.d), n, ndig, L, nall, f.batch, N, f.map, f.primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_hoisted_mask_fan(const hx_poly* digits, const hx_poly* c0, const hx_poly* c1, const uint64_t* k,
+                                   const hx_ksk* const* W, const hx_poly* const* A, const hx_poly* const* B, int n,
+                                   const int* sp_idx, int nsp, hx_poly* const* out0, hx_poly* const* out1)
+{
+  if (!digits || !c0 || !c1 || !k || !W || !out0 || !out1 || (nsp > 0 && !sp_idx) || nsp < 0)
+    return err(HX_ERR_INVALID, "null argument");
+  if (n < 1)
+    return err(HX_ERR_INVALID, "hx_hoisted_mask_fan needs at least one term (n = %d)", n);
+  if (n > hx::MAD_CHUNK)
+    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_mask_fan takes at most %d terms (n = %d)", hx::MAD_CHUNK, n);
+  hx_ctx* ctx = hxi::poly_ctx(c0);
+  if (hxi::poly_ctx(digits) != ctx || hxi::poly_ctx(c1) != ctx)
+    return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  // the frame's rows are the outputs': c0's primes followed by the special primes (set once those are checked)
+  Frame f;
+  RC(f.enter(ctx, "hx_hoisted_mask_fan uploads a table of key rows and cannot be captured in a graph"));
+  RC(f.even("hx_hoisted_mask_fan"));
+  std::vector<hxi::KskView> kv(n);
+  std::vector<const hx_poly*> outs, ins = {digits, c0, c1};
+  for (int t = 0; t < n; t++) {
+    if (!out0[t] || !out1[t])
+      return err(HX_ERR_INVALID, "null output (term %d)", t);
+    if (!W[t])
+      return err(HX_ERR_INVALID, "null key-switching matrix (term %d)", t);
+    hxi::ksk_view(W[t], &kv[t]);
+    if (kv[t].ctx != ctx)
+      return err(HX_ERR_INVALID, "the key-switching matrix of term %d belongs to another context", t);
+    if (hxi::poly_ctx(out0[t]) != ctx || hxi::poly_ctx(out1[t]) != ctx || (A && A[t] && hxi::poly_ctx(A[t]) != ctx) ||
+        (B && B[t] && hxi::poly_ctx(B[t]) != ctx))
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects (term %d)", t);
+    outs.push_back(out0[t]);
+    outs.push_back(out1[t]);
+    if (A && A[t])
+      ins.push_back(A[t]);
+    if (B && B[t])
+      ins.push_back(B[t]);
+  }
+  std::sort(outs.begin(), outs.end());
+  if (std::adjacent_find(outs.begin(), outs.end()) != outs.end())
+    return err(HX_ERR_INVALID, "two outputs are the same poly");
+  for (const hx_poly* p : ins)
+    if (std::binary_search(outs.begin(), outs.end(), p))
+      return err(HX_ERR_INVALID, "an output is also an input or a mask");
+  const uint64_t m = f.v.m;
+  for (int t = 0; t < n; t++)
+    if (hxh::gcd(k[t] % m, m) != 1)
+      return err(HX_ERR_INVALID, "DoubleCRT::automorph: k[%d] = %llu is not in Zm*", t, (unsigned long long)k[t]);
+  RC(shape_of(c0, &f.batch, &f.idx));
+  RC(same_shape(c1, f, "c0 and c1 differ in batch or prime set"));
+  const int L = (int)f.idx.size();
+  if (L == 0)
+    return err(HX_ERR_INVALID, "c0 has no rows");
+  int nprimes = 0;
+  RC(hx_ctx_num_primes(ctx, &nprimes));
+  std::vector<int> all(f.idx);
+  for (int i = 0; i < nsp; i++) {
+    if (sp_idx[i] < 0 || sp_idx[i] >= nprimes || row_of(all.data(), all.size(), sp_idx[i]) >= 0)
+      return err(HX_ERR_INVALID, "special prime %d is not a prime of the context, or is listed twice or among c0's", sp_idx[i]);
+    all.push_back(sp_idx[i]);
+  }
+  RC(f.set_rows(all));
+  const int nall = f.rows;
+  int b2 = 0;
+  std::vector<int> other;
+  RC(shape_of(digits, &b2, &other));
+  if (b2 != f.batch || other.empty() || other.size() % nall != 0)
+    return err(HX_ERR_INVALID, "the digit block differs in batch, or is not a whole number of digits on %d rows", nall);
+  const int ndig = (int)other.size() / nall;
+  for (int d = 0; d < ndig; d++)
+    for (int r = 0; r < nall; r++)
+      if (other[(size_t)d * nall + r] != all[r])
+        return err(HX_ERR_INVALID, "digit rows do not match the ciphertext's primes followed by the special primes");
+  for (const hx_poly* o : outs) {
+    RC(shape_of(o, &b2, &other));
+    if (b2 != f.batch)
+      return err(HX_ERR_INVALID, "an output has batch %d, the operands %d", b2, f.batch);
+  }
+  // wrow[r n + t]: the row of W[t] on the prime of output row r (rows by prime index, the leading ndig digits);
+  // mrow[(2 t + i) nall + r]: the row of A_t (i = 0) or B_t (i = 1) on that prime, mper[2 t + i]: one row per batch element
+  std::vector<int> wrow((size_t)nall * n), mrow((size_t)2 * n * nall, 0), mper((size_t)2 * n, 0);
+  for (int t = 0; t < n; t++) {
+    if (kv[t].ndig < ndig)
+      return err(HX_ERR_INVALID, "W must have as many columns as there are digits (term %d: %d, the block has %d)", t,
+                 kv[t].ndig, ndig);
+    for (int r = 0; r < nall; r++) {
+      const int at = row_of(kv[t].row_idx, kv[t].nrows, all[r]);
+      if (at < 0)
+        return err(HX_ERR_PRIMESET, "No key-switching matrix row for prime %d (term %d)", all[r], t);
+      wrow[(size_t)r * n + t] = at;
+    }
+    for (int i = 0; i < 2; i++) {
+      const hx_poly* mk = i == 0 ? (A ? A[t] : nullptr) : (B ? B[t] : nullptr);
+      if (!mk)
+        continue;
+      int mb = 0;
+      std::vector<int> midx;
+      RC(shape_of(mk, &mb, &midx));
+      if (mb != f.batch && mb != 1)
+        return err(HX_ERR_INVALID, "%s[%d]: batch %d is neither 1 nor %d", i == 0 ? "A" : "B", t, mb, f.batch);
+      mper[2 * (size_t)t + i] = mb == f.batch && f.batch > 1;
+      for (int r = 0; r < nall; r++) {
+        const int at = row_of(midx.data(), midx.size(), all[r]);
+        if (at < 0)
+          return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (%s[%d] has no row for prime %d)",
+                     i == 0 ? "A" : "B", t, all[r]);
+        mrow[(2 * (size_t)t + i) * nall + r] = at;
+      }
+    }
+  }
+  // the inner accumulators take Psp sigma(c0) and ndig products of a digit word by a key word
+  if (ndig + 1 > hx::MAD_CHUNK)
+    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_mask_fan: ndig + 1 = %d products per word, the accumulators take %d", ndig + 1,
+               hx::MAD_CHUNK);
+  const uint32_t N = f.N;
+  const hipStream_t st = f.v.stream;
+  // table (kernels' layout): k[t] mod m; the output bases; per output row and term the two key row bases, the digit stride
+  // and the two mask rows; Psp per row
+  Table tab;
+  RC(tab.acquire(f, 3 * (size_t)n + (size_t)nall * (5 * (size_t)n + 1)));
+  uint32_t* perm = nullptr;
+  RC(tab.perm(f, (size_t)n * N, &perm));
+  // all checks have passed: the outputs take their shape, and one that still shares an input's rows (a lazy hx_poly_copy)
+  // lets go of them before the inputs' addresses are read into the table
+  uint64_t* h = tab.h;
+  for (int t = 0; t < n; t++) {
+    uint64_t *o0 = nullptr, *o1 = nullptr;
+    RC(hxi::poly_rows_reshape(out0[t], all.data(), nall, &o0));
+    RC(hxi::poly_rows_reshape(out1[t], all.data(), nall, &o1));
+    h[t] = k[t] % m;
+    h[n + t] = (uint64_t)(uintptr_t)o0;
+    h[2 * (size_t)n + t] = (uint64_t)(uintptr_t)o1;
+  }
+  const size_t rw = (size_t)f.batch * N;
+  for (int r = 0; r < nall; r++) {
+    uint64_t q = 0;
+    RC(hx_ctx_prime(ctx, all[r], &q, nullptr));
+    for (int t = 0; t < n; t++) {
+      uint64_t* e = h + 3 * (size_t)n + 5 * ((size_t)r * n + t);
+      const size_t at = (size_t)wrow[(size_t)r * n + t] * N;
+      e[0] = (uint64_t)(uintptr_t)(kv[t].d_b + at);
+      e[1] = (uint64_t)(uintptr_t)(kv[t].d_a + at);
+      e[2] = (uint64_t)kv[t].nrows * N;
+      for (int i = 0; i < 2; i++) {
+        const hx_poly* mk = i == 0 ? (A ? A[t] : nullptr) : (B ? B[t] : nullptr);
+        const int per = mper[2 * (size_t)t + i];
+        e[3 + i] = !mk ? 0
+                       : (uint64_t)(uintptr_t)(hxi::poly_rows_read(mk) +
+                                               (size_t)mrow[(2 * (size_t)t + i) * nall + r] * (per ? rw : (size_t)N)) |
+                             (uint64_t)per;
+      }
+    }
+    uint64_t psp = 1 % q;
+    for (int i = 0; i < nsp; i++) {
+      uint64_t qs = 0;
+      RC(hx_ctx_prime(ctx, sp_idx[i], &qs, nullptr));
+      psp = hxh::mulmod(psp, qs % q, q);
+    }
+    h[3 * (size_t)n + 5 * (size_t)nall * n + r] = psp;
+  }
+  RC(tab.commit(st));
+  HX_LAUNCH(hx::hoisted_perm_kernel, dim3((N + 255) / 256, (unsigned)n), dim3(256), 0, st, perm, f.v.d_zms, f.v.d_zms_index, N, m,
+            hx::as_ro(tab.d), (int)f.v.pow2);
+  CK(hipGetLastError());
+  dim3 grid = f.grid();
+  grid.x = (N + 255) / 256;   // one coefficient per thread
+  const uint64_t *dg = hxi::poly_rows_read(digits), *p0 = hxi::poly_rows_read(c0), *p1 = hxi::poly_rows_read(c1);
+  // (BP = 4: DESIGN.md 3.9t has the register budget)
+  HX_LAUNCH_W(f.bp != 1, (hx::hoisted_mask_fan_kernel<1>), (hx::hoisted_mask_fan_kernel<4>), grid, st, dg, p0, p1, perm,
               hx::as_ro(tab.d), n, ndig, L, nall, f.batch, N, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;

@@ -1630,6 +1630,9 @@ class Ctxt:
     # whole lookup through it won every alternated pair against l x hx_mul_add_many and one hx_tensor_sum
     # (tools/bench_table_lookup.py, profiles/table_lookup.json); set it to False to get those calls back
     fuseTableSum = True
+    # fused=None in BasicAutomorphPrecon.automorphMasked: the call sequence until hx_hoisted_mask_fan has been measured
+    # as the faster form in every pair of tools/bench_replicate.py
+    fuseHoistedFan = False
 
     @staticmethod
     def innerProduct(v1, v2, fused=None):
@@ -2112,6 +2115,77 @@ class BasicAutomorphPrecon:
         res.ptxtMag, res.lnRatFactor = mag, c.lnRatFactor + logProd
         res.lnNoise = ln
         res.primeSet = c.primeSet | frozenset(sp)
+        return res
+
+    def automorphMasked(self, ks, A, B, sizes, fused=None):
+        """For every t the ciphertext A[t] * ctxt + B[t] * precon.automorph(ks[t]), as a list of new ciphertexts: an
+        inner node of replicateAll's recursion (src/replicate.cpp:432-483) with both rotations taken from this one digit
+        decomposition.  A[t], B[t]: constants as Ctxt.multByConstant takes them (DoubleCRTs that may live on more
+        primes), None for no product; sizes[t] = (size of A[t], size of B[t]), a negative size being multByConstant's
+        default.  Unfused, per term: r = automorph(k); r.multByConstant(B, sizeB); a = ctxt.clone();
+        a.multByConstant(A, sizeA); a += r.  Fused: one ops.hoistedMaskFan (hx_hoisted_mask_fan) for all terms, with that
+        sequence's bookkeeping float operation for float operation.  It applies where _sumFused applies (BGV, the parts
+        {1, s}, every k with a matrix of its own, no special primes in the operand); otherwise, and with fused=False,
+        the sequence runs.  fused=True insists on a backend with hoistedMaskFan; fused=None follows Ctxt.fuseHoistedFan.
+        Words, lnNoise, primeSet, ptxtSpace, intFactor, ptxtMag and the part handles are the same either way."""
+        c = self.ctxt
+        n = len(ks)
+        A = [None] * n if A is None else list(A)
+        B = [None] * n if B is None else list(B)
+        sizes = [(-1.0, -1.0)] * n if sizes is None else list(sizes)
+        if not len(A) == len(B) == len(sizes) == n:
+            raise ValueError("automorphMasked: one A, one B and one pair of sizes per automorphism")
+        has = hasattr(c.ops, "hoistedMaskFan")
+        if fused and not has:
+            raise RuntimeError("BasicAutomorphPrecon::automorphMasked: fused=True, but this backend has no hoistedMaskFan")
+        if (Ctxt.fuseHoistedFan if fused is None else fused) and has:
+            ret = self._maskedFused(ks, A, B, sizes)
+            if ret is not None:
+                return ret
+        out = []
+        for k, a_t, b_t, (sa, sb) in zip(ks, A, B, sizes):
+            r = self.automorph(k)
+            if b_t is not None:
+                r.multByConstant(b_t, sb)
+            a = c.clone()
+            if a_t is not None:
+                a.multByConstant(a_t, sa)
+            a += r
+            out.append(a)
+        return out
+
+    def _maskedFused(self, ks, A, B, sizes):
+        """automorphMasked's fused form, or None where it does not apply (nothing has been touched then)"""
+        c = self.ctxt
+        ctx = c.context
+        sp = list(ctx.specialPrimes)
+        if ctx.ckks or self.polyDigits is None or set(c.parts) != {"1", "s"} or c.primeSet & frozenset(sp):
+            return None
+        ks = [k % ctx.m for k in ks]
+        if not ks or len(ks) > 256 or any(k == 1 or math.gcd(k, ctx.m) != 1 or c._firstStep(k) != k for k in ks):
+            return None
+        out0, out1 = c.ops.hoistedMaskFan(self.polyDigits, c.parts["1"], c.parts["s"], ks, [c.ksw_auto[k] for k in ks],
+                                          A, B, sp)
+        logProd = ctx.logOfProduct(sorted(sp))
+        defSize = ctx.noiseBoundForMod(c.ptxtSpace, ctx.phim)   # multByConstant's size < 0
+        res = []
+        for t in range(len(ks)):
+            x = Ctxt(ctx, c.ops, c.ksw, c.ksw_ptxtSpace, c.ksw_lnNoise)
+            x.ksw_auto, x.ksw_pow, x.ksw_map, x._like = c.ksw_auto, c.ksw_pow, c.ksw_map, c._like
+            x.ptxtSpace, x.intFactor = c.ptxtSpace, c.intFactor
+            x.parts = {"1": out0[t], "s": out1[t]}
+            sa, sb = sizes[t]
+            lr = self.lnNoise                                   # r = automorph(k)
+            if B[t] is not None:                                # r.multByConstant(B, sizeB)
+                lr = lr + _ln(defSize if sb < 0.0 else sb)
+            la = c.lnNoise                                      # a = ctxt.clone(); a.multByConstant(A, sizeA)
+            if A[t] is not None:
+                la = la + _ln(defSize if sa < 0.0 else sa)
+            la += logProd                                       # a += r: a.modUpToSet, then addCtxt's sums
+            x.ptxtMag, x.lnRatFactor = c.ptxtMag + x.ptxtMag, c.lnRatFactor + logProd
+            x.lnNoise = logaddexp(la, lr)
+            x.primeSet = c.primeSet | frozenset(sp)
+            res.append(x)
         return res
 
 

@@ -746,3 +746,7 @@ class HxBackend:
     def hoistedSum(self, digits, c0, c1, ks, Ws, special):
         """capi.hoistedAutomorphSum: the hoisted sum of traceMap in one device call"""
         return self.hx.hoistedAutomorphSum(digits, c0, c1, ks, Ws, special)
+
+    def hoistedMaskFan(self, digits, c0, c1, ks, Ws, A, B, special):
+        """capi.hoistedMaskFan: the masked, hoisted node of replicateAll in one device call"""
+        return self.hx.hoistedMaskFan(digits, c0, c1, ks, Ws, A, B, special)

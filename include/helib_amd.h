@@ -740,6 +740,38 @@ int hx_table_tensor_sum(hx_poly* o0, hx_poly* o1, hx_poly* o2, const hx_poly* co
 int hx_hoisted_automorph_sum(const hx_poly* digits, const hx_poly* c0, const hx_poly* c1, const uint64_t* k,
                              const hx_ksk* const* W, int n, const int* sp_idx, int nsp, hx_poly* out0, hx_poly* out1);
 
+/* The hoisted, masked fan-out of replicateAll: an inner node of recursiveReplicateDim (src/replicate.cpp:432-483:
+ *   masked = ctxt * M; left = masked + rotate(masked, +e); rest = ctxt - masked; right = rest + rotate(rest, -e))
+ * and its leaf (:411-415), with both rotations taken from ONE digit decomposition of ctxt (BasicAutomorphPrecon,
+ * src/matmul.cpp:48-184): since sigma_k(ctxt M) = sigma_k(ctxt) sigma_k(M), left = M ctxt + sigma_k+(M) rho^+e(ctxt) and
+ * right = (1 - M) ctxt + sigma_k-(1 - M) rho^-e(ctxt).  digits, c0, c1, k, W, sp_idx are as in hx_hoisted_automorph_sum;
+ * A[t], B[t] are masks in evaluation form, read at the word's own index (not gathered), of batch 1 (broadcast) or the
+ * operands' batch, on any superset of the outputs' primes in any order (rows are matched by prime index); a null A[t] or
+ * B[t], or a null array A or B, stands for the constant 1.  For every term t < n, per row, with Psp the product of the
+ * special primes modulo the row's prime and sigma_t the gather of hx_automorph by k[t]:
+ *   ctxt rows:     out0[t] = A_t (Psp c0) + B_t (Psp sigma_t(c0) + sum_d sigma_t(dig_d) b[t][d])
+ *                  out1[t] = A_t (Psp c1) + B_t (                  sum_d sigma_t(dig_d) a[t][d])
+ *   special rows:  out0[t] = B_t sum_d sigma_t(dig_d) b[t][d],  out1[t] likewise with a[t][d]
+ * The 2 n outputs end up on the primes of c0 followed by sp_idx; they are overwritten, not read, pairwise distinct, and
+ * none is an input or a mask; one that still shares rows with another poly (a lazy hx_poly_copy) lets go of them first.
+ * Every word written is canonical in [0, q) and equals, word for word, what this sequence of calls leaves per term -- a
+ * copy and hx_automorph of the digit block and of c0, hx_add_primes_and_scale, a zero part, hx_key_switch_digits, two
+ * hx_mul by B_t, copies of c0 and c1 times A_t, hx_add_primes_and_scale, two hx_add -- since all of it is exact
+ * arithmetic modulo the row's prime.  A word is two 128-bit sums: 1 + ndig <= 256 products of residues below 2^60,
+ * reduced, then two products, reduced (256 (2^60 - 2)^2 + 2^60 < 2^128).  Null required arguments, n < 1, a k[t]
+ * outside Z_m^*, a poly or matrix of another context, mismatched batches or prime sets (as hx_hoisted_automorph_sum
+ * refuses them), a mask whose batch is neither 1 nor the operands', aliased outputs, an output among the inputs or
+ * masks and a W[t] with fewer digits than the block are HX_ERR_INVALID; a prime that a W[t] or a mask lacks is
+ * HX_ERR_PRIMESET; n > 256, more than 160 rows and an odd phi(m) are HX_ERR_UNSUPPORTED; every check comes before
+ * anything is touched, so a refused call writes nothing.  The call uploads a table of key-row addresses, so it cannot be
+ * recorded: under an open graph capture it returns HX_ERR_UNSUPPORTED before touching the device.  Asynchronous on the
+ * context's stream.  Per term the sequence makes about 3 ndig + 24 passes over a part in some fifteen launches; this call
+ * reads every digit word and key word once per term, c0 and c1 once for all terms (and c0 once more per term at the
+ * gathered index), the masks once, and writes each output once, in two launches. */
+int hx_hoisted_mask_fan(const hx_poly* digits, const hx_poly* c0, const hx_poly* c1, const uint64_t* k,
+                        const hx_ksk* const* W, const hx_poly* const* A, const hx_poly* const* B, int n,
+                        const int* sp_idx, int nsp, hx_poly* const* out0, hx_poly* const* out1);
+
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
  * host pointers, synchronous, in-place allowed.  FFTFwd / FFTRev1 are what
