@@ -15,7 +15,8 @@ below derive from them and restate the reference's masked paths.
                       native `dim` is the base class's
 
 Out of scope, refused with a message that says so: MatMulFullExec over a hypercube with a non-native dimension
-(src/matmul.cpp:2157-2250), BlockMatMul*, p^r with r > 1 (integer slots mod p^r: helib_amd.bgv_pr, which derives from
+(src/matmul.cpp:2157-2250; this module's class keeps refusing, the product is helib_amd.matmul_full.MatMulFullExec),
+BlockMatMul*, p^r with r > 1 (integer slots mod p^r: helib_amd.bgv_pr, which derives from
 the class below).  Nothing here imports oracle/."""
 import contextlib
 import os
@@ -346,7 +347,7 @@ class MatMul1DExec(bgv_matmul.MatMul1DExec):
 
 class MatMulFullExec(bgv_matmul.MatMulFullExec):
     """bgv_matmul.MatMulFullExec; a hypercube with a non-native dimension is refused: the reference's recursion through
-    the masked rotations (src/matmul.cpp:2157-2250) is not built"""
+    the masked rotations (src/matmul.cpp:2157-2250) is not built here -- helib_amd.matmul_full.MatMulFullExec has it"""
 
     def __init__(self, ea, mat, minimal=False, device_diagonals=None):
         bgv_matmul._modPOnly(ea, "MatMulFullExec")

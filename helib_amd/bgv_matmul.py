@@ -256,6 +256,8 @@ class MatMulFullExec:
     """MatMulFullExec (src/matmul.cpp:2030-2273): one MatMul1DExec along the last dimension of `dims` per setting of
     the offsets in the dimensions before it"""
 
+    exec1D = MatMul1DExec      # the product along the last dimension (helib_amd.matmul_full: one that takes a non-native one)
+
     def __init__(self, ea, mat, minimal=False, device_diagonals=None):
         _modPOnly(ea, "MatMulFullExec")
         mat = mat if isinstance(mat, MatMulFull) else MatMulFull(ea, mat)
@@ -269,8 +271,8 @@ class MatMulFullExec:
 
         def rec(d, off):
             if d >= nd - 1:
-                self.transforms.append(MatMul1DExec(ea, _FullHelper(mat, off, self.dims[d]), minimal,
-                                                    device_diagonals=device_diagonals))
+                self.transforms.append(self.exec1D(ea, _FullHelper(mat, off, self.dims[d]), minimal,
+                                                   device_diagonals=device_diagonals))
                 return
             for o in range(ea.sizeOfDimension(self.dims[d])):
                 off1 = list(off)

@@ -61,7 +61,7 @@ SYMBOLS = [
     "hx_ckks_encode", "hx_ckks_embed", "hx_ckks_decode",
     "hx_mul_add_many", "hx_poly_extract", "hx_mask_split", "hx_mask_blend", "hx_scaled_sub",
     "hx_lin_comb", "hx_mul_add_circulant", "hx_hoisted_automorph_sum", "hx_mask_fan", "hx_tensor_sum",
-    "hx_table_tensor_sum", "hx_hoisted_mask_fan",
+    "hx_table_tensor_sum", "hx_hoisted_mask_fan", "hx_hoisted_blend",
     "hx_bgv_slots_create", "hx_bgv_slots_destroy", "hx_bgv_slots_info", "hx_bgv_encode", "hx_bgv_decode", "hx_bgv_embed",
     "hx_bgv_matrix_create", "hx_bgv_matrix_destroy", "hx_bgv_encode_diagonals",
     "hx_bgv_crt_create", "hx_bgv_crt_destroy", "hx_bgv_crt_info", "hx_bgv_crt_encode", "hx_bgv_crt_decode", "hx_bgv_crt_embed",
@@ -175,6 +175,7 @@ def lib():
             "hx_mul_add_circulant": [vp, vp, ip, vp, vp, vp, ip],
             "hx_hoisted_automorph_sum": [vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
             "hx_hoisted_mask_fan": [vp, vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
+            "hx_hoisted_blend": [vp, vp, vp, vp, vp, vp, vp, vp, vp, ip, vp, ip, vp, vp],
             "hx_bgv_slots_create": [vp, u64, vp], "hx_bgv_slots_destroy": [vp],
             "hx_bgv_slots_info": [vp, vp, vp, vp, vp, vp],
             "hx_bgv_encode": [vp, vp, ip, ip, u64, vp, vp],
@@ -1291,6 +1292,32 @@ def hoistedMaskFan(digits, c0, c1, ks, Ws, A, B, special):
         return (C.c_void_p * n)(*[p.h if p is not None else None for p in ps]) if ps is not None else None
     _chk(lib().hx_hoisted_mask_fan(digits.h, c0.h, c1.h, _p(ka), arr(Ws), arr(A), arr(B), n, _p(sp), len(sp), arr(out0),
                                    arr(out1)))
+    return out0, out1
+
+
+def hoistedBlend(digA, a0, a1, digB, b0, b1, ks, Ws, masks, special):
+    """For every t: M * X + Y - M * Y with X the image of (a0, a1) and Y the image of (b0, b1) under the automorphism
+    ks[t], each key-switched by Ws[t] from its own digit block (digA of a1, digB of b1), M = masks[t], in one pass
+    (hx_hoisted_blend): the inner step of MatMulFullExec::rec_mul along a non-native dimension (src/matmul.cpp:2174-2204)
+    over two BasicAutomorphPrecon.  masks: one DoubleCRT in evaluation form per automorphism (batch 1 or the operands').
+    -> (list of out0, list of out1), new DoubleCRTs on the primes of a0 followed by special."""
+    if any(x is None for x in (digA, a0, a1, digB, b0, b1, ks, Ws, masks)):
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedBlend: both digit blocks, both part pairs, ks, Ws and masks are required")
+    n = len(ks)
+    if n < 1 or len(Ws) != n:
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedBlend takes at least one automorphism, and one matrix for each")
+    if len(masks) != n or any(mk is None for mk in masks):
+        raise InvalidArgument(HX_ERR_INVALID, "hoistedBlend: masks holds one mask per automorphism")
+    ka = np.array([int(k) for k in ks], dtype=np.uint64)
+    sp = _i32(list(special))
+    idx = a0.getIndexSet() + [int(i) for i in sp]
+    out0 = [DoubleCRT(a0.context, idx, a0.batch, zero=False) for _ in range(n)]
+    out1 = [DoubleCRT(a0.context, idx, a0.batch, zero=False) for _ in range(n)]
+
+    def arr(ps):
+        return (C.c_void_p * n)(*[p.h for p in ps])
+    _chk(lib().hx_hoisted_blend(digA.h, a0.h, a1.h, digB.h, b0.h, b1.h, _p(ka), arr(Ws), arr(masks), n, _p(sp), len(sp),
+                                arr(out0), arr(out1)))
     return out0, out1
 
 

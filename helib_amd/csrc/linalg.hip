@@ -36,7 +36,11 @@
 // (hx_hoisted_mask_fan):
 //   out[t] = A[t] * ctxt + B[t] * keySwitch(sigma_k[t](ctxt)),  t < n
 // (src/replicate.cpp:432-483 and :411-415 over BasicAutomorphPrecon, src/matmul.cpp:48-184), every digit word and key
-// word read once per term, the ciphertext once for all terms, each output written once.
+// word read once per term, the ciphertext once for all terms, each output written once; and of the inner step of
+// MatMulFullExec's recursion along a non-native dimension over two digit decompositions (hx_hoisted_blend):
+//   out[t] = M[t] * X + Y - M[t] * Y,  X = keySwitch(sigma_k[t](ctxt)),  Y = keySwitch(sigma_k[t](ctxt1)),  t < n
+// (src/matmul.cpp:2174-2204), every digit word of both blocks and every key word read once per term, each output written
+// once.
 // The unit reaches the context only through ckks_bridge.h (stream, lock, a state slot, the prime table, a poly's rows, a
 // key-switching matrix's rows, the tables of Z_m^*).
 #include <hip/hip_runtime.h>
@@ -995,6 +999,103 @@ hoisted_mask_fan_kernel(const uint64_t* __restrict__ dig, const uint64_t* __rest
       const u128 r1 = (u128)am * pc1[b] + (u128)bm * mad_reduce(a1[b], q, mu, mu64, k);
       st_stream1(o0 + boff[b], mad_reduce(r0, q, mu, mu64, k));
       st_stream1(o1 + boff[b], mad_reduce(r1, q, mu, mu64, k));
+    }
+  }
+}
+
+// The hoisted blend (hx_hoisted_blend), hoisted_mask_fan_kernel's sibling with two operands: the inner step of
+// MatMulFullExec::rec_mul along a non-native dimension (src/matmul.cpp:2174-2204) over two BasicAutomorphPrecon
+// (:48-184), of ctxt (digA, a0) and of ctxt1 = ctxt moved by g^(-ord) (digB, b0).  Per output row r and term t, with
+// sigma_t the gather by k[t] and M_t the mask read at the thread's own index,
+//   out0[t] = M_t X0 + Y0 - M_t Y0,  X0 = Psp sigma_t(a0) + sum_d sigma_t(digA_d) b[t][d],  Y0 likewise from b0, digB
+//   out1[t] = M_t X1 + Y1 - M_t Y1,  X1 =                   sum_d sigma_t(digA_d) a[t][d],  Y1 likewise from digB
+// the Psp terms on the ciphertext's rows (r < L) alone.  Both operands meet the same key words and the same mask word,
+// so the blend is taken on the operand words, z = M x + y - M y (reduced: it is multiplied again), before the products:
+//   out0[t] = Psp z(sigma_t(a0), sigma_t(b0)) + sum_d z(sigma_t(digA_d), sigma_t(digB_d)) b[t][d]
+// which is the same residue, all of it being exact arithmetic modulo the row's prime.  One accumulator pair per batch
+// element instead of one per operand, 3 + ndig reductions per output pair instead of 6, and each key word read once.
+//
+// Table (device, uint64 words): [0, n) the k[t] (hoisted_perm_kernel's); [n, 2n) and [2n, 3n) the bases of out0[t] and
+// out1[t]; then per output row r and term t four words at 3 n + 4 (r n + t): the address of row r's words of digit 0 in
+// b[t] and in a[t], the words between two digits of that matrix, and the address of the row of M_t on the prime of r, bit
+// 0 set when the mask has one row per batch element; behind them, at 3 n + 4 rows n + r, Psp modulo the prime of row r.
+// It is read through the constant address space: the entries are wave-uniform, so they are scalar loads.
+//
+// The thread shape is hoisted_mask_fan_kernel's: one output coefficient j of one prime row for BP batch elements.  Per
+// term the thread reads its gather index once and BP mask words, per digit the two key words once and 2 BP digit words at
+// the gathered index, into 128-bit accumulators of 1 + ndig <= MAD_CHUNK products, reduced once and stored
+// non-temporally.  No LDS: nothing is shared between threads.  (The second launch bound asks for hoisted_mask_fan_kernel's
+// five waves per SIMD: BP = 4 is 96 VGPRs with it and 98, four waves, without; no scratch either way.)
+template <int BP>
+__global__ void __launch_bounds__(256, 5)
+hoisted_blend_kernel(const uint64_t* __restrict__ digA, const uint64_t* __restrict__ digB, const uint64_t* __restrict__ a0,
+                     const uint64_t* __restrict__ b0, const uint32_t* __restrict__ perm, ro_u64 tab, int n, int ndig, int L,
+                     int nall, int batch, uint32_t N, MadRows map, const PrimeDev* __restrict__ primes)
+{
+  // The 2 BP (ndig + 1) rows a workgroup gathers from are those of every workgroup with its (y, z); workgroups go round
+  // the 8 XCDs by their linear index, x fastest, so unchanged each row would be fetched into all 8 L2s.  The remap (a
+  // bijection for any grid) gives each XCD a contiguous run of (x, y, z): a row's workgroups share one L2.
+  const uint32_t gx = gridDim.x, gy = gridDim.y, nwg = gx * gy * gridDim.z;
+  const uint32_t lin = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+  const uint32_t xcd = lin % 8, per = nwg / 8, rem = nwg % 8;
+  const uint32_t wg = (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + lin / 8;
+  const uint32_t j = (wg % gx) * blockDim.x + threadIdx.x;
+  if (j >= N)
+    return;
+  const int row = (wg / gx) % gy;
+  const int bb = (wg / (gx * gy)) * BP;
+  const PrimeDev pd = primes[map.p[row]];
+  const uint64_t q = pd.q, mu = pd.mu, mu64 = pd.mu64;
+  const uint32_t k = pd.k;
+  const size_t rw = (size_t)batch * N;
+  const size_t row_off = (size_t)row * rw;
+  // batch elements past the end repeat the last one (loads of valid rows; their stores are skipped)
+  size_t boff[BP];
+#pragma unroll
+  for (int b = 0; b < BP; b++)
+    boff[b] = (size_t)(bb + b < batch ? bb + b : batch - 1) * N;
+  const bool own = row < L;
+  const uint64_t psp = tab[3 * (size_t)n + 4 * (size_t)nall * n + row];
+  ro_u64 e = tab + 3 * (size_t)n + 4 * (size_t)row * n;
+  const size_t dstride = (size_t)nall * rw;   // words between two digits of a block
+  // m x + y - m y = m (x + q - y) + y <= (q - 1)(2 q - 1) + q - 1 < 2 q^2 for canonical words: red128_wide's domain
+  // (below 8 q^2), a third of mad_reduce's multiplies; so is the sum of 1 + ndig <= 8 products (wave-uniform branch)
+  auto blend = [&](uint64_t x, uint64_t y, uint64_t m) { return red128_wide((u128)m * (x + q - y) + y, q, mu, k); };
+  const bool few = ndig + 1 <= 8;
+  auto reduce = [&](u128 x) { return few ? red128_wide(x, q, mu, k) : mad_reduce(x, q, mu, mu64, k); };
+  for (int t = 0; t < n; t++) {
+    const uint32_t s = perm[(size_t)t * N + j];
+    const uint64_t* kb = reinterpret_cast<const uint64_t*>(e[4 * t]);
+    const uint64_t* ka = reinterpret_cast<const uint64_t*>(e[4 * t + 1]);
+    const size_t kstride = e[4 * t + 2];
+    const uint64_t me = e[4 * t + 3];
+    const uint64_t* mp = reinterpret_cast<const uint64_t*>(me & ~(uint64_t)1) + j;
+    uint64_t mk[BP];
+    u128 r0[BP], r1[BP];
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      mk[b] = mp[(me & 1) ? boff[b] : 0];
+      r0[b] = own ? (u128)psp * blend(a0[row_off + boff[b] + s], b0[row_off + boff[b] + s], mk[b]) : (u128)0;
+      r1[b] = 0;
+    }
+    for (int d = 0; d < ndig; d++) {
+      const uint64_t wb = kb[d * kstride + j], wa = ka[d * kstride + j];
+      const size_t at = d * dstride + row_off + s;
+#pragma unroll
+      for (int b = 0; b < BP; b++) {
+        const uint64_t z = blend(digA[at + boff[b]], digB[at + boff[b]], mk[b]);
+        r0[b] += (u128)z * wb;
+        r1[b] += (u128)z * wa;
+      }
+    }
+    uint64_t* o0 = reinterpret_cast<uint64_t*>(tab[n + t]) + row_off + j;
+    uint64_t* o1 = reinterpret_cast<uint64_t*>(tab[2 * (size_t)n + t]) + row_off + j;
+#pragma unroll
+    for (int b = 0; b < BP; b++) {
+      if (bb + b >= batch)
+        break;
+      st_stream1(o0 + boff[b], reduce(r0[b]));
+      st_stream1(o1 + boff[b], reduce(r1[b]));
     }
   }
 }
@@ -2272,6 +2373,175 @@ extern "C" int hx_hoisted_mask_fan(const hx_poly* digits, const hx_poly* c0, con
   const uint64_t *dg = hxi::poly_rows_read(digits), *p0 = hxi::poly_rows_read(c0), *p1 = hxi::poly_rows_read(c1);
   // (BP = 4: DESIGN.md 3.9t has the register budget)
   HX_LAUNCH_W(f.bp != 1, (hx::hoisted_mask_fan_kernel<1>), (hx::hoisted_mask_fan_kernel<4>), grid, st, dg, p0, p1, perm,
+              hx::as_ro(tab.d), n, ndig, L, nall, f.batch, N, f.map, f.primes);
+  CK(hipGetLastError());
+  return HX_OK;
+}
+
+extern "C" int hx_hoisted_blend(const hx_poly* digA, const hx_poly* a0, const hx_poly* a1, const hx_poly* digB,
+                                const hx_poly* b0, const hx_poly* b1, const uint64_t* k, const hx_ksk* const* W,
+                                const hx_poly* const* M, int n, const int* sp_idx, int nsp, hx_poly* const* out0,
+                                hx_poly* const* out1)
+{
+  if (!digA || !a0 || !a1 || !digB || !b0 || !b1 || !k || !W || !M || !out0 || !out1 || (nsp > 0 && !sp_idx) || nsp < 0)
+    return err(HX_ERR_INVALID, "null argument");
+  if (n < 1)
+    return err(HX_ERR_INVALID, "hx_hoisted_blend needs at least one term (n = %d)", n);
+  if (n > hx::MAD_CHUNK)
+    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_blend takes at most %d terms (n = %d)", hx::MAD_CHUNK, n);
+  hx_ctx* ctx = hxi::poly_ctx(a0);
+  for (const hx_poly* p : {digA, a1, digB, b0, b1})
+    if (hxi::poly_ctx(p) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects");
+  // the frame's rows are the outputs': a0's primes followed by the special primes (set once those are checked)
+  Frame f;
+  RC(f.enter(ctx, "hx_hoisted_blend uploads a table of key rows and cannot be captured in a graph"));
+  RC(f.even("hx_hoisted_blend"));
+  std::vector<hxi::KskView> kv(n);
+  std::vector<const hx_poly*> outs, ins = {digA, a0, a1, digB, b0, b1};
+  for (int t = 0; t < n; t++) {
+    if (!out0[t] || !out1[t])
+      return err(HX_ERR_INVALID, "null output (term %d)", t);
+    if (!W[t])
+      return err(HX_ERR_INVALID, "null key-switching matrix (term %d)", t);
+    if (!M[t])
+      return err(HX_ERR_INVALID, "null mask (term %d)", t);
+    hxi::ksk_view(W[t], &kv[t]);
+    if (kv[t].ctx != ctx)
+      return err(HX_ERR_INVALID, "the key-switching matrix of term %d belongs to another context", t);
+    if (hxi::poly_ctx(out0[t]) != ctx || hxi::poly_ctx(out1[t]) != ctx || hxi::poly_ctx(M[t]) != ctx)
+      return err(HX_ERR_INVALID, "DoubleCRT::Op: incompatible objects (term %d)", t);
+    outs.push_back(out0[t]);
+    outs.push_back(out1[t]);
+    ins.push_back(M[t]);
+  }
+  std::sort(outs.begin(), outs.end());
+  if (std::adjacent_find(outs.begin(), outs.end()) != outs.end())
+    return err(HX_ERR_INVALID, "two outputs are the same poly");
+  for (const hx_poly* p : ins)
+    if (std::binary_search(outs.begin(), outs.end(), p))
+      return err(HX_ERR_INVALID, "an output is also an input or a mask");
+  const uint64_t m = f.v.m;
+  for (int t = 0; t < n; t++)
+    if (hxh::gcd(k[t] % m, m) != 1)
+      return err(HX_ERR_INVALID, "DoubleCRT::automorph: k[%d] = %llu is not in Zm*", t, (unsigned long long)k[t]);
+  RC(shape_of(a0, &f.batch, &f.idx));
+  RC(same_shape(a1, f, "a0 and a1 differ in batch or prime set"));
+  RC(same_shape(b0, f, "the two operands differ in batch or prime set"));
+  RC(same_shape(b1, f, "the two operands differ in batch or prime set"));
+  const int L = (int)f.idx.size();
+  if (L == 0)
+    return err(HX_ERR_INVALID, "a0 has no rows");
+  int nprimes = 0;
+  RC(hx_ctx_num_primes(ctx, &nprimes));
+  std::vector<int> all(f.idx);
+  for (int i = 0; i < nsp; i++) {
+    if (sp_idx[i] < 0 || sp_idx[i] >= nprimes || row_of(all.data(), all.size(), sp_idx[i]) >= 0)
+      return err(HX_ERR_INVALID, "special prime %d is not a prime of the context, or is listed twice or among a0's", sp_idx[i]);
+    all.push_back(sp_idx[i]);
+  }
+  RC(f.set_rows(all));
+  const int nall = f.rows;
+  int b2 = 0, ndig = 0;
+  std::vector<int> other;
+  for (int w = 0; w < 2; w++) {
+    RC(shape_of(w == 0 ? digA : digB, &b2, &other));
+    if (b2 != f.batch || other.empty() || other.size() % nall != 0)
+      return err(HX_ERR_INVALID, "the digit block differs in batch, or is not a whole number of digits on %d rows", nall);
+    if (w == 1 && (int)other.size() != ndig * nall)
+      return err(HX_ERR_INVALID, "the two digit blocks differ in their number of digits (%d and %d)", ndig,
+                 (int)other.size() / nall);
+    ndig = (int)other.size() / nall;
+    for (int d = 0; d < ndig; d++)
+      for (int r = 0; r < nall; r++)
+        if (other[(size_t)d * nall + r] != all[r])
+          return err(HX_ERR_INVALID, "digit rows do not match the ciphertext's primes followed by the special primes");
+  }
+  for (const hx_poly* o : outs) {
+    RC(shape_of(o, &b2, &other));
+    if (b2 != f.batch)
+      return err(HX_ERR_INVALID, "an output has batch %d, the operands %d", b2, f.batch);
+  }
+  // wrow[r n + t]: the row of W[t] on the prime of output row r (rows by prime index, the leading ndig digits);
+  // mrow[t nall + r]: the row of M_t on that prime, mper[t]: one row per batch element
+  std::vector<int> wrow((size_t)nall * n), mrow((size_t)n * nall, 0), mper(n, 0);
+  for (int t = 0; t < n; t++) {
+    if (kv[t].ndig < ndig)
+      return err(HX_ERR_INVALID, "W must have as many columns as there are digits (term %d: %d, the block has %d)", t,
+                 kv[t].ndig, ndig);
+    for (int r = 0; r < nall; r++) {
+      const int at = row_of(kv[t].row_idx, kv[t].nrows, all[r]);
+      if (at < 0)
+        return err(HX_ERR_PRIMESET, "No key-switching matrix row for prime %d (term %d)", all[r], t);
+      wrow[(size_t)r * n + t] = at;
+    }
+    int mb = 0;
+    std::vector<int> midx;
+    RC(shape_of(M[t], &mb, &midx));
+    if (mb != f.batch && mb != 1)
+      return err(HX_ERR_INVALID, "M[%d]: batch %d is neither 1 nor %d", t, mb, f.batch);
+    mper[t] = mb == f.batch && f.batch > 1;
+    for (int r = 0; r < nall; r++) {
+      const int at = row_of(midx.data(), midx.size(), all[r]);
+      if (at < 0)
+        return err(HX_ERR_PRIMESET, "DoubleCRT::Op: incompatible index sets (M[%d] has no row for prime %d)", t, all[r]);
+      mrow[(size_t)t * nall + r] = at;
+    }
+  }
+  // the accumulators take Psp times the blended word of the 1-part and ndig products of a blended digit word by a key word
+  if (ndig + 1 > hx::MAD_CHUNK)
+    return err(HX_ERR_UNSUPPORTED, "hx_hoisted_blend: ndig + 1 = %d products per word, the accumulators take %d", ndig + 1,
+               hx::MAD_CHUNK);
+  const uint32_t N = f.N;
+  const hipStream_t st = f.v.stream;
+  // table (kernels' layout): k[t] mod m; the output bases; per output row and term the two key row bases, the digit stride
+  // and the mask row; Psp per row
+  Table tab;
+  RC(tab.acquire(f, 3 * (size_t)n + (size_t)nall * (4 * (size_t)n + 1)));
+  uint32_t* perm = nullptr;
+  RC(tab.perm(f, (size_t)n * N, &perm));
+  // all checks have passed: the outputs take their shape, and one that still shares an input's rows (a lazy hx_poly_copy)
+  // lets go of them before the inputs' addresses are read into the table
+  uint64_t* h = tab.h;
+  for (int t = 0; t < n; t++) {
+    uint64_t *o0 = nullptr, *o1 = nullptr;
+    RC(hxi::poly_rows_reshape(out0[t], all.data(), nall, &o0));
+    RC(hxi::poly_rows_reshape(out1[t], all.data(), nall, &o1));
+    h[t] = k[t] % m;
+    h[n + t] = (uint64_t)(uintptr_t)o0;
+    h[2 * (size_t)n + t] = (uint64_t)(uintptr_t)o1;
+  }
+  const size_t rw = (size_t)f.batch * N;
+  for (int r = 0; r < nall; r++) {
+    uint64_t q = 0;
+    RC(hx_ctx_prime(ctx, all[r], &q, nullptr));
+    for (int t = 0; t < n; t++) {
+      uint64_t* e = h + 3 * (size_t)n + 4 * ((size_t)r * n + t);
+      const size_t at = (size_t)wrow[(size_t)r * n + t] * N;
+      e[0] = (uint64_t)(uintptr_t)(kv[t].d_b + at);
+      e[1] = (uint64_t)(uintptr_t)(kv[t].d_a + at);
+      e[2] = (uint64_t)kv[t].nrows * N;
+      e[3] = (uint64_t)(uintptr_t)(hxi::poly_rows_read(M[t]) + (size_t)mrow[(size_t)t * nall + r] * (mper[t] ? rw : (size_t)N)) |
+             (uint64_t)mper[t];
+    }
+    uint64_t psp = 1 % q;
+    for (int i = 0; i < nsp; i++) {
+      uint64_t qs = 0;
+      RC(hx_ctx_prime(ctx, sp_idx[i], &qs, nullptr));
+      psp = hxh::mulmod(psp, qs % q, q);
+    }
+    h[3 * (size_t)n + 4 * (size_t)nall * n + r] = psp;
+  }
+  RC(tab.commit(st));
+  HX_LAUNCH(hx::hoisted_perm_kernel, dim3((N + 255) / 256, (unsigned)n), dim3(256), 0, st, perm, f.v.d_zms, f.v.d_zms_index, N, m,
+            hx::as_ro(tab.d), (int)f.v.pow2);
+  CK(hipGetLastError());
+  dim3 grid = f.grid();
+  grid.x = (N + 255) / 256;   // one coefficient per thread
+  const uint64_t *da = hxi::poly_rows_read(digA), *db = hxi::poly_rows_read(digB);
+  const uint64_t *pa = hxi::poly_rows_read(a0), *pb = hxi::poly_rows_read(b0);
+  // (BP = 4: DESIGN.md 3.9u has the register budget; a1 and b1 are checked, not read -- the key switch replaces them)
+  HX_LAUNCH_W(f.bp != 1, (hx::hoisted_blend_kernel<1>), (hx::hoisted_blend_kernel<4>), grid, st, da, db, pa, pb, perm,
               hx::as_ro(tab.d), n, ndig, L, nall, f.batch, N, f.map, f.primes);
   CK(hipGetLastError());
   return HX_OK;

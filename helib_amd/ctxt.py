@@ -1633,6 +1633,11 @@ class Ctxt:
     # fused=None in BasicAutomorphPrecon.automorphMasked: the call sequence until hx_hoisted_mask_fan has been measured
     # as the faster form in every pair of tools/bench_replicate.py
     fuseHoistedFan = False
+    # fused=None in automorphBlend (and so in matmul_full.MatMulFullExec.mul): one hx_hoisted_blend wherever it applies.
+    # True because the kernel won every alternated pair against the sequence with hx_mask_blend, in the stage alone and
+    # in the whole product, with the same words (tools/bench_matmul_full.py, profiles/matmul_full.json); set
+    # it to False to get the sequence back
+    fuseHoistedBlend = True
 
     @staticmethod
     def innerProduct(v1, v2, fused=None):
@@ -2187,6 +2192,80 @@ class BasicAutomorphPrecon:
             x.primeSet = c.primeSet | frozenset(sp)
             res.append(x)
         return res
+
+
+def automorphBlend(pre, pre1, ks, masks, sizes, fused=None):
+    """For every t the ciphertext m * pre.automorph(k) + pre1.automorph(k) - m * pre1.automorph(k), k = ks[t], m =
+    masks[t], as a list of new ciphertexts: the inner step of MatMulFullExec::rec_mul along a non-native dimension
+    (src/matmul.cpp:2186-2200) over the two BasicAutomorphPrecon of ctxt and of ctxt moved by g^(-ord).  masks[t]: a
+    constant as Ctxt.multByConstant takes it (a DoubleCRT that may live on more primes); sizes[t]: its size, negative for
+    multByConstant's default.  Unfused, per term: tmp = pre.automorph(k); tmp1 = pre1.automorph(k);
+    tmp.multByConstant(m, sz); tmp += tmp1; tmp1.multByConstant(m, sz); tmp -= tmp1.  Fused: one ops.hoistedBlend
+    (hx_hoisted_blend) for all terms, with that sequence's bookkeeping float operation for float operation.  It applies
+    to two BGV precons with digits and the parts {1, s} on one prime set without special primes, with the same digit
+    split, ptxtSpace and intFactor (at p > 2 the key switch that made pre1's ciphertext can leave another intFactor, and
+    addCtxt then rescales), every k other than 1 with a matrix of its own, n <= 256; otherwise, and with fused=False, the
+    sequence runs.  fused=True insists on a backend with hoistedBlend; fused=None follows Ctxt.fuseHoistedBlend.  Words,
+    lnNoise, primeSet, ptxtSpace, intFactor, ptxtMag and the part handles are the same either way."""
+    n = len(ks)
+    masks, sizes = list(masks), [-1.0] * n if sizes is None else list(sizes)
+    if not len(masks) == len(sizes) == n or any(mk is None for mk in masks):
+        raise ValueError("automorphBlend: one mask and one size per automorphism")
+    c = pre.ctxt
+    has = hasattr(c.ops, "hoistedBlend")
+    if fused and not has:
+        raise RuntimeError("automorphBlend: fused=True, but this backend has no hoistedBlend")
+    if (Ctxt.fuseHoistedBlend if fused is None else fused) and has:
+        ret = _blendFused(pre, pre1, ks, masks, sizes)
+        if ret is not None:
+            return ret
+    out = []
+    for k, mk, sz in zip(ks, masks, sizes):
+        tmp, tmp1 = pre.automorph(k), pre1.automorph(k)
+        tmp.multByConstant(mk, sz)
+        tmp += tmp1
+        tmp1.multByConstant(mk, sz)
+        tmp -= tmp1
+        out.append(tmp)
+    return out
+
+
+def _blendFused(pre, pre1, ks, masks, sizes):
+    """automorphBlend's fused form, or None where it does not apply (nothing has been touched then)"""
+    c, c1 = pre.ctxt, pre1.ctxt
+    ctx = c.context
+    sp = list(ctx.specialPrimes)
+    if ctx.ckks or c1.context is not ctx or pre.polyDigits is None or pre1.polyDigits is None:
+        return None
+    if set(c.parts) != {"1", "s"} or set(c1.parts) != {"1", "s"} or c.primeSet != c1.primeSet or c.primeSet & frozenset(sp):
+        return None
+    if pre.digits != pre1.digits or c.ptxtSpace != c1.ptxtSpace or c.intFactor != c1.intFactor:
+        return None
+    if c.ksw_auto is not c1.ksw_auto or c.ksw_map is not c1.ksw_map:
+        return None
+    ks = [k % ctx.m for k in ks]
+    if not ks or len(ks) > 256 or any(k == 1 or math.gcd(k, ctx.m) != 1 or c._firstStep(k) != k for k in ks):
+        return None
+    out0, out1 = c.ops.hoistedBlend(pre.polyDigits, c.parts["1"], c.parts["s"], pre1.polyDigits, c1.parts["1"],
+                                    c1.parts["s"], ks, [c.ksw_auto[k] for k in ks], masks, sp)
+    defSize = ctx.noiseBoundForMod(c.ptxtSpace, ctx.phim)       # multByConstant's size < 0
+    res = []
+    for t in range(len(ks)):
+        x = Ctxt(ctx, c.ops, c.ksw, c.ksw_ptxtSpace, c.ksw_lnNoise)
+        x.ksw_auto, x.ksw_pow, x.ksw_map, x._like = c.ksw_auto, c.ksw_pow, c.ksw_map, c._like
+        x.ptxtSpace, x.intFactor = c.ptxtSpace, c.intFactor
+        x.parts = {"1": out0[t], "s": out1[t]}
+        lsz = _ln(defSize if sizes[t] < 0.0 else sizes[t])
+        mag1 = x.ptxtMag                                        # (an automorph's ptxtMag is the constructor's)
+        ln = pre.lnNoise + lsz                                  # tmp.multByConstant(m, sz)
+        x.ptxtMag += mag1                                       # tmp += tmp1
+        ln = logaddexp(ln, pre1.lnNoise)
+        ln1 = pre1.lnNoise + lsz                                # tmp1.multByConstant(m, sz): the bound alone
+        x.ptxtMag += mag1                                       # tmp -= tmp1
+        x.lnNoise = logaddexp(ln, ln1)
+        x.primeSet = c.primeSet | frozenset(sp)
+        res.append(x)
+    return res
 
 
 # ---------------------------------------------------------------------------------------------

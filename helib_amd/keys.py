@@ -750,3 +750,7 @@ class HxBackend:
     def hoistedMaskFan(self, digits, c0, c1, ks, Ws, A, B, special):
         """capi.hoistedMaskFan: the masked, hoisted node of replicateAll in one device call"""
         return self.hx.hoistedMaskFan(digits, c0, c1, ks, Ws, A, B, special)
+
+    def hoistedBlend(self, digA, a0, a1, digB, b0, b1, ks, Ws, masks, special):
+        """capi.hoistedBlend: the masked blend of two hoisted rotations of MatMulFullExec in one device call"""
+        return self.hx.hoistedBlend(digA, a0, a1, digB, b0, b1, ks, Ws, masks, special)

@@ -772,6 +772,39 @@ int hx_hoisted_mask_fan(const hx_poly* digits, const hx_poly* c0, const hx_poly*
                         const hx_ksk* const* W, const hx_poly* const* A, const hx_poly* const* B, int n,
                         const int* sp_idx, int nsp, hx_poly* const* out0, hx_poly* const* out1);
 
+/* The hoisted blend of MatMulFullExec::rec_mul along a non-native dimension (src/matmul.cpp:2174-2204:
+ *   tmp = precon->automorph(i); tmp1 = precon1->automorph(i); tmp = tmp * m1 + tmp1 - tmp1 * m1)
+ * over the two digit decompositions (BasicAutomorphPrecon, src/matmul.cpp:48-184) of ctxt = (a0, a1) with the digit block
+ * digA and of ctxt1 = ctxt moved by g^(-ord) = (b0, b1) with digB, both as hx_break_into_digits leaves them on the
+ * operands' primes followed by sp_idx.  k, W, sp_idx are as in hx_hoisted_automorph_sum; every M[t] is required, a mask in
+ * evaluation form read at the word's own index (not gathered), of batch 1 (broadcast) or the operands' batch, on any
+ * superset of the outputs' primes in any order (rows are matched by prime index).  For every term t < n, per row, with Psp
+ * the product of the special primes modulo the row's prime and sigma_t the gather of hx_automorph by k[t]:
+ *   X0 = Psp sigma_t(a0) + sum_d sigma_t(digA_d) b[t][d]      X1 = sum_d sigma_t(digA_d) a[t][d]
+ *   Y0 = Psp sigma_t(b0) + sum_d sigma_t(digB_d) b[t][d]      Y1 = sum_d sigma_t(digB_d) a[t][d]
+ *   out0[t] = M_t X0 + Y0 - M_t Y0                            out1[t] = M_t X1 + Y1 - M_t Y1
+ * the Psp terms on the operands' own rows only.  a1 and b1 are held to the operands' shape and not read: the key switch
+ * replaces the s-part.  The 2 n outputs end up on the primes of a0 followed by sp_idx; they are overwritten, not read,
+ * pairwise distinct, and none is an input or a mask; one that still shares rows with another poly (a lazy hx_poly_copy)
+ * lets go of them first.  Every word written is canonical in [0, q) and equals, word for word, what this sequence of calls
+ * leaves per term -- for each operand a copy and hx_automorph of the digit block and of the 1-part,
+ * hx_add_primes_and_scale, a zero part and hx_key_switch_digits, then hx_mask_blend -- since all of it is exact arithmetic
+ * modulo the row's prime: the kernel blends the gathered operand words first (M x + y - M y, reduced) and multiplies the
+ * blended word by the key word, one 128-bit sum of 1 + ndig <= 256 products of residues below 2^60 per output word.
+ * Null arguments (a null M[t] included), n < 1, a k[t] outside Z_m^*, a poly or matrix of another context, mismatched
+ * batches or prime sets (a1 against a0, the second operand against the first, the digit rows against a0's primes and
+ * sp_idx, digit blocks of different length), a mask whose batch is neither 1 nor the operands', aliased outputs, an output
+ * among the inputs or masks and a W[t] with fewer digits than the blocks are HX_ERR_INVALID; a prime that a W[t] or a mask
+ * lacks is HX_ERR_PRIMESET; n > 256, more than 160 rows and an odd phi(m) are HX_ERR_UNSUPPORTED; every check comes
+ * before anything is touched, so a refused call writes nothing.  The call uploads a table of key-row addresses, so it
+ * cannot be recorded: under an open graph capture it returns HX_ERR_UNSUPPORTED before touching the device.  Asynchronous
+ * on the context's stream.  Per term the sequence makes two full key-switch passes and a blend in some twenty launches;
+ * this call reads every digit word of both blocks and every key word once per term, the mask once, and writes each output
+ * once, in two launches. */
+int hx_hoisted_blend(const hx_poly* digA, const hx_poly* a0, const hx_poly* a1, const hx_poly* digB, const hx_poly* b0,
+                     const hx_poly* b1, const uint64_t* k, const hx_ksk* const* W, const hx_poly* const* M, int n,
+                     const int* sp_idx, int nsp, hx_poly* const* out0, hx_poly* const* out1);
+
 /* ---------------- HEXL-shim compatibility layer ---------------- */
 /* Same signatures and semantics as namespace intel (src/intelExt.h:20-59):
  * host pointers, synchronous, in-place allowed.  FFTFwd / FFTRev1 are what
